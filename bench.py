@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- BLS12-377 G1 MSM throughput on MI355X (BASELINE.json metric), one process per GPU.
 
-  python bench.py --gpus 1 --steps 5 --warmup 1
-  python bench.py --only headline                       (the timed loop and its re-takes only: seconds, not minutes)
+  python bench.py --gpus 1 --steps 5 --warmup 1          (set-up, warm-up, the timed steps, the result line: nothing else)
+  python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR   (also writes the last timed step's result under DIR)
+  python bench.py --full                                (every secondary measurement below as well: minutes)
+  python bench.py --full --only headline                (the timed loop and its re-takes only: seconds, not minutes)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+Without --full a run measures the headline only: no HBM probe, no clock / power telemetry, no re-takes, no weak-scaling point, no
+CPU baseline and none of the N = 1 secondary objects.  --full restores all of them (each of --repeat, --hbm-probe, --extras,
+--also-precompute and --cpu-sample-pow may still be set on its own either way).
 
 A "step" is one MSM of 2^npow point-scalar pairs per GPU (default 2^26, BASELINE.json configs[1]) with the bases
 AND the scalars already resident in HBM: device scalars -> digits -> sort -> bucket accumulation -> bucket reduction ->
@@ -107,7 +113,7 @@ class Telemetry:
     the amdgpu hwmon files in sysfs (freq1_input / power1_average|power1_input; pp_dpm_sclk's starred level when there is no
     freq1_input), then the amdsmi Python package.  None available: every figure is None and `source` says why."""
 
-    def __init__(self, torch_device_index, hz=20.0):
+    def __init__(self, torch_device_index, hz=20.0, enabled=True):
         self.period = 1.0 / hz
         self.source = None
         self.why_not = []
@@ -115,6 +121,9 @@ class Telemetry:
         self._thread = None
         self._stop = threading.Event()
         self.samples = []
+        if not enabled:
+            self.why_not.append("not sampled (run with --full)")
+            return
         try:
             self._init_sysfs(torch_device_index)
         except Exception as e:   # never lose a bench line to telemetry
@@ -370,6 +379,15 @@ def ark_ec_probe(npow, budget_s=900):
             "sample": f"ark-ec 0.3 VariableBaseMSM::multi_scalar_mul, 2^{npow} pairs, rayon over the host's threads (rust/benches/msm.rs)",
             "gpu_equals_ark_ec": kv.get("GPU_EQUALS_ARK_EC") == "1",
             "harness_four_batches_ms": float(kv["MI355_MSM_MS_PER_4_BATCHES"]) if "MI355_MSM_MS_PER_4_BATCHES" in kv else None}
+
+
+def dump_outputs(out_dir, result, np):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the normalised projective image of the MSM
+    (144 bytes for G1, 288 for G2: X | Y | Z, each little-endian limbs as the C ABI returns them) -- as msm_result.npy, one row per
+    coordinate, one float64 per byte.  The workload is seeded, so the same arguments give the same file on every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.frombuffer(result, dtype=np.uint8).reshape(3, -1).astype(np.float64)
+    np.save(os.path.join(out_dir, "msm_result.npy"), img)
 
 
 class Env:
@@ -683,28 +701,42 @@ def main():
                          "(BASELINE.json configs[3]), otherwise unset (2^npow per GPU); 0 = never")
     ap.add_argument("--curve", default="bls12_377_g1", choices=["bls12_377_g1", "bls12_381_g1", "bls12_377_g2", "bls12_381_g2"])
     ap.add_argument("--only", default="all", choices=["all", "headline"],
-                    help="headline = the timed loop, its re-takes, telemetry and the HBM probe only (seconds): the number the driver times, "
-                         "re-taken several times per lease")
+                    help="headline = no secondary objects; with --full: the timed loop, its re-takes, telemetry and the HBM probe only "
+                         "(seconds)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (HBM probe, telemetry, re-takes, weak-scaling point, CPU baseline, host scalars, "
+                         "XYZZ, stateless, precomputed tables, other configs, small-input latency); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result of the last timed step to DIR as .npy files (float64)")
     ap.add_argument("--repeat", type=int, default=-1,
-                    help="re-take the K-step timed loop this many more times (`headline_samples`); default 2 at N = 1 (4 with --only headline), 0 otherwise")
-    ap.add_argument("--cpu-sample-pow", type=int, default=26,
-                    help="log2 pairs of the CPU-baseline sample (0 = skip); 26 = the whole workload once, about a minute of host time")
-    ap.add_argument("--extras", type=int, default=1,
+                    help="re-take the K-step timed loop this many more times (`headline_samples`); default with --full 2 at N = 1 "
+                         "(4 with --only headline), 0 otherwise")
+    ap.add_argument("--cpu-sample-pow", type=int, default=-1,
+                    help="log2 pairs of the CPU-baseline sample (0 = skip); default 26 with --full (the whole workload once, about a minute "
+                         "of host time), 0 otherwise")
+    ap.add_argument("--extras", type=int, default=-1,
                     help="at N = 1 also measure, in the same run, SURVEY 8(d)'s primary metric and its neighbours: scalars in HOST memory "
-                         "(1 and 4 batches, pageable and pinned), the XYZZ group law on BLS12-377, one stateless mi355_msm() call")
+                         "(1 and 4 batches, pageable and pinned), the XYZZ group law on BLS12-377, one stateless mi355_msm() call; "
+                         "default 1 with --full, 0 otherwise")
     ap.add_argument("--logical-shards", type=int, default=0,
                     help="single-process --gpus N on a box with fewer GPUs: place the N shards on the visible devices round-robin")
     ap.add_argument("--precompute", type=int, default=0, help="1 = context with precomputed 2^(c w) P tables (row f1; init untimed); 2 = auto")
-    ap.add_argument("--also-precompute", type=int, default=1,
-                    help="at N = 1 also time contexts with precomputed tables (reported as a secondary object, never as `value`)")
+    ap.add_argument("--also-precompute", type=int, default=-1,
+                    help="at N = 1 also time contexts with precomputed tables (reported as a secondary object, never as `value`); "
+                         "default 1 with --full, 0 otherwise")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for --gpus > 1 (nccl = RCCL over xGMI; gloo only to rehearse the multi-rank path on one GPU)")
     ap.add_argument("--window-bits", type=int, default=0)
     ap.add_argument("--lane-entries", type=int, default=0)
     ap.add_argument("--assume-subgroup", type=int, default=0,
                     help="1 = context option assume_subgroup (scalars above r/2 run as (r - k)(-P): the winners' top-bit trick, valid for bases in the r-torsion)")
-    ap.add_argument("--hbm-probe", type=int, default=1, help="0 = skip the device-to-device copy probe (roofline.peak_measured)")
+    ap.add_argument("--hbm-probe", type=int, default=-1,
+                    help="1 = run the device-to-device copy probe (roofline.peak_measured); default 1 with --full, 0 otherwise")
     args = ap.parse_args()
+    # -1 = the option's value follows --full
+    for name, with_full in (("cpu_sample_pow", 26), ("extras", 1), ("also_precompute", 1), ("hbm_probe", 1)):
+        if getattr(args, name) < 0:
+            setattr(args, name, with_full if args.full else 0)
     headline_only = args.only == "headline"
     if headline_only:
         args.extras = args.also_precompute = args.cpu_sample_pow = 0
@@ -736,7 +768,7 @@ def main():
             dist.init_process_group(backend="gloo")
     coll_device = device if args.backend == "nccl" else None
     single = world == 1 and not c_sharded
-    repeat = args.repeat if args.repeat >= 0 else ((4 if headline_only else 2) if single else 0)
+    repeat = args.repeat if args.repeat >= 0 else ((4 if headline_only else 2) if (single and args.full) else 0)
 
     cid = ea.CURVE_IDS[args.curve]
     n_ranks = args.gpus if c_sharded else world
@@ -749,14 +781,15 @@ def main():
     if total_npow:
         if n_ranks & (n_ranks - 1) or (1 << total_npow) < n_ranks:
             raise SystemExit("--total-npow needs a power-of-two number of GPUs")
-        weak_secondary = args.npow if args.total_npow < 0 else None      # the default N = 8 line also carries the weak-scaling point
+        # the default N = 8 line also carries the weak-scaling point (--full)
+        weak_secondary = args.npow if (args.total_npow < 0 and args.full) else None
         args.npow = total_npow - (n_ranks.bit_length() - 1)
     n = 1 << args.npow
     distinct = min(n, 1 << 15)
 
     # the box's own HBM rate, before the workload takes the memory (rank 0 of a single-GPU run: the probe is about the chip, not the job)
     probe = hbm_probe(torch, device) if (single and args.hbm_probe) else None
-    telemetry = Telemetry(local_rank)
+    telemetry = Telemetry(local_rank, enabled=args.full)
 
     # synthetic inputs in the reference generator's shape: 2^15 distinct subgroup points replicated to n,
     # uniform scalars below r; every rank has its own slice of the global problem (different scalars per rank)
@@ -835,6 +868,8 @@ def main():
         dt_r, res_r, _, acc_r, launches_r, _, tele_r = timed_loop()
         samples.append({"ms_per_step": dt_r / args.steps * 1e3, "accumulate_ms": acc_r / max(launches_r, 1), "clock_MHz_mean": tele_r["clock_MHz_mean"],
                         "power_W_mean": tele_r["power_W_mean"], "same_result": res_r == result})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result, np)
     per_rank = None
     if world > 1:
         my_elapsed = elapsed
@@ -972,6 +1007,7 @@ def main():
                        "group_law": "extended twisted Edwards (7M mixed add)" if ctx_te_path else "XYZZ (8M+2S mixed add)",
                        "g2_paired": g2_paired,
                        "init_s": t_init,
+                       "full": args.full,
                        "clock_MHz_mean": tele["clock_MHz_mean"], "clock_MHz_min": tele["clock_MHz_min"], "clock_MHz_max": tele["clock_MHz_max"],
                        "power_W_mean": tele["power_W_mean"], "power_W_max": tele["power_W_max"], "telemetry_samples": tele["samples"],
                        "telemetry_source": telemetry.describe(),

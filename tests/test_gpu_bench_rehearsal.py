@@ -52,7 +52,7 @@ def test_driver_command_shape_multi_rank(built, n):
     port = 29900 + (os.getpid() + n) % 500
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), "bench.py", "--gpus", str(n), "--backend", "gloo", "--npow", str(NPOW), "--steps", "2", "--warmup", "1",
-           "--cpu-sample-pow", "0"]
+           "--cpu-sample-pow", "0", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = _line(r.stdout)
@@ -75,7 +75,7 @@ def test_driver_command_shape_multi_rank(built, n):
 def test_driver_command_shape_single_process_sharded(built):
     """`python bench.py --gpus 8` without a launcher: one process, eight shards behind the C ABI (here all on device 0)."""
     cmd = [sys.executable, "bench.py", "--gpus", "8", "--logical-shards", "1", "--npow", str(NPOW), "--steps", "2", "--warmup", "1",
-           "--cpu-sample-pow", "0"]
+           "--cpu-sample-pow", "0", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = _line(r.stdout)
@@ -90,7 +90,7 @@ def test_driver_command_shape_single_process_sharded(built):
 def test_default_single_gpu_line_small(built):
     """The N = 1 shape with every secondary measurement switched on, at a size that finishes in seconds: the line must carry
     `roofline`, `cpu_baseline`, the host-scalar figures and the stateless call without an `error` member anywhere."""
-    cmd = [sys.executable, "bench.py", "--npow", "18", "--steps", "2", "--warmup", "1", "--cpu-sample-pow", "14", "--also-precompute", "1"]
+    cmd = [sys.executable, "bench.py", "--npow", "18", "--steps", "2", "--warmup", "1", "--cpu-sample-pow", "14", "--also-precompute", "1", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = _line(r.stdout)
@@ -99,3 +99,34 @@ def test_default_single_gpu_line_small(built):
     assert line["cpu_baseline"]["gpu_matches_cpu_on_sample"] is True
     assert "error" not in json.dumps(line["survey_8d_metrics"]), line["survey_8d_metrics"]
     assert "error" not in line["with_precomputed_tables"], line["with_precomputed_tables"]
+
+
+def test_plain_line_is_the_headline_only_and_dumps_its_result(built, oracle, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: exactly K timed steps, the headline fields, none of the secondary objects;
+    --dump-outputs writes the last timed step's result, which is the CPU oracle's MSM of the same seeded workload."""
+    import numpy as np
+
+    import bench
+    import entries_amd as ea
+    from conftest import oracle_msm_np
+
+    npow = 16
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--npow", str(npow), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    line = _line(r.stdout)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["config"]["full"] is False
+    assert line["metric"] == "BLS12-377 G1 MSM point-scalar pairs/s" and line["unit"] == "pairs/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "u32" and abs(line["value"] - (1 << npow) / line["ms_per_step"] * 1e3) <= 1e-6 * line["value"]
+    for k in ("cpu_baseline", "survey_8d_metrics", "host_scalars_ms_per_msm", "with_precomputed_tables", "secondary_configs", "small_input_latency"):
+        assert k not in line, k
+    assert len(line["headline_samples"]["ms_per_step"]) == 1 and line["roofline"]["peak_probe"] is None
+    assert line["config"]["telemetry_samples"] == 0
+    img = np.load(tmp_path / "msm_result.npy")
+    assert img.dtype == np.float64 and img.shape == (3, 48)
+    # the workload bench.py builds (seeded): 2^15 distinct points replicated, uniform scalars below r from the device generator
+    n, distinct = 1 << npow, 1 << 15
+    tile = ea.generate_points(distinct, distinct=distinct, seed=0x5A5052495A45, curve="bls12_377_g1")
+    bases = np.ascontiguousarray(np.tile(tile, (n // distinct, 1)))
+    scalars = np.ascontiguousarray(bench.uniform_scalars(n, bench.R377_TOP, "cuda:0", seed=1234).cpu().numpy())
+    assert img.astype(np.uint8).tobytes() == oracle_msm_np(oracle, 0, bases, scalars, n)

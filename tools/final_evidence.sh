@@ -6,9 +6,9 @@ python tools/make_pmc_json.py gpurun_out/prof > /dev/null 2>&1; cp profiles/r02_
 cp $(find gpurun_out/prof/stats -name "*kernel_stats.csv" | head -1) $D/kernel_stats.csv 2>/dev/null
 OUT=gpurun_out/prof_g2 NPOW=24 EXTRA="--curve bls12_377_g2" bash tools/profile_gpu.sh > $D/rocprof_summary_g2.txt 2>&1
 python tools/make_pmc_json.py gpurun_out/prof_g2 $D/pmc_k_accumulate_g2.json 13 24 20 "bls12_377_g2 npow=24 (c = 20, 13 windows): the k_accumulate_glds<SwLaw<Fp2El>> launch of a bench step, XYZZ over Fp2, one wave per SIMD" > /dev/null 2>&1
-python bench.py 2>/dev/null | tail -1 > $D/bench.json
-python bench.py --curve bls12_381_g1 --extras 0 2>/dev/null | tail -1 > $D/bench_381.json
-python bench.py --curve bls12_377_g2 --npow 24 --extras 0 2>/dev/null | tail -1 > $D/bench_g2.json
+python bench.py --full 2>/dev/null | tail -1 > $D/bench.json
+python bench.py --full --curve bls12_381_g1 --extras 0 2>/dev/null | tail -1 > $D/bench_381.json
+python bench.py --full --curve bls12_377_g2 --npow 24 --extras 0 2>/dev/null | tail -1 > $D/bench_g2.json
 python tools/size_sweep.py 2>/dev/null | grep "^2\^" > $D/size_sweep.txt
 python tools/host_rate.py 2>/dev/null | grep -v amdgpu.ids > $D/host_rate.txt
 python tools/fuzz_gpu.py 400 2>&1 | tail -3 > $D/fuzz.txt

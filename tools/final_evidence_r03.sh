@@ -16,8 +16,10 @@ for t in "prof 377 " "prof_381 381 _381" "prof_g2 g2 _g2"; do
   cp gpurun_out/r03_pmc_k_accumulate${3:-}.json profiles/
 done
 python -m pytest tests -m gpu -q 2>&1 | grep -v "^RCCL\|^HIP\|^ROCm\|^Hostname\|^Librccl" | tail -4 > gpurun_out/r03_pytest_gpu.txt
-python bench.py > gpurun_out/r03_bench.json 2> gpurun_out/r03_bench.err
-python bench.py --curve bls12_381_g1 --cpu-sample-pow 22 > gpurun_out/r03_bench_381.json 2>> gpurun_out/r03_bench.err
-python bench.py --curve bls12_377_g2 --npow 24 --cpu-sample-pow 20 > gpurun_out/r03_bench_g2.json 2>> gpurun_out/r03_bench.err
+BENCH_OUT=${BENCH_OUT:-build/evidence}   # where the bench lines are written
+mkdir -p $BENCH_OUT
+python bench.py --full > $BENCH_OUT/r03_bench.json 2> $BENCH_OUT/r03_bench.err
+python bench.py --full --curve bls12_381_g1 --cpu-sample-pow 22 > $BENCH_OUT/r03_bench_381.json 2>> $BENCH_OUT/r03_bench.err
+python bench.py --full --curve bls12_377_g2 --npow 24 --cpu-sample-pow 20 > $BENCH_OUT/r03_bench_g2.json 2>> $BENCH_OUT/r03_bench.err
 find gpurun_out -name "*.csv" -size +2M -delete
 cat gpurun_out/r03_calib_fetch.txt; tail -3 gpurun_out/r03_pytest_gpu.txt

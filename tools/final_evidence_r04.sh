@@ -4,21 +4,23 @@
 #   profiles/r03_calib_fetch.txt), the GPU suite, the bench lines.
 set -u
 cd "$(dirname "$0")/.."
-OUT=gpurun_out/prof bash tools/profile_gpu.sh > /dev/null 2>&1
-EXTRA="--curve bls12_381_g1" OUT=gpurun_out/prof_381 bash tools/profile_gpu.sh > /dev/null 2>&1
-EXTRA="--curve bls12_377_g2" NPOW=24 OUT=gpurun_out/prof_g2 bash tools/profile_gpu.sh > /dev/null 2>&1
+OUT_DIR=${OUT_DIR:-build/evidence}   # where the evidence files are written
+mkdir -p $OUT_DIR
+OUT=$OUT_DIR/prof bash tools/profile_gpu.sh > /dev/null 2>&1
+EXTRA="--curve bls12_381_g1" OUT=$OUT_DIR/prof_381 bash tools/profile_gpu.sh > /dev/null 2>&1
+EXTRA="--curve bls12_377_g2" NPOW=24 OUT=$OUT_DIR/prof_g2 bash tools/profile_gpu.sh > /dev/null 2>&1
 for t in "prof 377 " "prof_381 381 _381" "prof_g2 g2 _g2"; do
   set -- $t
-  python tools/make_pmc_json.py gpurun_out/$1 gpurun_out/r04_pmc_k_accumulate${3:-}.json $2 profiles/r03_calib_fetch.txt > /dev/null 2>&1
-  cp gpurun_out/$1/summary.txt gpurun_out/r04_rocprof_summary${3:-}.txt
+  python tools/make_pmc_json.py $OUT_DIR/$1 $OUT_DIR/r04_pmc_k_accumulate${3:-}.json $2 profiles/r03_calib_fetch.txt > /dev/null 2>&1
+  cp $OUT_DIR/$1/summary.txt $OUT_DIR/r04_rocprof_summary${3:-}.txt
   # bench.py quotes roofline.traffic from profiles/ when the counters were measured on the kernel sources AND the plan it runs: these were
-  cp gpurun_out/r04_pmc_k_accumulate${3:-}.json profiles/
+  cp $OUT_DIR/r04_pmc_k_accumulate${3:-}.json profiles/
 done
-cp $(find gpurun_out/prof/stats -name "*kernel_stats.csv" | head -1) gpurun_out/r04_kernel_stats.csv 2>/dev/null
-python -m pytest tests -m gpu -q 2>&1 | grep -v "^RCCL\|^HIP\|^ROCm\|^Hostname\|^Librccl" | tail -4 > gpurun_out/r04_pytest_gpu.txt
-python bench.py > gpurun_out/r04_bench.json 2> gpurun_out/r04_bench.err
-python bench.py --curve bls12_381_g1 --cpu-sample-pow 22 --also-precompute 0 > gpurun_out/r04_bench_381.json 2>> gpurun_out/r04_bench.err
-python bench.py --curve bls12_377_g2 --npow 24 --cpu-sample-pow 20 > gpurun_out/r04_bench_g2.json 2>> gpurun_out/r04_bench.err
-python bench.py --curve bls12_381_g2 --npow 24 --cpu-sample-pow 20 > gpurun_out/r04_bench_381g2.json 2>> gpurun_out/r04_bench.err
-find gpurun_out -name "*.csv" -size +2M -delete
-tail -3 gpurun_out/r04_pytest_gpu.txt; tail -c 600 gpurun_out/r04_bench.json
+cp $(find $OUT_DIR/prof/stats -name "*kernel_stats.csv" | head -1) $OUT_DIR/r04_kernel_stats.csv 2>/dev/null
+python -m pytest tests -m gpu -q 2>&1 | grep -v "^RCCL\|^HIP\|^ROCm\|^Hostname\|^Librccl" | tail -4 > $OUT_DIR/r04_pytest_gpu.txt
+python bench.py --full > $OUT_DIR/r04_bench.json 2> $OUT_DIR/r04_bench.err
+python bench.py --full --curve bls12_381_g1 --cpu-sample-pow 22 --also-precompute 0 > $OUT_DIR/r04_bench_381.json 2>> $OUT_DIR/r04_bench.err
+python bench.py --full --curve bls12_377_g2 --npow 24 --cpu-sample-pow 20 > $OUT_DIR/r04_bench_g2.json 2>> $OUT_DIR/r04_bench.err
+python bench.py --full --curve bls12_381_g2 --npow 24 --cpu-sample-pow 20 > $OUT_DIR/r04_bench_381g2.json 2>> $OUT_DIR/r04_bench.err
+find $OUT_DIR -name "*.csv" -size +2M -delete
+tail -3 $OUT_DIR/r04_pytest_gpu.txt; tail -c 600 $OUT_DIR/r04_bench.json
