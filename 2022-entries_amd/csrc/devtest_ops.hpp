@@ -8,6 +8,7 @@
 // SPK ec/xyzz_t.hpp:178-249).  Test scaffolding: nothing in the engine links it.
 #pragma once
 #include "curve.hpp"
+#include "digits.hpp"
 #include "te.hpp"
 
 namespace msm {
@@ -34,7 +35,9 @@ enum DevtestOp : int {
   DT_ADD_QUAD = 18,     // as DT_ADD, four lanes per record (device only)
   DT_TE_ADD_QUAD = 19,  // as DT_TE_ADD, four lanes per record (device only)
   DT_FE_WEAK_REDUCE = 20,    // in a (limbs < 2^31, value < 32p)  out Fe
-  DT_COUNT = 21,
+  DT_FR_FROM_MONT = 21, // in 8 words (any 256-bit integer)   out 8 words   fr_from_montgomery of the curve's scalar field (digits.hpp)
+  DT_FR_TO_MONT = 22,   // in 8 words (any 256-bit integer)   out 8 words   fr_to_montgomery
+  DT_COUNT = 23,
   DT_PAIR = 64          // + a G2 op in [DT_EL_MUL, DT_DBL]: the same records with two lanes per record (fp2pair.hpp; device only)
 };
 
@@ -56,6 +59,7 @@ MSM_HD void devtest_shape(int op, int EW, int& in_words, int& out_words) {
     case DT_TE_ADD: case DT_TE_ADD_QUAD: in_words = 8 * NL; out_words = 4 * NL; break;
     case DT_TE_DBL: in_words = 4 * NL; out_words = 4 * NL; break;
     case DT_FE_WEAK_REDUCE: in_words = NL; out_words = NL; break;
+    case DT_FR_FROM_MONT: case DT_FR_TO_MONT: in_words = 8; out_words = 8; break;
     default: break;
   }
 }
@@ -110,6 +114,14 @@ MSM_HD void devtest_apply(const uint32_t* in, uint32_t* out) {
     dt_store(out, r);
   } else if constexpr (OP == DT_NOT_AND_LMASK) {
     out[0] = not_and_lmask(in[0]);
+  } else if constexpr (OP == DT_FR_FROM_MONT || OP == DT_FR_TO_MONT) {
+    uint32_t v[8];
+    for (int j = 0; j < 8; j++) v[j] = in[j];
+    if constexpr (OP == DT_FR_FROM_MONT)
+      fr_from_montgomery<typename C::FR>(v);
+    else
+      fr_to_montgomery<typename C::FR>(v);
+    for (int j = 0; j < 8; j++) out[j] = v[j];
   } else if constexpr (OP == DT_FE_WEAK_REDUCE) {
     Fe a;
     dt_load(a, in);

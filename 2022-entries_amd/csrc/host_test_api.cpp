@@ -504,6 +504,8 @@ static int t_devop(int op, const uint32_t* in, int iw, uint32_t* out, int ow, si
       DT_CASE(DT_FE_MUL2)
       DT_CASE(DT_NOT_AND_LMASK)
       DT_CASE(DT_FE_WEAK_REDUCE)
+      DT_CASE(DT_FR_FROM_MONT)
+      DT_CASE(DT_FR_TO_MONT)
       DT_CASE(DT_EL_MUL)
       DT_CASE(DT_EL_SQR)
       DT_CASE(DT_EL_MUL_C)

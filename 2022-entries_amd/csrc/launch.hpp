@@ -74,9 +74,9 @@ struct LaunchTe {
 };
 
 // Bucket grouping (partition.hip): digits + MSD partition of the (key, value) entries.  scalar_field: 0 = BLS12-377 Fr, 1 = BLS12-381 Fr
-// (only the Montgomery conversion depends on it).  Returns the index of the entry buffer that holds the sorted entries.
+// (only the Montgomery conversions depend on it); scalar_mode: a ScalarMode of digits.hpp.  Returns the index of the entry buffer that holds the sorted entries.
 struct PartLaunch {
-  static int run(int scalar_field, bool montgomery, const uint32_t* d_scalars, const uint8_t* d_inf, const PartPlan& p, const PartBuffers& b,
+  static int run(int scalar_field, int scalar_mode, const uint32_t* d_scalars, const uint8_t* d_inf, const PartPlan& p, const PartBuffers& b,
                  hipStream_t st, hipEvent_t mid, hipError_t& err);
   // -DMSM_DEBUG builds only (otherwise a no-op that reports nothing): the slot-key check after the accumulation, then the stream is
   // synchronised and the violation counters of this chunk are read -- what[] names the first violated invariant, empty = all held.

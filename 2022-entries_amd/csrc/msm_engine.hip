@@ -371,6 +371,7 @@ struct mi355_msm_ctx {
   size_t pinned_bytes = 0;
   hipEvent_t ev[8] = {};
   long opt_window_bits = 0, opt_lane_entries = 0, opt_max_chunk = 0, opt_seg_entries = 0, opt_scalars_montgomery = 0, opt_reduce_scan_log = 0;
+  long opt_scalars_to_montgomery = 0;   // 1: every scalar a runs as a * 2^256 mod r (normal-form `scalars.bin` integers, digits.hpp)
   long opt_precompute = 0;
   long opt_table_levels = 0;      // with precompute: table levels k (0 = one per window); windows g, g + G, ... share bucket set g
   long opt_assume_subgroup = 0;   // 1: every base is in the order-r subgroup (r P = O), so a scalar k in (r/2, r) may run as (r - k)(-P)
@@ -1134,7 +1135,8 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
   gb.counts = ctx->part_counts.as<uint32_t>();
   gb.totals = ctx->part_totals.as<uint32_t>();
   hipError_t gerr = hipSuccess;
-  const int sorted = PartLaunch::run((ctx->curve == MI355_BLS12_381_G1 || ctx->curve == MI355_BLS12_381_G2) ? 1 : 0, ctx->opt_scalars_montgomery != 0, d_scalars, inf, gp, gb, st,
+  const int scalar_mode = ctx->opt_scalars_montgomery ? SCALARS_FROM_MONT : ctx->opt_scalars_to_montgomery ? SCALARS_TO_MONT : SCALARS_PLAIN;
+  const int sorted = PartLaunch::run((ctx->curve == MI355_BLS12_381_G1 || ctx->curve == MI355_BLS12_381_G2) ? 1 : 0, scalar_mode, d_scalars, inf, gp, gb, st,
                                      ev[1], gerr);
   HIP_OK(gerr);
   const uint2* entries = gb.entries[sorted];
@@ -2188,7 +2190,11 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value) 
       if (value < 0 || value > 64) bad_arg("table_levels %ld out of range [0, 64]", value);
       ctx->opt_table_levels = value;
     } else if (k == "scalars_montgomery") {
+      if (value != 0 && ctx->opt_scalars_to_montgomery) bad_arg("scalars_montgomery and scalars_to_montgomery exclude each other");
       ctx->opt_scalars_montgomery = value != 0;
+    } else if (k == "scalars_to_montgomery") {
+      if (value != 0 && ctx->opt_scalars_montgomery) bad_arg("scalars_to_montgomery and scalars_montgomery exclude each other");
+      ctx->opt_scalars_to_montgomery = value != 0;
     } else if (k == "assume_subgroup") {
       ctx->opt_assume_subgroup = value != 0;
     } else if (k == "carry") {

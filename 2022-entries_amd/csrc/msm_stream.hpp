@@ -24,7 +24,7 @@ struct mi355_msm_stream {
   std::vector<uint8_t> bases, scalars; // the buffered pairs, `stride` and 32 bytes each
   std::unordered_map<std::string, size_t> index;   // hashmap mode: affine image -> position in the buffers
   std::vector<uint8_t> result;         // normalised Projective image of everything flushed so far
-  long opt_scalars_montgomery = 0, opt_window_bits = 0;
+  long opt_scalars_montgomery = 0, opt_scalars_to_montgomery = 0, opt_window_bits = 0;
   uint64_t flushes = 0, merged = 0;
 };
 
@@ -93,13 +93,14 @@ void stream_flush(mi355_msm_stream* s) {
     struct Restore {
       mi355_msm_ctx* c;
       ~Restore() {
-        for (const char* k : {"scalars_montgomery", "window_bits", "assume_subgroup"}) {
+        for (const char* k : {"scalars_montgomery", "scalars_to_montgomery", "window_bits", "assume_subgroup"}) {
           RustError e = mi355_msm_set_option(c, k, 0);
           if (e.message) free(e.message);
         }
       }
     } restore{ws.ctx};
     take(mi355_msm_set_option(ws.ctx, "scalars_montgomery", s->opt_scalars_montgomery));
+    take(mi355_msm_set_option(ws.ctx, "scalars_to_montgomery", s->opt_scalars_to_montgomery));
     take(mi355_msm_set_option(ws.ctx, "window_bits", s->opt_window_bits));
     // (a pooled context keeps whatever the last stateless call set: the accumulators are exact for any curve point unless the
     //  environment says the bases are in the subgroup, as for mi355_msm -- ADVICE r4)
@@ -174,9 +175,13 @@ RustError mi355_msm_stream_set_option(mi355_msm_stream* s, const char* key, long
   return guarded([&] {
     if (!s || !key) bad_arg("null argument");
     const std::string k(key);
-    if (k == "scalars_montgomery")
+    if (k == "scalars_montgomery") {
+      if (value != 0 && s->opt_scalars_to_montgomery) bad_arg("scalars_montgomery and scalars_to_montgomery exclude each other");
       s->opt_scalars_montgomery = value != 0;
-    else if (k == "window_bits") {
+    } else if (k == "scalars_to_montgomery") {
+      if (value != 0 && s->opt_scalars_montgomery) bad_arg("scalars_to_montgomery and scalars_montgomery exclude each other");
+      s->opt_scalars_to_montgomery = value != 0;
+    } else if (k == "window_bits") {
       if (value != 0 && (value < 2 || value > 24)) bad_arg("window_bits %ld out of range [2, 24]", value);
       s->opt_window_bits = value;
     } else

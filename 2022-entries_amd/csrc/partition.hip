@@ -1,17 +1,21 @@
-// partition.hip -- the bucket-grouping kernels (partition.hpp) instantiated for the two scalar fields, with and without the
-// Fr-Montgomery entry (row f3).  Curve-independent otherwise; its own translation unit so that it compiles in parallel.
+// partition.hip -- the bucket-grouping kernels (partition.hpp) instantiated for the two scalar fields and the three scalar modes
+// of digits.hpp (plain integers; from Fr-Montgomery form, row f3; to Fr-Montgomery form).  Curve-independent otherwise; its own
+// translation unit so that it compiles in parallel.
 #include "launch.hpp"
 #include "partition.hpp"
 
 namespace msm {
 
-int PartLaunch::run(int scalar_field, bool montgomery, const uint32_t* d_scalars, const uint8_t* d_inf, const PartPlan& p, const PartBuffers& b,
+int PartLaunch::run(int scalar_field, int scalar_mode, const uint32_t* d_scalars, const uint8_t* d_inf, const PartPlan& p, const PartBuffers& b,
                     hipStream_t st, hipEvent_t mid, hipError_t& err) {
-  if (scalar_field == 1)
-    return montgomery ? part_run<Bls12_381_Fr, true>(d_scalars, d_inf, p, b, st, mid, err)
-                      : part_run<Bls12_381_Fr, false>(d_scalars, d_inf, p, b, st, mid, err);
-  return montgomery ? part_run<Bls12_377_Fr, true>(d_scalars, d_inf, p, b, st, mid, err)
-                    : part_run<Bls12_377_Fr, false>(d_scalars, d_inf, p, b, st, mid, err);
+  if (scalar_field == 1) {
+    if (scalar_mode == SCALARS_FROM_MONT) return part_run<Bls12_381_Fr, SCALARS_FROM_MONT>(d_scalars, d_inf, p, b, st, mid, err);
+    if (scalar_mode == SCALARS_TO_MONT) return part_run<Bls12_381_Fr, SCALARS_TO_MONT>(d_scalars, d_inf, p, b, st, mid, err);
+    return part_run<Bls12_381_Fr, SCALARS_PLAIN>(d_scalars, d_inf, p, b, st, mid, err);
+  }
+  if (scalar_mode == SCALARS_FROM_MONT) return part_run<Bls12_377_Fr, SCALARS_FROM_MONT>(d_scalars, d_inf, p, b, st, mid, err);
+  if (scalar_mode == SCALARS_TO_MONT) return part_run<Bls12_377_Fr, SCALARS_TO_MONT>(d_scalars, d_inf, p, b, st, mid, err);
+  return part_run<Bls12_377_Fr, SCALARS_PLAIN>(d_scalars, d_inf, p, b, st, mid, err);
 }
 
 hipError_t PartLaunch::debug_finish(const PartPlan& p, const PartBuffers& b, const uint32_t* slot_keys, uint32_t nslots, hipStream_t st, char* what,

@@ -177,12 +177,29 @@ __device__ __forceinline__ bool fold_decision(const ScalarDigits& st) {
   return st.s[7] > (FR::R[7] >> 1) && st.s[7] < FR::R[7];
 }
 
-template <class FR, bool MONT>
+// fr_to_montgomery as a real call: k_l1_scatter keeps its tile of eight scalars in registers (126 VGPRs in every mode), and inlined
+// eight times the conversion's second operand row let the scheduler interleave them into 134 spilled VGPRs.  Behind a call the
+// kernel stays at 126 VGPRs with no scratch (tests/test_isa.py); the 8 words travel in registers both ways.
+struct ScalarWords {
+  uint32_t w[8];
+};
+template <class FR>
+__device__ __noinline__ ScalarWords fr_to_montgomery_call(ScalarWords a) {
+  fr_to_montgomery<FR>(a.w);
+  return a;
+}
+
+template <class FR, int MODE>
 __device__ __forceinline__ void load_scalar(ScalarDigits& st, const uint32_t* __restrict__ scalars, uint32_t i) {
   const uint4* sp = reinterpret_cast<const uint4*>(scalars) + 2 * (size_t)i;
   const uint4 lo = sp[0], hi = sp[1];
   uint32_t s[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  if (MONT) fr_from_montgomery<FR>(s);
+  if constexpr (MODE == SCALARS_FROM_MONT) fr_from_montgomery<FR>(s);
+  if constexpr (MODE == SCALARS_TO_MONT) {
+    const ScalarWords w = fr_to_montgomery_call<FR>(ScalarWords{{s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7]}});
+#pragma unroll
+    for (int j = 0; j < 8; j++) s[j] = w.w[j];
+  }
 #pragma unroll
   for (int j = 0; j < 8; j++) st.s[j] = s[j];
   st.carry = 0;
@@ -249,7 +266,7 @@ __device__ __forceinline__ uint32_t l1_bin(const PartPlan& p, uint32_t w, uint32
 
 // ------------------------------------------------------------------------------------------------------------------------
 // L1 histogram: one block per tile, matrix row = the tile's entry count per level-1 bin.
-template <class FR, bool MONT, bool FOLD>
+template <class FR, int MODE, bool FOLD>
 __global__ void __launch_bounds__(PART_THREADS) k_l1_hist(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf, PartPlan p,
                                                           uint32_t* __restrict__ matrix) {
   extern __shared__ uint32_t hist[];   // nbins
@@ -270,7 +287,7 @@ __global__ void __launch_bounds__(PART_THREADS) k_l1_hist(const uint32_t* __rest
     ScalarDigits st;
     bool flip = false;
     if (have) {
-      load_scalar<FR, MONT>(st, scalars, i);
+      load_scalar<FR, MODE>(st, scalars, i);
       if (FOLD) flip = fold_decision<FR>(st);
     } else {
 #pragma unroll
@@ -428,7 +445,7 @@ __global__ void __launch_bounds__(256) k_l1_merge_shared(const PartSeg* __restri
 
 // L1 scatter: one block per tile; the tile's scalars stay in registers while the windows are processed one after the other.
 // LDS: stage (8192 x u64; the bin rides in the high half of the key word until the entry leaves) + three (b1 + 1)-word arrays.
-template <class FR, bool MONT, bool FOLD>
+template <class FR, int MODE, bool FOLD>
 __global__ void __launch_bounds__(PART_THREADS) k_l1_scatter(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf, PartPlan p,
                                                              const uint32_t* __restrict__ matrix, uint2* __restrict__ out) {
   __shared__ uint2 stage[PART_TILE];
@@ -449,7 +466,7 @@ __global__ void __launch_bounds__(PART_THREADS) k_l1_scatter(const uint32_t* __r
   for (int k = 0; k < PART_PER_THREAD; k++) {
     const uint32_t i = i0 + threadIdx.x + k * PART_THREADS;
     if (i < p.n) {
-      load_scalar<FR, MONT>(st[k], scalars, i);
+      load_scalar<FR, MODE>(st[k], scalars, i);
       if (p.table_stride || inf[p.idx0 + i] == 0) alive |= 1u << k;   // (with tables the flag is read per level, below)
     } else {
 #pragma unroll
@@ -858,14 +875,14 @@ namespace msm {
 enum { DBG_DIGITS = 0, DBG_SEG_GAP = 1, DBG_SEG_END = 2, DBG_KEY_BITS = 3, DBG_UNSORTED = 4, DBG_KEY_RANGE = 5, DBG_VALUE_RANGE = 6,
        DBG_SLOT_KEY = 7, DBG_CHECKS = 8, DBG_WORDS = 12 };
 
-template <class FR, bool MONT, bool FOLD>
+template <class FR, int MODE, bool FOLD>
 __global__ void __launch_bounds__(256) k_dbg_count_digits(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf, PartPlan p,
                                                           uint32_t* __restrict__ dbg) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   uint32_t count = 0;
   if (i < p.n) {
     ScalarDigits st;
-    load_scalar<FR, MONT>(st, scalars, i);
+    load_scalar<FR, MODE>(st, scalars, i);
     const bool flip = FOLD ? fold_decision<FR>(st) : false;
     const uint32_t wmask = (1u << p.c) - 1;
     for (uint32_t w = 0; w < p.windows; w++) {
@@ -952,7 +969,7 @@ struct PartProbe {
 
 // Enqueues the whole grouping on `st`; returns the index (0/1) of the entry buffer that holds the result.
 // `mid` (optional) is recorded after level 1 so the caller can time the two halves.
-template <class FR, bool MONT>
+template <class FR, int MODE>
 inline int part_run(const uint32_t* d_scalars, const uint8_t* d_inf, const PartPlan& p, const PartBuffers& b, hipStream_t st,
                     hipEvent_t mid, hipError_t& err, PartProbe* probe = nullptr) {
   err = hipSuccess;
@@ -975,9 +992,9 @@ inline int part_run(const uint32_t* d_scalars, const uint8_t* d_inf, const PartP
   const dim3 scan_grid(part_ceil_div(p.nbins, 256), PART_SCAN_GROUPS);
   const uint32_t l1_grid = 8 * ((p.ntiles + 7) / 8) * p.wgroups;   // l1_tile(): a contiguous tile range per XCD; wgroups blocks per tile
   if (p.fold)
-    hipLaunchKernelGGL((k_l1_hist<FR, MONT, true>), dim3(l1_grid), dim3(PART_THREADS), p.nbins * 4, st, d_scalars, d_inf, p, b.matrix);
+    hipLaunchKernelGGL((k_l1_hist<FR, MODE, true>), dim3(l1_grid), dim3(PART_THREADS), p.nbins * 4, st, d_scalars, d_inf, p, b.matrix);
   else
-    hipLaunchKernelGGL((k_l1_hist<FR, MONT, false>), dim3(l1_grid), dim3(PART_THREADS), p.nbins * 4, st, d_scalars, d_inf, p, b.matrix);
+    hipLaunchKernelGGL((k_l1_hist<FR, MODE, false>), dim3(l1_grid), dim3(PART_THREADS), p.nbins * 4, st, d_scalars, d_inf, p, b.matrix);
   PART_MARK("l1_hist");
   hipLaunchKernelGGL(k_l1_scan_a, scan_grid, dim3(256), 0, st, b.matrix, p, b.partial);
   hipLaunchKernelGGL(k_l1_scan_b, dim3(1), dim3(1024), 0, st, b.partial, p, b.segs[0], b.subjob_first, b.totals);
@@ -991,9 +1008,9 @@ inline int part_run(const uint32_t* d_scalars, const uint8_t* d_inf, const PartP
     nsegs = (uint64_t)p.bsets * p.b1;
   }
   if (p.fold)
-    hipLaunchKernelGGL((k_l1_scatter<FR, MONT, true>), dim3(l1_grid), dim3(PART_THREADS), 0, st, d_scalars, d_inf, p, b.matrix, b.entries[0]);
+    hipLaunchKernelGGL((k_l1_scatter<FR, MODE, true>), dim3(l1_grid), dim3(PART_THREADS), 0, st, d_scalars, d_inf, p, b.matrix, b.entries[0]);
   else
-    hipLaunchKernelGGL((k_l1_scatter<FR, MONT, false>), dim3(l1_grid), dim3(PART_THREADS), 0, st, d_scalars, d_inf, p, b.matrix, b.entries[0]);
+    hipLaunchKernelGGL((k_l1_scatter<FR, MODE, false>), dim3(l1_grid), dim3(PART_THREADS), 0, st, d_scalars, d_inf, p, b.matrix, b.entries[0]);
   PART_MARK("l1_scatter");
   PART_DBG_LEVEL(b.entries[0], b.segs[seg_cur], nsegs, p.lb);
   if (mid) (void)hipEventRecord(mid, st);
@@ -1039,9 +1056,9 @@ inline int part_run(const uint32_t* d_scalars, const uint8_t* d_inf, const PartP
     if (getenv("MI355_MSM_DEBUG_CORRUPT")) hipLaunchKernelGGL(k_dbg_corrupt, dim3(1), dim3(1), 0, st, b.entries[cur], b.totals);
     hipLaunchKernelGGL(k_dbg_check_sorted, dim3(2048), dim3(256), 0, st, b.entries[cur], b.totals, key_limit, p.idx0, idx_hi, dbg);
     if (p.fold)
-      hipLaunchKernelGGL((k_dbg_count_digits<FR, MONT, true>), dim3(part_ceil_div(p.n, 256)), dim3(256), 0, st, d_scalars, d_inf, p, dbg);
+      hipLaunchKernelGGL((k_dbg_count_digits<FR, MODE, true>), dim3(part_ceil_div(p.n, 256)), dim3(256), 0, st, d_scalars, d_inf, p, dbg);
     else
-      hipLaunchKernelGGL((k_dbg_count_digits<FR, MONT, false>), dim3(part_ceil_div(p.n, 256)), dim3(256), 0, st, d_scalars, d_inf, p, dbg);
+      hipLaunchKernelGGL((k_dbg_count_digits<FR, MODE, false>), dim3(part_ceil_div(p.n, 256)), dim3(256), 0, st, d_scalars, d_inf, p, dbg);
     hipLaunchKernelGGL(k_dbg_check_slots, dim3(1), dim3(256), 0, st, b.totals, 0u, 0u, dbg);
   }
 #endif

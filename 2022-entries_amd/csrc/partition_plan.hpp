@@ -9,6 +9,13 @@
 
 namespace msm {
 
+// What load_scalar does to a 256-bit input (context options "scalars_montgomery" / "scalars_to_montgomery")
+enum ScalarMode : int {
+  SCALARS_PLAIN = 0,      // the integer as it is
+  SCALARS_FROM_MONT = 1,  // fr_from_montgomery (digits.hpp)
+  SCALARS_TO_MONT = 2,    // fr_to_montgomery
+};
+
 constexpr int PART_TILE = 8192;        // scalars per level-1 tile (8 per thread of a 1024-thread block)
 constexpr int PART_THREADS = 1024;
 constexpr int PART_PER_THREAD = PART_TILE / PART_THREADS;

@@ -5,7 +5,11 @@
   ``scalars.bin`` (``Vec<Fr>``), ``arkworks_results.bin`` (``Vec<G1Affine>``).  A ``Vec`` is a little-endian u64 element
   count followed by the elements; an affine point is ``x | y`` as little-endian NORMAL-form integers with ``SWFlags`` in the
   top two bits of the last byte (bit 6 = infinity; P1B nickray driver/algebra/serialize/src/flags.rs:107-134); an ``Fr`` is
-  its 32-byte little-endian normal-form integer, which is exactly the ``BigInteger256`` image the MSM ABI takes.
+  its 32-byte little-endian NORMAL-form integer ``a`` (``into_repr``; P1B nickray driver/algebra/ff/src/fields/models/fp/mod.rs:583-608).
+  That is NOT the integer the harness's MSM runs on: it deserializes the file into ``Fr`` (whose limbs hold the Montgomery
+  image ``a * 2^256 mod r``) and hands those limbs over through ``transmute::<&[Fr], &[BigInteger256]>`` (util.rs:72-140,
+  tests/msm.rs:17-40), so ``arkworks_results.bin[b] = sum_i (a_i * 2^256 mod r) P_i``.  Run the file's integers with the
+  context option ``scalars_to_montgomery`` = 1 (``run_harness_dir``) to get those results.
 * whitespace-separated hex text (one big-endian hex number per token; points as x then y) as read by
   ``MSMReadHexPoints`` / ``MSMReadHexScalars`` (CMB MSM.cu:77-128) and ``parseHex`` (prize4 yrrid C/Reader.c:10-54).
 
@@ -16,7 +20,9 @@ from __future__ import annotations
 
 import ctypes
 import struct
-from typing import List, Tuple
+from typing import List, NamedTuple, Tuple
+
+import numpy as np
 
 from .msm import MultiScalarMultContext, _check, _curve_id, _COORD_BYTES, load_library, projective_bytes
 
@@ -30,7 +36,10 @@ def read_points_bin(path: str, curve="bls12_377_g1") -> Tuple[bytes, int]:
     """``points.bin`` -> (records without the length prefix, count)."""
     rb = record_bytes(curve)
     with open(path, "rb") as f:
-        (n,) = struct.unpack("<Q", f.read(8))
+        head = f.read(8)
+        if len(head) != 8:
+            raise ValueError(f"{path}: no element count")
+        (n,) = struct.unpack("<Q", head)
         data = f.read(n * rb)
     if len(data) != n * rb:
         raise ValueError(f"{path}: expected {n} records of {rb} bytes, file is short")
@@ -46,13 +55,42 @@ def write_points_bin(path: str, records: bytes, curve="bls12_377_g1") -> None:
         f.write(records)
 
 
-def read_scalars_bin(path: str) -> Tuple[bytes, int]:
-    """``scalars.bin`` (``Vec<Fr>``) -> (32-byte little-endian integers, count): already the MSM scalar ABI."""
+# the scalar field order r of each curve id (BLS12-377 Fr: ARKC bls12_377/src/fields/fr.rs:24; BLS12-381 Fr: bls12_381/src/fields/fr.rs:4)
+_FR_377 = 8444461749428370424248824938781546531375899335154063827935233455917409239041
+_FR_381 = 52435875175126190479447740508185965837690552500527637822603658699938581184513
+SCALAR_FIELD_ORDER = {0: _FR_377, 1: _FR_381, 2: _FR_377, 3: _FR_381}
+
+
+def _first_not_below(data: bytes, r: int) -> int:
+    """Index of the first 32-byte little-endian integer >= r, or -1."""
+    a = np.frombuffer(data, dtype="<u8").reshape(-1, 4)
+    lt = np.zeros(len(a), dtype=bool)
+    eq = np.ones(len(a), dtype=bool)
+    for i in (3, 2, 1, 0):
+        ri = np.uint64((r >> (64 * i)) & ((1 << 64) - 1))
+        lt |= eq & (a[:, i] < ri)
+        eq &= a[:, i] == ri
+    bad = np.flatnonzero(~lt)
+    return int(bad[0]) if bad.size else -1
+
+
+def read_scalars_bin(path: str, curve=None) -> Tuple[bytes, int]:
+    """``scalars.bin`` (``Vec<Fr>``) -> (the file's 32-byte little-endian normal-form integers, count).  A value >= r is rejected
+    with ValueError, as arkworks' ``from_repr`` rejects it: r of ``curve``'s scalar field, or -- no curve given, the file does not
+    say which field it holds -- the larger r of the two (BLS12-381's), which no scalar of either field reaches.  The harness runs
+    these integers as their Montgomery images (module docstring)."""
     with open(path, "rb") as f:
-        (n,) = struct.unpack("<Q", f.read(8))
+        head = f.read(8)
+        if len(head) != 8:
+            raise ValueError(f"{path}: no element count")
+        (n,) = struct.unpack("<Q", head)
         data = f.read(n * 32)
     if len(data) != n * 32:
         raise ValueError(f"{path}: expected {n} scalars, file is short")
+    r = max(SCALAR_FIELD_ORDER.values()) if curve is None else SCALAR_FIELD_ORDER[_curve_id(curve)]
+    bad = _first_not_below(data, r)
+    if bad >= 0:
+        raise ValueError(f"{path}: scalar {bad} is not below the scalar field order")
     return data, n
 
 
@@ -115,3 +153,37 @@ def point_to_serialized(projective: bytes, curve="bls12_377_g1") -> bytes:
 def write_results_bin(path: str, results: List[bytes], curve="bls12_377_g1") -> None:
     """``arkworks_results.bin``: the per-batch results as ``Vec<Affine>``."""
     write_points_bin(path, b"".join(point_to_serialized(r, curve) for r in results), curve)
+
+
+class HarnessData(NamedTuple):
+    """A ``TEST_LOAD_DATA_FROM`` directory: ``records`` (serialized points), ``scalars`` (the file's normal-form integers, batch after
+    batch), ``n`` points, ``batches``, ``expected`` (one serialized record per batch, from ``arkworks_results.bin``)."""
+    records: bytes
+    scalars: bytes
+    n: int
+    batches: int
+    expected: List[bytes]
+
+
+def load_harness_dir(path: str, curve="bls12_377_g1") -> HarnessData:
+    """Read ``points.bin``, ``scalars.bin`` and ``arkworks_results.bin`` of a harness data directory (P1B test_fpga_harness
+    src/util.rs:72-140: ``batches`` scalar vectors of ``n`` each, one result per batch)."""
+    import os
+
+    records, n = read_points_bin(os.path.join(path, "points.bin"), curve)
+    scalars, ns = read_scalars_bin(os.path.join(path, "scalars.bin"), curve)
+    res, nr = read_points_bin(os.path.join(path, "arkworks_results.bin"), curve)
+    if n == 0 or ns % n or ns // n != nr:
+        raise ValueError(f"{path}: {ns} scalars and {nr} results do not make whole batches of {n} points")
+    rb = record_bytes(curve)
+    return HarnessData(records, scalars, n, nr, [res[i * rb:(i + 1) * rb] for i in range(nr)])
+
+
+def run_harness_dir(ctx: MultiScalarMultContext, data: HarnessData, scalars=None, to_montgomery: bool = True) -> List[bool]:
+    """What the harness computes for a loaded data set: the file's integers run as their Montgomery images (context option
+    ``scalars_to_montgomery``, left set on ``ctx``), one MSM per batch.  ``scalars``: the same bytes elsewhere (e.g. a device
+    tensor) instead of ``data.scalars``.  Returns, per batch, whether the serialized result equals ``arkworks_results.bin``."""
+    ctx.set_option("scalars_to_montgomery", 1 if to_montgomery else 0)
+    set_bases_serialized(ctx, data.records)
+    got = ctx.run(data.scalars if scalars is None else scalars, data.n)
+    return [point_to_serialized(g, ctx.curve) == e for g, e in zip(got, data.expected)]

@@ -198,6 +198,11 @@ RustError mi355_msm_job_wait(mi355_msm_job* job);
  * "scalars_montgomery" = 1 makes every run treat the scalars as arkworks `Fr` values (Montgomery form, a*2^256 mod r)
  * and convert them on the device first -- VariableBaseMSM::msm(bases, &[Fr]) = into_bigint + msm_bigint
  * (ARK ec/src/msm/variable_base/mod.rs:48-53; sppark's `mont` flag SPK msm/pippenger.cuh:157-164).
+ * "scalars_to_montgomery" = 1 is the mirror image: every 256-bit scalar a (any value, not only a < r) runs as a*2^256 mod r, the
+ * Montgomery image of a.  That is what the ZPrize harness computes for a data set loaded from TEST_LOAD_DATA_FROM: scalars.bin
+ * holds normal-form integers (serialize_unchecked writes into_repr()), the harness deserializes them into `Fr` and hands the MSM
+ * the `Fr` limbs through transmute::<&[Fr], &[BigInteger256]> (P1B test_fpga_harness/src/util.rs:72-140, tests/msm.rs:17-40), so
+ * arkworks_results.bin[b] = sum (a_i*2^256 mod r) P_i.  Setting both options is an error (-1); 0 turns either off.
  * Mirrors Matter Labs' runtime msm_configuration (P1A matter-labs/.../bellman-cuda.h:49-71). */
 RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value);
 /* "twisted_edwards" (default 1; set BEFORE set_bases; BLS12-377 G1 only) lets the context keep, next to the bases, their image on
@@ -262,7 +267,7 @@ RustError mi355_msm_pool_stats(uint64_t* out, size_t count);
  * is left, writes the normalised Projective image and leaves the accumulator empty for reuse (arkworks' finalize consumes it).
  * Each flush is the stateless pipeline of mi355_msm() on `device` (< 0: the current device).  Options: "scalars_montgomery"
  * (the scalars are arkworks Fr images, converted on the device -- sums of Montgomery images are Montgomery images of sums),
- * "window_bits".  Queries: "buffered", "flushes", "merged" (pairs that landed on an existing hashmap entry), "buf_size". */
+ * "scalars_to_montgomery" (each scalar a runs as a*2^256 mod r, see mi355_msm_set_option), "window_bits".  Queries: "buffered", "flushes", "merged" (pairs that landed on an existing hashmap entry), "buf_size". */
 typedef struct mi355_msm_stream mi355_msm_stream;
 RustError mi355_msm_stream_create(mi355_msm_stream** out, int curve, int device, size_t max_msm_buffer, int hashmap);
 RustError mi355_msm_stream_set_option(mi355_msm_stream* s, const char* key, long value);

@@ -22,6 +22,12 @@ def test_field_ops_host(host_libs, cid):
     g.test_weak_reduce_and_bfi_step(host_libs, cid)
 
 
+@pytest.mark.parametrize("cid", [0, 1])
+def test_fr_montgomery_conversions_host(host_libs, cid):
+    """Both scalar conversions of csrc/digits.hpp against Python big integers on the representation edges (inputs >= r included)."""
+    g.check_fr_conversions(host_libs, cid, 1 << 12)
+
+
 @pytest.mark.parametrize("cid", [2, 3])
 def test_fp2_ops_host(host_libs, cid):
     g.test_fp2_products_in_every_operand_class(host_libs, cid)

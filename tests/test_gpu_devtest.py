@@ -29,7 +29,7 @@ LMASK = (1 << LB) - 1
 R392 = 1 << (NL * LB)
 OPS = dict(FE_MUL=0, FE_SQR=1, FE_MUL2=2, NOT_AND_LMASK=3, EL_MUL=4, EL_SQR=5, EL_MUL_C=6, EL_MUL_C_BIG=7, EL_SQR_C=8,
            EL_MUL_SUB_C=9, MADD_COMMON=10, MADD=11, ADD=12, DBL=13, TE_MADD=14, TE_MADD_SWAPPED=15, TE_ADD=16, TE_DBL=17,
-           ADD_QUAD=18, TE_ADD_QUAD=19, FE_WEAK_REDUCE=20)
+           ADD_QUAD=18, TE_ADD_QUAD=19, FE_WEAK_REDUCE=20, FR_FROM_MONT=21, FR_TO_MONT=22)
 DT_PAIR = 64
 CURVES = {0: m.BLS12_377_G1, 1: m.BLS12_381_G1, 2: m.BLS12_377_G2, 3: m.BLS12_381_G2}
 
@@ -192,6 +192,44 @@ def test_weak_reduce_and_bfi_step(libs, cid):
     words = [0, 1, LMASK, LMASK + 1, 0xFFFFFFFF, 0xF0000000, 0x0FFFFFFE] + [rng.randrange(1 << 32) for _ in range(4089)]
     out, _ = run_both(libs, cid, "NOT_AND_LMASK", arr([[w] for w in words]))
     assert [int(x) for x in out[:, 0]] == [(~w) & LMASK for w in words]
+
+
+# ---- scalar-field Montgomery conversions (digits.hpp: what load_scalar runs for "scalars_montgomery" / "scalars_to_montgomery") --
+def fr_edge_values(r, rng, n):
+    """n 256-bit integers: the representation edges of both directions first, then random ones below r and up to 2^256.  Inputs
+    >= r pin the "any 256-bit input" contract (the from-Montgomery reduction ends at <= r, i.e. its subtraction is exercised)."""
+    R = (1 << 256) % r
+    top = (1 << 256) - 1
+    v = [0, 1, 2, r - 1, r, r + 1, 2 * r - 1, 2 * r, 2 * r + 1, (1 << 253) - 1, 1 << 253, (1 << 255) - 1, 1 << 255, top, top - 1,
+         pow(R, -1, r), R, r - R, (r - 1) * pow(R, -1, r) % r, (r + 1) // 2 * pow(R, -1, r) % r, (r - 1) // 2, (r + 1) // 2,
+         (1 << 256) // r * r, (1 << 256) // r * r - 1, top - r, top - r + 1]
+    v += [k * r + d for k in range(1, (1 << 256) // r + 1) for d in (-1, 0, 1) if k * r + d <= top]
+    for j in range(8):
+        v += [1 << (32 * j), 0xFFFFFFFF << (32 * j), top ^ (0xFFFFFFFF << (32 * j)), (1 << (32 * j + 31))]   # single hot / cold limbs
+    v += [rng.randrange(1 << 256) & ~0xFFFFFFFF for _ in range(64)]                                        # zero low limb
+    v += [rng.randrange(r) & ~((1 << 64) - 1) for _ in range(64)]
+    v = [x for x in v if 0 <= x <= top]
+    while len(v) < n:
+        v.append(rng.randrange(r) if len(v) % 2 else rng.randrange(1 << 256))
+    return v[:n]
+
+
+def check_fr_conversions(libs, cid, n):
+    r = CURVES[cid].r
+    R = (1 << 256) % r
+    rinv = pow(R, -1, r)
+    vals = fr_edge_values(r, random.Random(0xF4 + cid), n)
+    recs = arr([[(x >> (32 * j)) & 0xFFFFFFFF for j in range(8)] for x in vals])
+    for op, f in (("FR_FROM_MONT", lambda x: x * rinv % r), ("FR_TO_MONT", lambda x: x * R % r)):
+        out, _ = run_both(libs, cid, op, recs)
+        got = [sum(int(w) << (32 * j) for j, w in enumerate(row)) for row in out.tolist()]
+        bad = [i for i, x in enumerate(vals) if got[i] != f(x)]
+        assert not bad, f"{op} curve {cid}: {len(bad)} of {n} wrong, first input {vals[bad[0]]:#x} -> {got[bad[0]]:#x}"
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_fr_montgomery_conversions(libs, cid):
+    check_fr_conversions(libs, cid, 1 << 16)
 
 
 # ---- Fp2 (G2) carried-operand forms ----------------------------------------------------------------------------------

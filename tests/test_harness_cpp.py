@@ -50,6 +50,18 @@ def test_msm_correctness_cpp(built, npow, batches, cv):
     assert f"curve={0 if cv == '377' else 1} " in r.stdout and ": ok" in r.stdout
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("cv,name", [("377", "377_g1_random"), ("377", "377_g1_trivial"), ("381", "381_g1_random")])
+def test_msm_correctness_cpp_load_data(built, cv, name):
+    """The harness's TEST_LOAD_DATA_FROM path in C++: the committed data sets (tests/golden/harness/) deserialized into Fr limbs on
+    the CPU, run through the unchanged C ABI, every batch equal to arkworks_results.bin byte for byte."""
+    _build()
+    r = subprocess.run([EXES[cv], "load", os.path.join(ROOT, "tests", "golden", "harness", name)], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "batches=4: ok" in r.stdout, r.stdout
+
+
 class _RustError(ctypes.Structure):
     _fields_ = [("code", ctypes.c_int), ("message", ctypes.c_void_p)]
 

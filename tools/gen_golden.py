@@ -14,6 +14,13 @@ asserted equal to the C oracle, whose Fp2 template instance is itself checked ag
 msm_vectors_large.json (sizes 2^10 and 2^12, SURVEY 8c "sizes 2^4 ... 2^12") keeps the FFI images compact: the `distinct` base
 records once (the test replicates them by doubling the vector, exactly what the reference generator does: P1A
 yrrid/src/util.rs:15-28) and every scalar explicitly.
+
+tests/golden/harness/<set>/{points,scalars,arkworks_results}.bin are data sets in the exact byte layout of the ZPrize FPGA harness's
+TEST_LOAD_DATA_FROM directories (P1B hardcaml/zprize/msm_pippenger/test_fpga_harness/src/util.rs:72-140, tests/msm.rs:17-40): a u64
+count, then the records (serialize_unchecked).  The harness restates each scalar as the NORMAL-form integer a in the file
+(into_repr) but runs the MSM on the Fr limbs, i.e. on the Montgomery image a * 2^256 mod r, so the expected result of batch b is
+sum_i (a_i * 2^256 mod r) P_i -- computed here with the images, and cross-checked with the reference's own code.
+    python tools/gen_golden.py            everything;   python tools/gen_golden.py harness   the harness sets only
 """
 import ctypes
 import json
@@ -28,6 +35,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import pymodel as m  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
+HARNESS_OUT = os.path.join(OUT, "harness")
 
 
 def ref377(curve, pts, sc):
@@ -97,7 +105,90 @@ def case(name, curve, pts, sc, note, zero_style="0.4", check_ref=True):
             "expected": exp.hex()}
 
 
+def _vec(records: bytes, count: int) -> bytes:
+    """arkworks Vec<T> serialization: u64 little-endian count, then the records."""
+    return count.to_bytes(8, "little") + records
+
+
+def _write_harness(name, curve, pts, file_scalars, batches, note):
+    """One TEST_LOAD_DATA_FROM directory.  Expected results: the MSM of the Montgomery IMAGES of the file's integers per batch."""
+    n = len(pts)
+    assert len(file_scalars) == n * batches and all(0 <= a < curve.r for a in file_scalars)
+    R = (1 << 256) % curve.r
+    images = [a * R % curve.r for a in file_scalars]
+    results, checked = [], ["pymodel.msm_pippenger", "oracle/msm_oracle.c"]
+    for b in range(batches):
+        sc = images[b * n:(b + 1) * n]
+        P = curve.msm_pippenger(pts, sc)
+        exp = curve.encode_projective_normalized(P)
+        assert oracle_c(curve, curve.encode_affine_array(pts), m.encode_scalars(sc), n) == exp, (name, b)
+        if curve.curve_id == 0:
+            assert ref377(curve, pts, sc) == exp, (name, b)
+        else:
+            keep = [i for i in range(n) if pts[i] is not None and sc[i]]
+            if keep and P is not None:
+                assert ref381(curve, [pts[i] for i in keep], [sc[i] for i in keep]) == exp, (name, b)
+        results.append(curve.encode_serialized(P))
+    checked.append("oracle/_ref/libref377.so (reference HostCurve, naive)" if curve.curve_id == 0 else "oracle/_ref/yrrid381_msm (reference C MSM)")
+    d = os.path.join(HARNESS_OUT, name)
+    os.makedirs(d, exist_ok=True)
+    files = {"points.bin": _vec(b"".join(curve.encode_serialized(P) for P in pts), n),
+             "scalars.bin": _vec(m.encode_scalars(file_scalars), len(file_scalars)),
+             "arkworks_results.bin": _vec(b"".join(results), batches)}
+    for fn, data in files.items():
+        assert len(data) < 256 * 1024, (name, fn)
+        with open(os.path.join(d, fn), "wb") as f:
+            f.write(data)
+    print("harness", name, curve.name, f"n={n} batches={batches}:", note, "| checked:", ", ".join(checked), flush=True)
+
+
+def harness_sets():
+    """tests/golden/harness/: TEST_LOAD_DATA_FROM data sets (module docstring), 4 batches each as in util.rs:77."""
+    batches = 4
+    for name, curve, npow in (("377_g1_random", m.BLS12_377_G1, 10), ("381_g1_random", m.BLS12_381_G1, 10)):
+        r, n = curve.r, 1 << npow
+        R = (1 << 256) % r
+        rinv = pow(R, -1, r)
+        rng = random.Random(0x4A5 + curve.curve_id)
+        distinct = 64
+        base = m.random_points(curve, distinct, rng, distinct)
+        base[3] = None                                   # util.rs:44 `points[3] = G::zero()` (commented out there), replicated
+        pts = list(base)
+        while len(pts) < n:                              # util.rs:45-47: the vector doubled up to len
+            pts.extend(pts[: n - len(pts)])
+        sc = m.random_scalars(curve, n * batches, rng)
+        # file scalars chosen for what their IMAGE (a * 2^256 mod r) becomes; planted in batch 0 and again in batch 3
+        planted = [0, 1, r - 1,
+                   rinv,                                 # image 1
+                   (r - 1) * rinv % r,                   # image r - 1
+                   (r + 1) // 2 * rinv % r,              # image (r + 1) / 2: just above r / 2, the subgroup-fold boundary
+                   (1 << 252) * rinv % r]                # image 2^252: the top window only
+        for b in (0, 3):
+            for j, a in enumerate(planted):
+                sc[b * n + 8 + j] = a
+            x = sc[b * n + 20]                           # positions 20 and 20 + distinct share a base: images x R, -x R cancel
+            sc[b * n + 20 + distinct] = (r - x) % r
+        _write_harness(name, curve, pts, sc, batches, "random bases (64 distinct, one infinity) and scalars, planted edges")
+    # TEST_TRIVIAL_INPUTS (util.rs:76-96) at 2^8: every base is the generator; the scalar at i % n == 0 is
+    # Fp256::new(BigInteger256::from(1)), every other one 0; the harness pushes the generator itself as each batch's result.
+    # In ark-ff 0.3 `Fp256::new` is the RAW constructor: the Fr's limbs ARE 1, so its value -- what serialize_unchecked writes, via
+    # into_repr -- is R^-1 mod r.  (The reference tree holds ark-ff 0.4 sources only, so this is not checked against source.)  The
+    # harness's own literal result settles it: the MSM runs on the limbs (1) and yields G, which is what it expects; under
+    # value semantics (limbs = R) the MSM would return (2^256 mod r) G instead.  _write_harness asserts the generator below.
+    c = m.BLS12_377_G1
+    n = 1 << 8
+    rinv = pow((1 << 256) % c.r, -1, c.r)
+    g = c.generator()
+    _write_harness("377_g1_trivial", c, [g] * n, [rinv if i % n == 0 else 0 for i in range(n * batches)], batches,
+                   "TEST_TRIVIAL_INPUTS")
+    res = open(os.path.join(HARNESS_OUT, "377_g1_trivial", "arkworks_results.bin"), "rb").read()
+    assert res == _vec(c.encode_serialized(g) * batches, batches)
+
+
 def main():
+    if sys.argv[1:] == ["harness"]:
+        harness_sets()
+        return
     os.makedirs(OUT, exist_ok=True)
     cases = []
     for curve in (m.BLS12_377_G1, m.BLS12_381_G1):
@@ -243,6 +334,8 @@ def main():
     with open(cpath, "w") as f:
         json.dump(consts, f, indent=1)
         f.write("\n")
+
+    harness_sets()
 
 
 if __name__ == "__main__":
