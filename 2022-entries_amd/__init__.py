@@ -5,7 +5,9 @@ The directory name (``2022-entries_amd``) is not a Python identifier; import it 
 """
 from .msm import (  # noqa: F401
     CURVE_IDS,
+    CheckResult,
     MsmError,
+    check_points,
     MultiScalarMultContext,
     VariableBaseMSM,
     affine_stride,

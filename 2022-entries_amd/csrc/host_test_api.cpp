@@ -583,3 +583,36 @@ extern "C" int ht_devop_shape(int curve, int op, int* in_words, int* out_words) 
   if (curve != 0 && ((op >= DT_TE_MADD && op <= DT_TE_DBL) || op == DT_TE_ADD_QUAD)) *in_words = *out_words = 0;
   return (*in_words) ? 0 : -1;
 }
+
+// ---- per-point classification (check_points.hpp) with the limb-bound checker armed ---------------------------------------------
+// `in`: n records, `stride` bytes apart (serialized != 0: uncompressed CanonicalSerialize records, stride = 2 coordinates);
+// method: 0 exact, 1 endomorphism.  One status byte per record.  The device twin is k_check_points (kernels_check.hip).
+#include "check_points.hpp"
+
+template <class C>
+static int t_check_points(int serialized, int method, const uint8_t* in, size_t stride, size_t n, uint8_t* status) {
+  using E = typename C::E;
+  typename E::Md md;
+  constexpr size_t CB = E::WORDS * 4;
+  if (stride < (serialized ? 2 * CB : 2 * CB + 1)) return -1;
+  for (size_t i = 0; i < n; i++) {
+    uint32_t w[2 * E::WORDS];
+    memcpy(w, in + i * stride, 2 * CB);
+    const uint8_t flag = serialized ? 0 : in[i * stride + 2 * CB];
+    if (serialized)
+      status[i] = method ? check_point<E, true, CHECK_ENDO>(w, flag, md) : check_point<E, true, CHECK_EXACT>(w, flag, md);
+    else
+      status[i] = method ? check_point<E, false, CHECK_ENDO>(w, flag, md) : check_point<E, false, CHECK_EXACT>(w, flag, md);
+  }
+  return 0;
+}
+
+extern "C" int ht_check_points(int curve, int serialized, int method, const uint8_t* in, size_t stride, size_t n, uint8_t* status) {
+  if (curve < 0 || curve > 3 || (n && (!in || !status)) || method < 0 || method > 1) return -1;
+  switch (curve) {
+    case 0: return t_check_points<Bls12_377_G1>(serialized, method, in, stride, n, status);
+    case 1: return t_check_points<Bls12_381_G1>(serialized, method, in, stride, n, status);
+    case 2: return t_check_points<Bls12_377_G2>(serialized, method, in, stride, n, status);
+    default: return t_check_points<Bls12_381_G2>(serialized, method, in, stride, n, status);
+  }
+}

@@ -38,6 +38,9 @@ struct Launch {
   // anchored window: one fragment per lane of the plain sum of bases [first, first + n) (k_sum_bases)
   static hipError_t sum_bases(const AffineDevT<El>* bases, const uint8_t* inf, uint32_t first, uint32_t n, uint32_t per_lane, SegOutT<El> out,
                               uint32_t nlanes, hipStream_t st);
+  // one status byte per record (check_points.hpp): 0 valid, 1 not canonical, 2 off the curve, 3 outside the order-r subgroup.
+  // Defined and instantiated in kernels_check.hip, not with the rest of the struct.
+  static hipError_t check_points(const uint8_t* in, size_t stride, uint32_t n, bool serialized, bool exact, uint8_t* status, hipStream_t st);
 };
 
 // The throughput kernels of a G2 curve with two lanes per point (SwPairLaw, laws.hpp); kernels_<curve>p.hip.  E = Fp2El<F, NB>.

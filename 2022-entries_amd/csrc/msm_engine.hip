@@ -374,6 +374,8 @@ struct mi355_msm_ctx {
   long opt_scalars_to_montgomery = 0;   // 1: every scalar a runs as a * 2^256 mod r (normal-form `scalars.bin` integers, digits.hpp)
   long opt_precompute = 0;
   long opt_table_levels = 0;      // with precompute: table levels k (0 = one per window); windows g, g + G, ... share bucket set g
+  long opt_validate_bases = 0;   // 1: set_bases* classify the new base set first (check_bases_impl) and refuse it, keeping the old one, if a point is invalid
+  bool bases_validated = false;   // the current base set passed that check
   long opt_assume_subgroup = 0;   // 1: every base is in the order-r subgroup (r P = O), so a scalar k in (r/2, r) may run as (r - k)(-P)
   long opt_anchor = 1;            // option "anchor_window": 1 = end the signed-digit carry chain at the last full window where that saves additions
   bool anchor_armed = false;      // ... for the run under way: the sum of its bases is at hand (run_device_t)
@@ -1753,6 +1755,108 @@ void run_host(mi355_msm_ctx* ctx, void* out, const void* scalars, size_t n, size
   }
 }
 
+// ---- on-curve and subgroup checks (check_points.hpp, kernels_check.hip) ---------------------------------------------------------
+// Classifies n records on the context's device and stream without touching the context's bases.  Host input is staged in pieces of
+// kCheckPiece records (never a second full copy on the device); the status bytes come back piece by piece and are counted here, in
+// index order, so the first invalid index is the smallest one.  The kernel marks flagged-infinity records with bit 7, which stays here.
+constexpr size_t kCheckPiece = (size_t)1 << 20;
+
+// `first_status` (may be null): the status of the first invalid point, 0 when there is none.
+void check_bases_impl(mi355_msm_ctx* ctx, const void* pts, size_t n, size_t stride, unsigned flags, uint8_t* status, uint64_t* out, bool on_device,
+                      uint8_t* first_status = nullptr) {
+  if (!ctx) bad_arg("null context");
+  if (!out) bad_arg("null result pointer");
+  if (!ctx->shards.empty()) bad_arg("check_bases is not available on a sharded context: check on a single-device context");
+  if (n && !pts) bad_arg("null points pointer");
+  if (flags & ~3u) bad_arg("unknown check_bases flags 0x%x", flags);
+  const bool serialized = (flags & 1) != 0, exact = (flags & 2) != 0;
+  const size_t cb2 = 2 * coord_bytes(ctx->curve);
+  if (serialized) {
+    stride = cb2;
+  } else if (stride < cb2 + 1 || (stride & 3)) {
+    bad_arg("affine stride %zu is not a 4-byte multiple >= %zu", stride, cb2 + 1);
+  }
+  if (n >= (1ull << 31)) bad_arg("npoints %zu exceeds 2^31-1", n);
+  uint64_t cnt[4] = {0, 0, 0, 0}, flagged = 0, first = n;
+  uint8_t first_st = 0;
+  float ms = 0;
+  if (n) {
+    ensure_device(ctx);
+    hipStream_t st = ctx->own_stream;
+    const size_t piece = n < kCheckPiece ? n : kCheckPiece;
+    DevBuf raw, dstat;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::vector<uint8_t> hstat(piece);
+    try {
+      dstat.reserve(piece);
+      if (!on_device) raw.reserve(piece * stride);
+      HIP_OK(hipEventCreate(&ev0));
+      HIP_OK(hipEventCreate(&ev1));
+      for (size_t at = 0; at < n; at += piece) {
+        const size_t m = n - at < piece ? n - at : piece;
+        const uint8_t* src = (const uint8_t*)pts + at * stride;
+        if (!on_device) {
+          // (the last record of a strided image may end before at * stride + m * stride: copy up to the end of its coordinates and flag)
+          const size_t bytes = (m - 1) * stride + (serialized ? cb2 : cb2 + 1);
+          HIP_OK(hipMemcpyAsync(raw.p, src, bytes, hipMemcpyHostToDevice, st));
+          src = (const uint8_t*)raw.p;
+        }
+        HIP_OK(hipEventRecord(ev0, st));   // device microseconds = the kernels alone, for host and device input alike: the staging copy is not in it
+        with_curve(ctx->curve, [&]<class C>() { HIP_OK(Launch<typename C::E>::check_points(src, stride, (uint32_t)m, serialized, exact, dstat.as<uint8_t>(), st)); });
+        HIP_OK(hipEventRecord(ev1, st));
+        HIP_OK(hipMemcpyAsync(hstat.data(), dstat.p, m, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        float t = 0;
+        HIP_OK(hipEventElapsedTime(&t, ev0, ev1));
+        ms += t;
+        for (size_t i = 0; i < m; i++) {
+          const uint8_t s = hstat[i] & 3;
+          cnt[s]++;
+          if (hstat[i] & 0x80) flagged++;
+          if (s && first == n) {
+            first = at + i;
+            first_st = s;
+          }
+          if (status) status[at + i] = s;
+        }
+      }
+    } catch (...) {
+      (void)hipStreamSynchronize(st);
+      if (ev0) (void)hipEventDestroy(ev0);
+      if (ev1) (void)hipEventDestroy(ev1);
+      raw.release();
+      dstat.release();
+      throw;
+    }
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+    raw.release();
+    dstat.release();
+  }
+  out[0] = cnt[0];
+  out[1] = flagged;
+  out[2] = cnt[1];
+  out[3] = cnt[2];
+  out[4] = cnt[3];
+  out[5] = first;
+  out[6] = exact ? 0 : 1;
+  out[7] = (uint64_t)(ms * 1000.0f);
+  if (first_status) *first_status = first_st;
+}
+
+// option "validate_bases": called by the set_bases entry points BEFORE anything of the previous base set is released
+void validate_new_bases(mi355_msm_ctx* ctx, const void* pts, size_t n, size_t stride, bool serialized, bool on_device) {
+  if (!ctx->opt_validate_bases) return;
+  uint64_t o[8];
+  uint8_t st1 = 0;
+  check_bases_impl(ctx, pts, n, stride, serialized ? 1u : 0u, nullptr, o, on_device, &st1);
+  if (o[5] != n) {
+    static const char* const kWhy[4] = {"valid", "a coordinate is not below p", "not on the curve", "outside the order-r subgroup"};
+    bad_arg("validate_bases: point %llu is invalid (status %u: %s); %llu of %zu points are invalid; the previous bases are kept",
+            (unsigned long long)o[5], (unsigned)st1, kWhy[st1 & 3], (unsigned long long)(o[2] + o[3] + o[4]), n);
+  }
+}
+
 }  // namespace
 
 #include "msm_sharded.hpp"
@@ -2013,6 +2117,9 @@ RustError mi355_msm_create_env(mi355_msm_ctx** out, int curve) {
   // MI355_MSM_ASSUME_SUBGROUP = 0 | 1: the harness's bases are (are not) all in the order-r subgroup -- option "assume_subgroup"
   const char* sub = getenv("MI355_MSM_ASSUME_SUBGROUP");
   if (sub && *sub) e = mi355_msm_set_option(*out, "assume_subgroup", atol(sub) != 0);
+  // MI355_MSM_VALIDATE_BASES = 0 | 1: option "validate_bases" -- what a harness that promises subgroup points can turn on to have it checked
+  const char* val = getenv("MI355_MSM_VALIDATE_BASES");
+  if (!e.code && val && *val) e = mi355_msm_set_option(*out, "validate_bases", atol(val) != 0);
   // MI355_MSM_PRECOMPUTE = auto | 0 | 1 (+ MI355_MSM_TABLE_LEVELS = k): the harness's init is untimed (CMB MSM.cu:380-383 builds its
   // tables there), so a harness that owns the GPU may let the context spend free HBM on tables -- options "precompute" / "table_levels"
   const char* pre = getenv("MI355_MSM_PRECOMPUTE");
@@ -2039,7 +2146,10 @@ RustError mi355_msm_set_bases(mi355_msm_ctx* ctx, const void* affine, size_t npo
     if (!ctx) bad_arg("null context");
     if (npoints && !affine) bad_arg("null bases pointer");
     if (!ctx->shards.empty()) return sharded_set_bases(ctx, affine, npoints, stride, false, false);
+    validate_new_bases(ctx, affine, npoints, stride, false, false);
+    ctx->bases_validated = false;   // (the verdict of the set that is about to go: an upload that throws leaves no base set to vouch for)
     set_bases_host(ctx, affine, npoints, stride, false);
+    ctx->bases_validated = ctx->opt_validate_bases != 0;
   });
 }
 
@@ -2049,7 +2159,10 @@ RustError mi355_msm_set_bases_serialized(mi355_msm_ctx* ctx, const void* records
     if (npoints && !records) bad_arg("null records pointer");
     const size_t stride = 2 * coord_bytes(ctx->curve);
     if (!ctx->shards.empty()) return sharded_set_bases(ctx, records, npoints, stride, true, false);
+    validate_new_bases(ctx, records, npoints, stride, true, false);
+    ctx->bases_validated = false;
     set_bases_host(ctx, records, npoints, stride, true);
+    ctx->bases_validated = ctx->opt_validate_bases != 0;
   });
 }
 
@@ -2095,7 +2208,25 @@ RustError mi355_msm_set_bases_device(mi355_msm_ctx* ctx, const void* d_affine, s
     // the producer (e.g. torch) may have written the buffer on another stream: make it visible first
     ensure_device(ctx);
     HIP_OK(hipDeviceSynchronize());
+    validate_new_bases(ctx, d_affine, npoints, stride, false, true);
+    ctx->bases_validated = false;
     set_bases_device(ctx, d_affine, npoints, stride);
+    ctx->bases_validated = ctx->opt_validate_bases != 0;
+  });
+}
+
+RustError mi355_msm_check_bases(mi355_msm_ctx* ctx, const void* affine, size_t npoints, size_t stride, unsigned flags, uint8_t* status, uint64_t* out) {
+  return guarded_dev([&] { check_bases_impl(ctx, affine, npoints, stride, flags, status, out, false); });
+}
+
+RustError mi355_msm_check_bases_device(mi355_msm_ctx* ctx, const void* d_affine, size_t npoints, size_t stride, unsigned flags, uint8_t* status,
+                                       uint64_t* out) {
+  return guarded_dev([&] {
+    if (ctx && ctx->shards.empty() && npoints) {
+      ensure_device(ctx);
+      HIP_OK(hipDeviceSynchronize());   // the producer may have written the buffer on another stream
+    }
+    check_bases_impl(ctx, d_affine, npoints, stride, flags, status, out, true);
   });
 }
 
@@ -2126,6 +2257,10 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value) 
       ctx->opt_force_peer_staging = value != 0;
       return;
     }
+    if (!ctx->shards.empty() && k == "validate_bases" && value != 0)
+      // a shard that refused its slice after another had replaced its own would leave the context between two base sets
+      bad_arg("validate_bases is not available on a sharded context (MI355_MSM_VALIDATE_BASES with several MI355_MSM_DEVICES): check the bases "
+              "on a single-device context with mi355_msm_check_bases");
     if (!ctx->shards.empty() && k != "combine") {
       for (mi355_msm_ctx* sh : ctx->shards) {
         RustError e = mi355_msm_set_option(sh, key, value);
@@ -2195,6 +2330,8 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value) 
     } else if (k == "scalars_to_montgomery") {
       if (value != 0 && ctx->opt_scalars_montgomery) bad_arg("scalars_to_montgomery and scalars_montgomery exclude each other");
       ctx->opt_scalars_to_montgomery = value != 0;
+    } else if (k == "validate_bases") {
+      ctx->opt_validate_bases = value != 0;
     } else if (k == "assume_subgroup") {
       ctx->opt_assume_subgroup = value != 0;
     } else if (k == "carry") {
@@ -2337,6 +2474,10 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
       *value = ctx->te_demotions;
     else if (k == "assume_subgroup")
       *value = ctx->opt_assume_subgroup ? 1 : 0;
+    else if (k == "validate_bases")
+      *value = ctx->opt_validate_bases ? 1 : 0;
+    else if (k == "bases_validated")
+      *value = ctx->bases_validated ? 1 : 0;
     else if (k == "carry")
       *value = ctx->opt_carry ? 1 : 0;
     else if (k == "anchor")

@@ -32,8 +32,10 @@ def record_bytes(curve) -> int:
     return 2 * _COORD_BYTES[_curve_id(curve)]
 
 
-def read_points_bin(path: str, curve="bls12_377_g1") -> Tuple[bytes, int]:
-    """``points.bin`` -> (records without the length prefix, count)."""
+def read_points_bin(path: str, curve="bls12_377_g1", validate: bool = False) -> Tuple[bytes, int]:
+    """``points.bin`` -> (records without the length prefix, count).  ``validate=True`` is arkworks' ``deserialize_uncompressed``
+    beside the default ``deserialize_unchecked``: the records go through the GPU check (msm.check_points) and a ValueError names the
+    first record that has a non-canonical coordinate, is off the curve or lies outside the order-r subgroup."""
     rb = record_bytes(curve)
     with open(path, "rb") as f:
         head = f.read(8)
@@ -43,6 +45,14 @@ def read_points_bin(path: str, curve="bls12_377_g1") -> Tuple[bytes, int]:
         data = f.read(n * rb)
     if len(data) != n * rb:
         raise ValueError(f"{path}: expected {n} records of {rb} bytes, file is short")
+    if validate:
+        from .msm import CHECK_STATUS_TEXT, check_points
+
+        res = check_points(data, curve=curve, serialized=True)
+        if not res.ok:
+            i = res.first_invalid
+            raise ValueError(f"{path}: record {i} is not a valid point (status {int(res.status[i])}: {CHECK_STATUS_TEXT[int(res.status[i])]}); "
+                             f"{n - res.counts['valid']} of {n} records are invalid")
     return data, n
 
 
@@ -165,12 +175,12 @@ class HarnessData(NamedTuple):
     expected: List[bytes]
 
 
-def load_harness_dir(path: str, curve="bls12_377_g1") -> HarnessData:
+def load_harness_dir(path: str, curve="bls12_377_g1", validate: bool = False) -> HarnessData:
     """Read ``points.bin``, ``scalars.bin`` and ``arkworks_results.bin`` of a harness data directory (P1B test_fpga_harness
     src/util.rs:72-140: ``batches`` scalar vectors of ``n`` each, one result per batch)."""
     import os
 
-    records, n = read_points_bin(os.path.join(path, "points.bin"), curve)
+    records, n = read_points_bin(os.path.join(path, "points.bin"), curve, validate=validate)   # (validate: the bases, not the results)
     scalars, ns = read_scalars_bin(os.path.join(path, "scalars.bin"), curve)
     res, nr = read_points_bin(os.path.join(path, "arkworks_results.bin"), curve)
     if n == 0 or ns % n or ns // n != nr:

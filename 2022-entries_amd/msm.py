@@ -90,6 +90,8 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_destroy": [vp],
         "mi355_msm_set_bases": [vp, vp, sz, sz],
         "mi355_msm_set_bases_device": [vp, vp, sz, sz],
+        "mi355_msm_check_bases": [vp, vp, sz, sz, ctypes.c_uint, vp, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_check_bases_device": [vp, vp, sz, sz, ctypes.c_uint, vp, ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_run": [vp, vp, vp, sz, sz],
         "mi355_msm_run_device": [vp, vp, vp, sz, sz, vp],
         "mi355_msm_run_async": [vp, vp, vp, sz, sz, vp, vp, vp, ctypes.POINTER(vp)],
@@ -195,6 +197,20 @@ def _flat_bytes(obj):
     return memoryview(obj if isinstance(obj, (bytes, bytearray)) else bytes(obj))
 
 
+CHECK_STATUS_TEXT = ("valid", "a coordinate is not below p", "not on the curve", "outside the order-r subgroup")
+
+
+class CheckResult:
+    """What MultiScalarMultContext.check_bases found: `status` holds one byte per point (0 valid, 1 not canonical, 2 off the curve,
+    3 outside the order-r subgroup)."""
+
+    def __init__(self, ok, counts, first_invalid, status, method, device_us):
+        self.ok, self.counts, self.first_invalid, self.status, self.method, self.device_us = ok, counts, first_invalid, status, method, device_us
+
+    def __repr__(self):
+        return f"CheckResult(ok={self.ok}, counts={self.counts}, first_invalid={self.first_invalid}, method={self.method!r}, device_us={self.device_us})"
+
+
 class MultiScalarMultContext:
     """``#[repr(C)] struct MultiScalarMultContext { context: *mut c_void }`` (P1A 6block/src/lib.rs:18-21)."""
 
@@ -244,6 +260,29 @@ class MultiScalarMultContext:
         fn = self._lib.mi355_msm_set_bases_device if b.is_device else self._lib.mi355_msm_set_bases
         _check(fn(self.context, b.ptr, n, stride))
         self.npoints = n
+
+    def check_bases(self, points, stride: Optional[int] = None, serialized: bool = False, exact: bool = False) -> "CheckResult":
+        """On-curve and subgroup check of `points` on the context's device (mi355_msm_check_bases): bytes, numpy or torch CPU / GPU
+        tensors like set_bases.  `serialized`: uncompressed CanonicalSerialize records instead of in-memory Affine images.  `exact`:
+        decide the subgroup by [r]P == O instead of the endomorphism test (same verdicts).  The context's bases are not touched."""
+        import numpy as np
+
+        rec = 2 * (projective_bytes(self.curve) // 3) if serialized else (affine_stride(self.curve) if stride is None else stride)
+        b = _Buf(points)
+        if b.nbytes % rec:
+            raise ValueError(f"points image of {b.nbytes} bytes is not a multiple of the {rec}-byte record")
+        n = b.nbytes // rec
+        self._check_device(b, "points")
+        status = np.zeros(n, dtype=np.uint8)
+        out = (ctypes.c_uint64 * 8)()
+        fn = self._lib.mi355_msm_check_bases_device if b.is_device else self._lib.mi355_msm_check_bases
+        flags = (1 if serialized else 0) | (2 if exact else 0)
+        _check(fn(self.context, b.ptr, n, rec, flags, status.ctypes.data_as(ctypes.c_void_p) if n else None, out))
+        counts = {"valid": int(out[0]), "flagged_infinity": int(out[1]), "not_canonical": int(out[2]), "off_curve": int(out[3]),
+                  "off_subgroup": int(out[4])}
+        first = int(out[5])
+        return CheckResult(ok=first == n, counts=counts, first_invalid=None if first == n else first, status=status,
+                           method="endomorphism" if out[6] else "exact", device_us=int(out[7]))
 
     def run(self, scalars, npoints: Optional[int] = None) -> List[bytes]:
         b = _Buf(scalars)
@@ -343,6 +382,16 @@ def multi_scalar_mult_init(points, curve="bls12_377_g1", device: Optional[int] =
     ctx = MultiScalarMultContext(curve, device, devices)
     ctx.set_bases(points)
     return ctx
+
+
+def check_points(points, curve="bls12_377_g1", stride: Optional[int] = None, serialized: bool = False, exact: bool = False,
+                 device: Optional[int] = None) -> CheckResult:
+    """MultiScalarMultContext.check_bases on a throwaway context."""
+    ctx = MultiScalarMultContext(curve, device)
+    try:
+        return ctx.check_bases(points, stride=stride, serialized=serialized, exact=exact)
+    finally:
+        ctx.close()
 
 
 def multi_scalar_mult(ctx: MultiScalarMultContext, points, scalars) -> List[bytes]:

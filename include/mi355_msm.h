@@ -98,6 +98,34 @@ RustError mi355_msm_set_bases(mi355_msm_ctx* ctx, const void* affine, size_t npo
 /* Same, bases already resident in DEVICE memory (e.g. a torch uint8 tensor's data_ptr). */
 RustError mi355_msm_set_bases_device(mi355_msm_ctx* ctx, const void* d_affine, size_t npoints, size_t stride);
 
+/* Are these points legal bases?  One status byte per point, decided on the context's device and stream; the context's own bases are
+ * neither read nor changed.
+ *   0  valid: flagged infinity, or on the curve and in the order-r subgroup
+ *   1  a coordinate is not below p (in-memory image: the Montgomery limbs; serialized record: the integer after the two flag bits
+ *      are masked)
+ *   2  canonical, but y^2 != x^3 + b
+ *   3  on the curve, outside the order-r subgroup
+ * The infinity flag is authoritative (of a serialized record's flag bits only bit 6 is read: a record with both bits set, which arkworks
+ * refuses, counts as infinity); the lowest applicable status wins.  This is what arkworks' checked reader does and
+ * `deserialize_unchecked` skips (ARK ec/src/models/short_weierstrass.rs:67-77, 1204-1224); status 3 is decided by the endomorphism
+ * tests of eprint 2021/1130 (ARKC bls12_381/src/curves/g1.rs:47-85, g2.rs:58-71) or, with flag bit 1, by [r]P == O itself --
+ * identical verdicts (csrc/check_points.hpp argues why, for BLS12-377 as well).
+ * flags: bit 0 = records are uncompressed CanonicalSerialize records (stride ignored), bit 1 = exact method.
+ * status: HOST memory, npoints bytes, may be NULL.
+ * out[8]: valid, of those flagged infinity, status 1, status 2, status 3, index of the first invalid point (npoints if none),
+ *         method used (0 exact, 1 endomorphism), device microseconds (the check kernels alone, between events on the context's stream:
+ *         neither the staging copies of host input nor the status copies back, so less than what the caller waits for).
+ * Returns 0 when the check RAN, whatever it found; -1 for a sharded context, a stride too small or not a multiple of 4.
+ * Option "validate_bases" = 1 (default 0; MI355_MSM_VALIDATE_BASES for mi355_msm_create_env) makes the three set_bases calls run
+ * this check first: an invalid point fails the call with -1 and a message naming the first bad index and its status, and the
+ * context keeps its previous bases.  Query "bases_validated": 1 when the current base set passed the check.
+ * A sharded context refuses "validate_bases" = 1 (-1, from mi355_msm_set_option and so from mi355_msm_create_env when
+ * MI355_MSM_VALIDATE_BASES=1 meets a list of several MI355_MSM_DEVICES): check on a single-device context first. */
+RustError mi355_msm_check_bases(mi355_msm_ctx* ctx, const void* affine, size_t npoints, size_t stride, unsigned flags, uint8_t* status,
+                                uint64_t* out);
+RustError mi355_msm_check_bases_device(mi355_msm_ctx* ctx, const void* d_affine, size_t npoints, size_t stride, unsigned flags,
+                                       uint8_t* status, uint64_t* out);
+
 /* Bases as arkworks CanonicalSerialize UNCOMPRESSED records in host memory (row f2: what the harness persists with
  * `points.serialize_unchecked(File::create("points.bin"))`, P1B hardcaml/.../test_fpga_harness/src/util.rs:126-140): per point
  * x | y as little-endian normal-form integers (2 x 48 B for G1, 2 x 96 B for G2), SWFlags in the top two bits of the last

@@ -57,6 +57,33 @@ struct MultiScalarMultContext {   // #[repr(C)] struct { context: *mut c_void }
   }
 };
 
+// On-curve and subgroup check of host-resident points (mi355_msm_check_bases): status[i] in 0..3, true when every point is valid.
+struct CheckResult {
+  bool ok = true;
+  uint64_t valid = 0, flagged_infinity = 0, not_canonical = 0, off_curve = 0, off_subgroup = 0, first_invalid = 0, method = 0, device_us = 0;
+  std::vector<uint8_t> status;
+};
+inline CheckResult check_bases(MultiScalarMultContext& ctx, const std::vector<G1Affine>& points, bool exact = false) {
+  CheckResult r;
+  uint64_t out[8] = {0};
+  r.status.resize(points.size());
+  check(mi355_msm_check_bases(ctx.context, points.data(), points.size(), sizeof(G1Affine), exact ? 2u : 0u, r.status.data(), out));
+  r.valid = out[0]; r.flagged_infinity = out[1]; r.not_canonical = out[2]; r.off_curve = out[3]; r.off_subgroup = out[4];
+  r.first_invalid = out[5]; r.method = out[6]; r.device_us = out[7];
+  r.ok = out[5] == points.size();
+  return r;
+}
+inline CheckResult check_bases_device(MultiScalarMultContext& ctx, const void* d_points, size_t npoints, size_t stride, bool exact = false) {
+  CheckResult r;
+  uint64_t out[8] = {0};
+  r.status.resize(npoints);
+  check(mi355_msm_check_bases_device(ctx.context, d_points, npoints, stride, exact ? 2u : 0u, r.status.data(), out));
+  r.valid = out[0]; r.flagged_infinity = out[1]; r.not_canonical = out[2]; r.off_curve = out[3]; r.off_subgroup = out[4];
+  r.first_invalid = out[5]; r.method = out[6]; r.device_us = out[7];
+  r.ok = out[5] == npoints;
+  return r;
+}
+
 inline MultiScalarMultContext multi_scalar_mult_init(const std::vector<G1Affine>& points, int curve = MI355_BLS12_377_G1) {
   MultiScalarMultContext ctx;
   check(mi355_msm_create(&ctx.context, curve, -1));

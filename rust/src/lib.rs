@@ -15,7 +15,7 @@
 //! the bases and every scalar batch are split into contiguous slices, one per MI355X, and the partial points are
 //! all-gathered over RCCL/xGMI and folded -- no change on the Rust side.
 
-use std::os::raw::{c_char, c_int, c_long, c_void};
+use std::os::raw::{c_char, c_int, c_long, c_uint, c_void};
 
 use ark_ec::AffineCurve;
 use ark_ff::PrimeField;
@@ -94,7 +94,7 @@ extern "C" {
 
 /// The engine's canonical C ABI (include/mi355_msm.h), for callers that want more than the harness API.
 pub mod sys {
-    use super::{c_char, c_int, c_long, c_void, Error};
+    use super::{c_char, c_int, c_long, c_uint, c_void, Error};
 
     /// completion callback of `mi355_msm_run_async` (include/mi355_msm.h `mi355_msm_done_fn`)
     pub type DoneFn = extern "C" fn(user: *mut c_void, status: Error);
@@ -110,6 +110,12 @@ pub mod sys {
         pub fn mi355_msm_destroy(ctx: *mut c_void) -> Error;
         pub fn mi355_msm_set_bases(ctx: *mut c_void, affine: *const c_void, npoints: usize, stride: usize) -> Error;
         pub fn mi355_msm_set_bases_serialized(ctx: *mut c_void, records: *const c_void, npoints: usize) -> Error;
+        /// On-curve and subgroup check of `npoints` records (flags: bit 0 serialized records, bit 1 exact method); one status byte per
+        /// point into `status` (may be null), counts / first invalid index / method / device microseconds into `out[8]`.
+        pub fn mi355_msm_check_bases(ctx: *mut c_void, affine: *const c_void, npoints: usize, stride: usize, flags: c_uint, status: *mut u8,
+                                     out: *mut u64) -> Error;
+        pub fn mi355_msm_check_bases_device(ctx: *mut c_void, d_affine: *const c_void, npoints: usize, stride: usize, flags: c_uint,
+                                            status: *mut u8, out: *mut u64) -> Error;
         pub fn mi355_msm_run(ctx: *mut c_void, out_projective: *mut c_void, scalars: *const c_void, npoints: usize, batches: usize) -> Error;
         pub fn mi355_msm_run_device(ctx: *mut c_void, out_projective: *mut c_void, d_scalars: *const c_void, npoints: usize, batches: usize,
                                     stream: *mut c_void) -> Error;
