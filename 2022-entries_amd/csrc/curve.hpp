@@ -8,8 +8,10 @@
 //
 // Stored-point invariants (what every function below both requires and re-establishes):
 //   Xyzz.x, Xyzz.y : limbs < 2^28 + 16, value < 16p
-//   Xyzz.zz, .zzz  : class M (normalized limbs, value < 2p);  infinity  <=>  zz == 0 (mod p)
+//   Xyzz.zz, .zzz  : class M as fp28.hpp defines it (normalized limbs, value < 1.5p);  infinity  <=>  zz == 0 (mod p)
 //   Affine.x, .y   : class M (canonical < p when produced by the base-conversion kernel)
+// (1.5p, not 2p: the BIAS2_28 negations of a class-M operand rely on the top limb that bound implies.  tests/test_gpu_xyzz_edges.py
+// runs every law below at the corners of these bounds.)
 #pragma once
 #include "fp28.hpp"
 
@@ -133,7 +135,7 @@ struct Fp2El {
   }
   // The same product for operands that are already CARRIED (limbs < 2^28 + 16), which is what the group law's hot path
   // holds anyway: no carries, no weak reduction.  The BETA factor moves to the a side, the sign to the b side:
-  //   c0 = a0 b0 + (5 a1)(K p - b1),   K p = BIAS2_28 for a class-M b (strictly normalized, < 2p), BIAS32_29 (B_BIG) for a
+  //   c0 = a0 b0 + (5 a1)(K p - b1),   K p = BIAS2_28 for a class-M b (strictly normalized, < 1.5p), BIAS32_29 (B_BIG) for a
   //   carried b of value <= 18p.  Column bound of the fused product: 14 (2^56 + 1.25 * 2^30 * 1.5 * 2^29 + 2^56) < 0.93 * 2^64;
   //   value: (18p 18p + 90p 32p) / 2^15 p + p < 2p -- class M as ever.
   template <bool B_BIG>

@@ -574,7 +574,7 @@ MSM_HD void fe_reduce(Fe& r) {
   }
 }
 
-// value == 0 (mod p) for a class-M element (normalized, < 2p): it is 0 or p.  The first-limb test
+// value == 0 (mod p) for a class-M element (normalized, < 1.5p): it is 0 or p.  The first-limb test
 // rejects all but ~2^-27 of the non-zero values, so the full compare is off the hot path.
 template <class F>
 MSM_HD bool fe_is_zero_M(const Fe& a) {
