@@ -25,6 +25,9 @@ from .msm import (  # noqa: F401
     pool_stats,
     ChunkedPippenger,
     HashMapPippenger,
+    FixedBase,
+    WindowTable,
+    fixed_base_msm,
 )
 from .dist import all_gather_partials, shard_bounds, sharded_msm  # noqa: F401,E402
 from . import formats  # noqa: F401,E402

@@ -616,3 +616,126 @@ extern "C" int ht_check_points(int curve, int serialized, int method, const uint
     default: return t_check_points<Bls12_381_G2>(serialized, method, in, stride, n, status);
   }
 }
+
+// ---- batch fixed-base multiplication (fixed_base.hpp) with the limb-bound checker armed ----------------------------------------
+// The SAME MSM_HD functions the kernels of kernels_fixed.hip wrap: level bases, table runs, windowed_mul, output normalisation.
+// The device twin of fb_host_table's normalisation step is k_pre_normalize (msm_kernels.hpp), whose record contract it restates:
+// canonical coordinates, all-zero for the point at infinity.
+#include <vector>
+
+#include "fixed_base.hpp"
+
+template <class E>
+static void fb_host_records(AffineDevT<typename E::T>* out, const XyzzT<typename E::T>* in, size_t n, const typename E::Md& md) {
+  using El = typename E::T;
+  std::vector<El> prefix(n);
+  El run, inv;
+  E::set_one(run);
+  for (size_t j = 0; j < n; j++) {
+    prefix[j] = run;
+    if (!xyzz_is_inf<E>(in[j])) {
+      El z;
+      E::mul(z, in[j].zz, in[j].zzz, md);
+      E::mul(run, run, z, md);
+    }
+  }
+  el_inv(inv, run, md, (E*)nullptr);
+  for (size_t j = n; j-- > 0;) {
+    if (xyzz_is_inf<E>(in[j])) {
+      E::zero(out[j].p.x);
+      E::zero(out[j].p.y);
+      continue;
+    }
+    El z, ti, zzi, zzzi;
+    E::mul(ti, inv, prefix[j], md);
+    E::mul(z, in[j].zz, in[j].zzz, md);
+    E::mul(inv, inv, z, md);
+    E::mul(zzi, ti, in[j].zzz, md);
+    E::mul(zzzi, ti, in[j].zz, md);
+    E::mul(out[j].p.x, in[j].x, zzi, md);
+    E::mul(out[j].p.y, in[j].y, zzzi, md);
+    E::reduce(out[j].p.x);
+    E::reduce(out[j].p.y);
+  }
+}
+
+// levels [j0, j1) of the table of g for window size w, as XYZZ (2^w entries per level), built the way the device builds them
+template <class E>
+static void fb_host_levels(std::vector<XyzzT<typename E::T>>& xyzz, const uint8_t* g_img, uint32_t w, uint32_t j0, uint32_t j1, const typename E::Md& md) {
+  using El = typename E::T;
+  const uint32_t levels = fb_levels(w), per = 1u << w;
+  uint32_t rec[2 * E::WORDS];
+  memcpy(rec, g_img, 8 * E::WORDS);
+  std::vector<XyzzT<El>> lb(levels);
+  fb_level_bases<E>(lb.data(), rec, g_img[8 * E::WORDS], w, levels, md);
+  std::vector<AffineDevT<El>> lba(levels);
+  fb_host_records<E>(lba.data(), lb.data(), levels, md);
+  xyzz.resize((size_t)(j1 - j0) * per);
+  for (uint32_t j = j0; j < j1; j++)
+    for (uint32_t d0 = 0; d0 < per; d0 += FB_TABLE_RUN)
+      fb_table_run<E>(xyzz.data() + (size_t)(j - j0) * per + d0, lba[j].p, xyzz_is_inf<E>(lb[j]), d0, d0 + FB_TABLE_RUN <= per ? FB_TABLE_RUN : per - d0, md);
+}
+
+// one table level as 2^w arkworks Affine images, `stride` bytes apart
+template <class C>
+static int t_fb_table_level(const uint8_t* g_img, int w, int level, uint8_t* out, size_t stride) {
+  using E = typename C::E;
+  using El = typename E::T;
+  typename E::Md md;
+  std::vector<XyzzT<El>> xyzz;
+  fb_host_levels<E>(xyzz, g_img, (uint32_t)w, (uint32_t)level, (uint32_t)level + 1, md);
+  const size_t n = xyzz.size();
+  std::vector<XyzzDevT<El>> dev(n);
+  for (size_t i = 0; i < n; i++) dev[i].p = xyzz[i];
+  std::vector<El> prefix(n);
+  fb_normalize_run<E, false>(dev.data(), 0, n, prefix.data(), out, stride, md);
+  return 0;
+}
+
+// out[i] = scalar_i * g: the whole table, windowed_mul per scalar, normalisation in runs of FB_NORM_RUN.  flags as mi355_msm_fixed_mul.
+template <class C>
+static int t_fb_mul(const uint8_t* g_img, int w, const uint8_t* scalars, size_t n, unsigned flags, uint8_t* out, size_t stride) {
+  using E = typename C::E;
+  using El = typename E::T;
+  typename E::Md md;
+  const uint32_t levels = fb_levels((uint32_t)w);
+  std::vector<XyzzT<El>> xyzz;
+  fb_host_levels<E>(xyzz, g_img, (uint32_t)w, 0, levels, md);
+  std::vector<AffineDevT<El>> table(xyzz.size());
+  fb_host_records<E>(table.data(), xyzz.data(), xyzz.size(), md);
+  std::vector<XyzzDevT<El>> res(n);
+  for (size_t i = 0; i < n; i++) {
+    uint32_t s[8];
+    memcpy(s, scalars + 32 * i, 32);
+    fb_windowed_mul<E>(res[i].p, table.data(), s, (flags & 1) != 0, (uint32_t)w, levels, md);
+  }
+  std::vector<El> prefix(n);
+  for (size_t lo = 0; lo < n; lo += FB_NORM_RUN) {
+    const size_t hi = lo + FB_NORM_RUN < n ? lo + FB_NORM_RUN : n;
+    if (flags & 2)
+      fb_normalize_run<E, true>(res.data(), lo, hi, prefix.data(), out, stride, md);
+    else
+      fb_normalize_run<E, false>(res.data(), lo, hi, prefix.data(), out, stride, md);
+  }
+  return 0;
+}
+
+extern "C" {
+// the digits of one 32-byte scalar for window size w: fb_levels(w) words
+int ht_fb_digits(const uint8_t* scalar, int w, uint32_t* out) {
+  if (!scalar || !out || w < 1 || w > (int)FB_MAX_WINDOW) return -1;
+  uint32_t s[8];
+  memcpy(s, scalar, 32);
+  const uint32_t levels = fb_levels((uint32_t)w);
+  for (uint32_t j = 0; j < levels; j++) out[j] = fb_digit(s, j, (uint32_t)w);
+  return (int)levels;
+}
+int ht_fb_table_level(int curve, const uint8_t* g_img, int w, int level, uint8_t* out, size_t stride) {
+  if (!g_img || !out || w < 1 || w > (int)FB_MAX_WINDOW || level < 0 || level >= (int)fb_levels((uint32_t)w) || stride % 4) return -1;
+  DISPATCH_C(curve, t_fb_table_level, g_img, w, level, out, stride)
+}
+int ht_fb_mul(int curve, const uint8_t* g_img, int w, const uint8_t* scalars, size_t n, unsigned flags, uint8_t* out, size_t stride) {
+  if (!g_img || (n && (!scalars || !out)) || w < 1 || w > (int)FB_MAX_WINDOW || stride % 4 || (flags & ~3u)) return -1;
+  DISPATCH_C(curve, t_fb_mul, g_img, w, scalars, n, flags, out, stride)
+}
+}

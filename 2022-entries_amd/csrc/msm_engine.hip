@@ -2715,3 +2715,4 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 }  // extern "C"
 
 #include "msm_stream.hpp"
+#include "msm_fixed.hpp"

@@ -113,6 +113,12 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_stream_finalize": [vp, vp],
         "mi355_msm_stream_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_stream_destroy": [vp],
+        "mi355_msm_fixed_create": [ctypes.POINTER(vp), ci, ci, vp, ci, sz],
+        "mi355_msm_fixed_mul": [vp, vp, sz, vp, sz, ctypes.c_uint],
+        "mi355_msm_fixed_mul_device": [vp, vp, sz, vp, sz, ctypes.c_uint, vp],
+        "mi355_msm_fixed_set_option": [vp, ctypes.c_char_p, ctypes.c_long],
+        "mi355_msm_fixed_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_fixed_destroy": [vp],
         "mi355_msm_trim": [],
         "mi355_msm_pool_stats": [ctypes.POINTER(ctypes.c_uint64), sz],
     }
@@ -121,6 +127,8 @@ def load_library() -> ctypes.CDLL:
         fn.argtypes = args
         fn.restype = _RustError
     lib.mi355_msm_version.restype = ctypes.c_char_p
+    lib.mi355_msm_fixed_window_size.argtypes = [sz]
+    lib.mi355_msm_fixed_window_size.restype = sz
     lib.mi355_msm_job_done.argtypes = [vp]
     lib.mi355_msm_job_done.restype = ci
     _LIB = lib
@@ -545,6 +553,116 @@ class HashMapPippenger(ChunkedPippenger):
     scalar (an ``Fr`` value) to that entry modulo r; the MSM runs when ``max_msm_buffer`` DISTINCT bases are buffered."""
 
     _HASHMAP = 1
+
+
+class WindowTable:
+    """The window table of ONE base, resident on one GPU (mi355_msm_fixed_*): what ``FixedBase::get_window_table`` returns in arkworks
+    (ARK ec/src/msm/fixed_base.rs:19-58), built on the device.  ``msm`` multiplies the base by every scalar of a batch."""
+
+    def __init__(self, g, curve="bls12_377_g1", window: int = 0, device: Optional[int] = None, expected_scalars: int = 0):
+        self.curve = _curve_id(curve)
+        self.handle = ctypes.c_void_p()
+        b = _Buf(g)
+        if b.is_device:
+            raise TypeError("the base is one Affine image in host memory")
+        if b.nbytes != affine_stride(self.curve):
+            raise ValueError(f"base image of {b.nbytes} bytes: one {affine_stride(self.curve)}-byte Affine image expected")
+        self._lib = load_library()
+        _check(self._lib.mi355_msm_fixed_create(ctypes.byref(self.handle), self.curve, -1 if device is None else device, b.ptr, int(window),
+                                                int(expected_scalars)))
+        self.device = self.query("device")
+
+    def msm(self, scalars, montgomery: bool = False, projective: bool = False, stride: Optional[int] = None):
+        """``out[i] = scalars[i] * g`` as arkworks Affine images (``projective``: normalised Projective images), ``stride`` bytes apart
+        (default: the image size).  ``scalars``: 32-byte little-endian integers, all 256 bits significant; ``montgomery``: arkworks ``Fr``
+        images, which is what ``FixedBase::msm`` takes.  bytes in, bytes out; a NumPy array or a torch CPU tensor gives an array /
+        tensor of shape (n, stride); a torch GPU tensor is read in place and gives a GPU tensor, ready for ``set_bases``."""
+        size = projective_bytes(self.curve) if projective else affine_stride(self.curve)
+        stride = size if stride is None else int(stride)
+        b = _Buf(scalars)
+        if b.nbytes % SCALAR_BYTES:
+            raise ValueError("scalars image is not a multiple of 32 bytes")
+        if stride % 4 or stride < size:
+            raise ValueError(f"stride {stride} must be a multiple of 4 and at least the {size}-byte image")
+        if not self.handle:
+            raise MsmError(-1, "the window table is closed")
+        if b.is_device and b.device_index != self.device:
+            raise MsmError(-1, f"scalars live on cuda:{b.device_index} but this table is bound to device {self.device}")
+        n = b.nbytes // SCALAR_BYTES
+        flags = (1 if montgomery else 0) | (2 if projective else 0)
+        if b.is_device:
+            import torch
+
+            out = torch.zeros((n, stride), dtype=torch.uint8, device=b.keep.device)
+            if n:
+                _check(self._lib.mi355_msm_fixed_mul_device(self.handle, out.data_ptr(), stride, b.ptr, n, flags, b.stream))
+            return out
+        import numpy as np
+
+        out = np.zeros((n, stride), dtype=np.uint8)
+        if n:
+            _check(self._lib.mi355_msm_fixed_mul(self.handle, out.ctypes.data, stride, b.ptr, n, flags))
+        if hasattr(scalars, "data_ptr") and hasattr(scalars, "is_cuda"):
+            import torch
+
+            return torch.from_numpy(out)
+        if hasattr(scalars, "__array_interface__"):
+            return out
+        return out.tobytes()
+
+    def set_option(self, key: str, value: int) -> None:
+        _check(self._lib.mi355_msm_fixed_set_option(self.handle, key.encode(), int(value)))
+
+    def query(self, key: str) -> int:
+        """ "window_bits", "levels", "table_bytes", "signed_digits", "build_us", "device", "last_mul_us", "last_device_us", "max_chunk", "work_bytes" """
+        v = ctypes.c_uint64(0)
+        _check(self._lib.mi355_msm_fixed_query(self.handle, key.encode(), ctypes.byref(v)))
+        return int(v.value)
+
+    def close(self) -> None:
+        if self.handle:
+            _check(self._lib.mi355_msm_fixed_destroy(self.handle))
+            self.handle = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FixedBase:
+    """Shape of arkworks' ``FixedBase`` (ARK ec/src/msm/fixed_base.rs:8-97)."""
+
+    @staticmethod
+    def get_mul_window_size(num_scalars: int) -> int:
+        """arkworks' rule (3 below 32 scalars, else ``ln_without_floats``), for API parity: a CPU cache heuristic that no table here
+        uses -- ``WindowTable.query("window_bits")`` says what one does."""
+        return int(load_library().mi355_msm_fixed_window_size(int(num_scalars)))
+
+    @staticmethod
+    def get_window_table(g, curve="bls12_377_g1", window: int = 0, device: Optional[int] = None, expected_scalars: int = 0) -> WindowTable:
+        return WindowTable(g, curve=curve, window=window, device=device, expected_scalars=expected_scalars)
+
+    @staticmethod
+    def msm(table: WindowTable, scalars, montgomery: bool = True, projective: bool = True):
+        """``FixedBase::msm(.., table, v: &[ScalarField]) -> Vec<Projective>``: Fr images in, Projective images out by default."""
+        return table.msm(scalars, montgomery=montgomery, projective=projective)
+
+
+def fixed_base_msm(g, scalars, curve="bls12_377_g1", montgomery: bool = False, projective: bool = False):
+    """One call: build the table of ``g`` for this many scalars, multiply, free the table.  Affine images of ``scalars[i] * g``."""
+    nbytes = _Buf(scalars).nbytes
+    if nbytes % SCALAR_BYTES:
+        raise ValueError("scalars image is not a multiple of 32 bytes")
+    with WindowTable(g, curve=curve, expected_scalars=max(nbytes // SCALAR_BYTES, 1)) as table:
+        return table.msm(scalars, montgomery=montgomery, projective=projective)
 
 
 def fold_partials(partials: Sequence[bytes], curve="bls12_377_g1") -> bytes:

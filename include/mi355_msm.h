@@ -304,6 +304,44 @@ RustError mi355_msm_stream_finalize(mi355_msm_stream* s, void* out_projective);
 RustError mi355_msm_stream_query(mi355_msm_stream* s, const char* key, uint64_t* value);
 RustError mi355_msm_stream_destroy(mi355_msm_stream* s);
 
+/* ---- batch fixed-base scalar multiplication (ARK ec/src/msm/fixed_base.rs:8-97) ------------------------------------------------
+ * out[i] = s_i * g for ONE base g and n scalars: FixedBase::{get_mul_window_size, get_window_table, windowed_mul, msm} followed by
+ * batch_normalization_into_affine -- what a KZG / Groth16 setup runs for [tau^i] G, and what produces the bases an MSM consumes.
+ * A handle is the window table of one base, resident on one device: level j holds d * 2^(w j) * g for every w-bit digit d
+ * (ceil(256 / w) levels, unsigned digits), built on the device by mi355_msm_fixed_create.
+ *   g        one arkworks Affine image (104 B / 200 B; only the bytes up to the flag byte are read; the flag byte is authoritative).
+ *            ANY curve point: off the subgroup, of small order, or flagged infinity (every output is then infinity).
+ *   scalars  32 B little-endian integers; ALL 256 bits count -- the result is the integer multiple, never reduced modulo r, because g
+ *            need not have order r.  Flag bit 0: the 32 B are arkworks Fr images (a * 2^256 mod r) and are converted first
+ *            (FixedBase::msm takes &[ScalarField] and calls into_bigint, fixed_base.rs:66-67); defined for any 256-bit image.
+ *   out      one image per scalar, in input order, out_stride bytes apart (a multiple of 4, at least the image size; bytes between
+ *            two images are not written).  Default: arkworks Affine images -- x, y canonical, flag byte 0, pad bytes 0; the point at
+ *            infinity is all zeros with flag 1 (arkworks 0.4) -- ready for mi355_msm_set_bases[_device] and mi355_msm_check_bases.
+ *            Flag bit 1: normalised Projective images, byte for byte what mi355_msm_run writes for the one-pair MSM (g, s_i).
+ * Results never depend on the window size, on chunking, or on host versus device pointers.
+ * window_bits 1..20, 0 = automatic from expected_scalars (0 = unknown: plan for a large batch): the cheapest of
+ * levels(w) * (2 * 2^w + expected_scalars) additions with the table inside the Infinity Cache (at most 16 bits for G1: 134 MB, 15 for
+ * G2: 151 MB).  mi355_msm_fixed_window_size is arkworks' own rule -- 3 below 32 scalars, else ceil(log2 n) * 69 / 100 -- exported for
+ * API parity only: it is a CPU cache heuristic and no handle uses it.
+ * mi355_msm_fixed_mul takes HOST pointers, mi355_msm_fixed_mul_device DEVICE pointers (4-byte aligned) and the hipStream_t on which
+ * the scalars become ready (NULL = the default stream); its work is enqueued there and the call returns when the output is written.
+ * n = 0 is a success that writes nothing.  Work memory does not grow with n: calls run in chunks of "max_chunk" scalars
+ * (mi355_msm_fixed_set_option, default 2^22, 0 restores it; a test hook -- results do not depend on it).
+ * Queries: "window_bits", "levels", "table_bytes", "signed_digits" (0), "build_us" (host clock around the table build), "device",
+ * "last_mul_us" (host clock around the most recent call), "last_device_us" (the same call between events on the stream it ran on),
+ * "max_chunk", "work_bytes" (chunk buffers held).
+ * Errors: -1 with a message for null pointers, a stride too small or not a multiple of 4, an unknown curve, window_bits outside 0..20,
+ * unknown flag bits -- decided before any device call; hipErrorNoDevice without a GPU. */
+typedef struct mi355_msm_fixed mi355_msm_fixed;
+size_t mi355_msm_fixed_window_size(size_t num_scalars);
+RustError mi355_msm_fixed_create(mi355_msm_fixed** out, int curve, int device, const void* base_affine, int window_bits, size_t expected_scalars);
+RustError mi355_msm_fixed_mul(mi355_msm_fixed* fb, void* out, size_t out_stride, const void* scalars, size_t n, unsigned flags);
+RustError mi355_msm_fixed_mul_device(mi355_msm_fixed* fb, void* d_out, size_t out_stride, const void* d_scalars, size_t n, unsigned flags,
+                                     void* stream);
+RustError mi355_msm_fixed_set_option(mi355_msm_fixed* fb, const char* key, long value);
+RustError mi355_msm_fixed_query(mi355_msm_fixed* fb, const char* key, uint64_t* value);
+RustError mi355_msm_fixed_destroy(mi355_msm_fixed* fb);
+
 /* Sum `count` projective images (any Z) into one normalised image: the multi-GPU combine step
  * ("final 8-point curve add").  Pure host arithmetic on <= a few dozen points; no device needed. */
 RustError mi355_msm_fold(int curve, void* out_projective, const void* projective, size_t count);

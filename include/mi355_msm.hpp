@@ -167,4 +167,47 @@ inline G1Projective msm_chunks(const std::vector<G1Affine>& bases, const std::ve
   return out;
 }
 
+// arkworks' FixedBase (ARK ec/src/msm/fixed_base.rs:8-97): out[i] = scalars[i] * g through a window table that lives on the GPU.
+// `scalars_fr` are Fr values (Montgomery form), as FixedBase::msm takes them; the results are normalised.
+struct WindowTable {   // what get_window_table returns: owns the device table
+  mi355_msm_fixed* handle = nullptr;
+  WindowTable() = default;
+  WindowTable(const WindowTable&) = delete;
+  WindowTable& operator=(const WindowTable&) = delete;
+  WindowTable(WindowTable&& o) noexcept : handle(o.handle) { o.handle = nullptr; }
+  uint64_t query(const char* key) const {
+    uint64_t v = 0;
+    check(mi355_msm_fixed_query(handle, key, &v));
+    return v;
+  }
+  ~WindowTable() {
+    if (handle) {
+      RustError e = mi355_msm_fixed_destroy(handle);
+      if (e.message) std::free(e.message);
+    }
+  }
+};
+
+struct FixedBase {
+  // arkworks' rule (a CPU cache heuristic, for parity; WindowTable::query("window_bits") says what a table uses)
+  static size_t get_mul_window_size(size_t num_scalars) { return mi355_msm_fixed_window_size(num_scalars); }
+  // window = 0: the engine chooses for `expected_scalars` (0 = a large batch)
+  static WindowTable get_window_table(const G1Affine& g, int window = 0, int curve = MI355_BLS12_377_G1, size_t expected_scalars = 0) {
+    WindowTable t;
+    check(mi355_msm_fixed_create(&t.handle, curve, -1, &g, window, expected_scalars));
+    return t;
+  }
+  static std::vector<G1Projective> msm(const WindowTable& table, const std::vector<BigInteger256>& scalars_fr) {
+    std::vector<G1Projective> out(scalars_fr.size());
+    check(mi355_msm_fixed_mul(table.handle, out.data(), sizeof(G1Projective), scalars_fr.data(), scalars_fr.size(), 1u | 2u));
+    return out;
+  }
+  // msm + batch_normalization_into_affine: Affine images, ready for multi_scalar_mult_init
+  static std::vector<G1Affine> msm_affine(const WindowTable& table, const std::vector<BigInteger256>& scalars_fr) {
+    std::vector<G1Affine> out(scalars_fr.size());
+    check(mi355_msm_fixed_mul(table.handle, out.data(), sizeof(G1Affine), scalars_fr.data(), scalars_fr.size(), 1u));
+    return out;
+  }
+};
+
 }  // namespace mi355

@@ -143,6 +143,16 @@ pub mod sys {
         pub fn mi355_msm_stream_finalize(s: *mut c_void, out_projective: *mut c_void) -> Error;
         pub fn mi355_msm_stream_query(s: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
         pub fn mi355_msm_stream_destroy(s: *mut c_void) -> Error;
+        // batch fixed-base multiplication (ark-ec msm/fixed_base.rs): one resident window table, out[i] = s_i * g
+        pub fn mi355_msm_fixed_window_size(num_scalars: usize) -> usize;
+        pub fn mi355_msm_fixed_create(out: *mut *mut c_void, curve: c_int, device: c_int, base_affine: *const c_void, window_bits: c_int,
+                                      expected_scalars: usize) -> Error;
+        pub fn mi355_msm_fixed_mul(fb: *mut c_void, out: *mut c_void, out_stride: usize, scalars: *const c_void, n: usize, flags: c_uint) -> Error;
+        pub fn mi355_msm_fixed_mul_device(fb: *mut c_void, d_out: *mut c_void, out_stride: usize, d_scalars: *const c_void, n: usize, flags: c_uint,
+                                          stream: *mut c_void) -> Error;
+        pub fn mi355_msm_fixed_set_option(fb: *mut c_void, key: *const c_char, value: c_long) -> Error;
+        pub fn mi355_msm_fixed_query(fb: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
+        pub fn mi355_msm_fixed_destroy(fb: *mut c_void) -> Error;
     }
 }
 
@@ -447,6 +457,85 @@ pub mod stream_pippenger {
         /// Update the final result with (base, scalar) pairs in the hash map.
         pub fn finalize(self) -> G1Projective {
             self.stream.finalize()
+        }
+    }
+}
+
+/// arkworks' `FixedBase` (ark-ec `msm::fixed_base`, fixed_base.rs:8-97) over the engine: `get_mul_window_size`, `get_window_table`,
+/// `windowed_mul` and `msm` with the reference's names and argument meaning.  The table lives in device memory -- `WindowTable` owns
+/// it -- so `scalar_size` and `window` are taken by `get_window_table` alone (`window` = 0 lets the engine choose; arkworks' own
+/// `get_mul_window_size` is a CPU cache heuristic and is exported for parity).  Results are normalised, so they equal the CPU path's
+/// after `into_affine`.
+pub mod fixed_base {
+    use super::sys;
+    use super::{Fr, G1Affine};
+    use ark_ec::AffineCurve;
+    use ark_std::Zero;
+    use std::os::raw::{c_int, c_void};
+
+    type G1Projective = <G1Affine as AffineCurve>::Projective;
+
+    #[cfg(not(feature = "bls12_381"))]
+    const CURVE: c_int = sys::MI355_BLS12_377_G1;
+    #[cfg(feature = "bls12_381")]
+    const CURVE: c_int = sys::MI355_BLS12_381_G1;
+
+    const SCALARS_MONTGOMERY: std::os::raw::c_uint = 1;
+    const PROJECTIVE: std::os::raw::c_uint = 2;
+
+    fn check(err: super::Error) {
+        if err.code != 0 {
+            panic!("{}", String::from(err));
+        }
+    }
+
+    /// What `get_window_table` returns in arkworks is `Vec<Vec<Affine>>`; here it is a handle to the same table on the GPU.
+    pub struct WindowTable(*mut c_void);
+
+    impl Drop for WindowTable {
+        fn drop(&mut self) {
+            if !self.0.is_null() {
+                let _ = unsafe { sys::mi355_msm_fixed_destroy(self.0) };
+            }
+        }
+    }
+
+    pub struct FixedBase;
+
+    impl FixedBase {
+        pub fn get_mul_window_size(num_scalars: usize) -> usize {
+            unsafe { sys::mi355_msm_fixed_window_size(num_scalars) }
+        }
+
+        /// `scalar_size` is accepted for the reference's shape; every table covers all 256 bits of a scalar.
+        pub fn get_window_table(_scalar_size: usize, window: usize, g: G1Projective) -> WindowTable {
+            let base: G1Affine = g.into();
+            let mut h: *mut c_void = std::ptr::null_mut();
+            check(unsafe { sys::mi355_msm_fixed_create(&mut h, CURVE, -1, &base as *const _ as *const c_void, window as c_int, 0) });
+            WindowTable(h)
+        }
+
+        pub fn windowed_mul(_outerc: usize, _window: usize, multiples_of_g: &WindowTable, scalar: &Fr) -> G1Projective {
+            Self::msm(0, 0, multiples_of_g, std::slice::from_ref(scalar))[0]
+        }
+
+        pub fn msm(_scalar_size: usize, _window: usize, table: &WindowTable, v: &[Fr]) -> Vec<G1Projective> {
+            let mut out = vec![G1Projective::zero(); v.len()];
+            check(unsafe {
+                sys::mi355_msm_fixed_mul(table.0, out.as_mut_ptr() as *mut c_void, std::mem::size_of::<G1Projective>(), v.as_ptr() as *const c_void,
+                                         v.len(), SCALARS_MONTGOMERY | PROJECTIVE)
+            });
+            out
+        }
+
+        /// `msm` followed by `batch_normalization_into_affine`, in one pass on the device
+        pub fn msm_affine(table: &WindowTable, v: &[Fr]) -> Vec<G1Affine> {
+            let mut out = vec![G1Affine::zero(); v.len()];
+            check(unsafe {
+                sys::mi355_msm_fixed_mul(table.0, out.as_mut_ptr() as *mut c_void, std::mem::size_of::<G1Affine>(), v.as_ptr() as *const c_void,
+                                         v.len(), SCALARS_MONTGOMERY)
+            });
+            out
         }
     }
 }
