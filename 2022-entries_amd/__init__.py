@@ -6,6 +6,9 @@ The directory name (``2022-entries_amd``) is not a Python identifier; import it 
 from .msm import (  # noqa: F401
     CURVE_IDS,
     CheckResult,
+    CodecResult,
+    compress_points,
+    decompress_points,
     MsmError,
     check_points,
     MultiScalarMultContext,

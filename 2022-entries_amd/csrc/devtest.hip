@@ -136,6 +136,9 @@ hipError_t launch_op(int op, const uint32_t* d_in, int in_words, uint32_t* d_out
     DT_CASE(DT_FE_WEAK_REDUCE)
     DT_CASE(DT_FR_FROM_MONT)
     DT_CASE(DT_FR_TO_MONT)
+    DT_CASE(DT_SQRT)
+    DT_CASE(DT_SQRT2)
+    DT_CASE(DT_LEX_LARGEST)
     DT_CASE(DT_EL_MUL)
     DT_CASE(DT_EL_SQR)
     DT_CASE(DT_EL_MUL_C)

@@ -9,6 +9,7 @@
 #pragma once
 #include "curve.hpp"
 #include "digits.hpp"
+#include "sqrt.hpp"
 #include "te.hpp"
 
 namespace msm {
@@ -37,7 +38,10 @@ enum DevtestOp : int {
   DT_FE_WEAK_REDUCE = 20,    // in a (limbs < 2^31, value < 32p)  out Fe
   DT_FR_FROM_MONT = 21, // in 8 words (any 256-bit integer)   out 8 words   fr_from_montgomery of the curve's scalar field (digits.hpp)
   DT_FR_TO_MONT = 22,   // in 8 words (any 256-bit integer)   out 8 words   fr_to_montgomery
-  DT_COUNT = 23,
+  DT_SQRT = 23,         // in a (Fe, class M)                out Fe, 1 word: has a root     fe_sqrt of the curve's base field (sqrt.hpp)
+  DT_SQRT2 = 24,        // in a (Fe2, class M components)    out Fe2, 1 word               el_sqrt over Fp2: G2 curves only
+  DT_LEX_LARGEST = 25,  // in y (T, class M components)      out 1 word: y > -y            el_lex_largest
+  DT_COUNT = 26,
   DT_PAIR = 64          // + a G2 op in [DT_EL_MUL, DT_DBL]: the same records with two lanes per record (fp2pair.hpp; device only)
 };
 
@@ -60,6 +64,9 @@ MSM_HD void devtest_shape(int op, int EW, int& in_words, int& out_words) {
     case DT_TE_DBL: in_words = 4 * NL; out_words = 4 * NL; break;
     case DT_FE_WEAK_REDUCE: in_words = NL; out_words = NL; break;
     case DT_FR_FROM_MONT: case DT_FR_TO_MONT: in_words = 8; out_words = 8; break;
+    case DT_SQRT: in_words = NL; out_words = NL + 1; break;
+    case DT_SQRT2: if (EW == 2 * NL) { in_words = 2 * NL; out_words = 2 * NL + 1; } break;
+    case DT_LEX_LARGEST: in_words = EW; out_words = 1; break;
     default: break;
   }
 }
@@ -127,6 +134,24 @@ MSM_HD void devtest_apply(const uint32_t* in, uint32_t* out) {
     dt_load(a, in);
     fe_weak_reduce<F>(a);
     dt_store(out, a);
+  } else if constexpr (OP == DT_SQRT) {
+    Fe a, r;
+    dt_load(a, in);
+    const bool ok = fe_sqrt<F>(r, a, md);
+    dt_store(out, r);
+    out[NL] = ok ? 1u : 0u;
+  } else if constexpr (OP == DT_SQRT2) {
+    if constexpr (EW == 2 * NL) {
+      T a, r;
+      dt_load(a, in);
+      const bool ok = el_sqrt(r, a, md, (E*)nullptr);
+      dt_store(out, r);
+      out[EW] = ok ? 1u : 0u;
+    }
+  } else if constexpr (OP == DT_LEX_LARGEST) {
+    T a;
+    dt_load(a, in);
+    out[0] = el_lex_largest<E>(a, md) ? 1u : 0u;
   } else if constexpr (OP == DT_EL_MUL || OP == DT_EL_MUL_C || OP == DT_EL_MUL_C_BIG) {
     T a, b, r;
     dt_load(a, in);

@@ -506,6 +506,9 @@ static int t_devop(int op, const uint32_t* in, int iw, uint32_t* out, int ow, si
       DT_CASE(DT_FE_WEAK_REDUCE)
       DT_CASE(DT_FR_FROM_MONT)
       DT_CASE(DT_FR_TO_MONT)
+      DT_CASE(DT_SQRT)
+      DT_CASE(DT_SQRT2)
+      DT_CASE(DT_LEX_LARGEST)
       DT_CASE(DT_EL_MUL)
       DT_CASE(DT_EL_SQR)
       DT_CASE(DT_EL_MUL_C)
@@ -739,3 +742,115 @@ int ht_fb_mul(int curve, const uint8_t* g_img, int w, const uint8_t* scalars, si
   DISPATCH_C(curve, t_fb_mul, g_img, w, scalars, n, flags, out, stride)
 }
 }
+
+// ---- square roots, the y ordering and the compressed-record codec (sqrt.hpp, point_codec.hpp) with the limb-bound checker armed ----
+// Elements cross as ABI images (x * 2^384 mod p, canonical; Fp2: c0 | c1), as in ht_el_mul.  The device twins are the sqrt / sqrt2 /
+// lex_largest ops of libmsm_devtest.so and k_decompress_points / k_compress_points (kernels_codec.hip).
+#include "point_codec.hpp"
+
+template <class C>
+static void t_el_sqrt(const uint8_t* a, uint8_t* out, int* has_root) {
+  using E = typename C::E;
+  typename E::Md md;
+  typename E::T x, z;
+  uint32_t wa[E::WORDS], wo[E::WORDS];
+  memcpy(wa, a, 4 * E::WORDS);
+  E::from_abi(x, wa, md);
+  *has_root = el_sqrt(z, x, md, (E*)nullptr) ? 1 : 0;
+  E::to_abi(wo, z, md);
+  memcpy(out, wo, 4 * E::WORDS);
+}
+
+template <class C>
+static void t_lex_largest(const uint8_t* a, int* larger) {
+  using E = typename C::E;
+  typename E::Md md;
+  typename E::T x;
+  uint32_t wa[E::WORDS];
+  memcpy(wa, a, 4 * E::WORDS);
+  E::from_abi(x, wa, md);
+  *larger = el_lex_largest<E>(x, md) ? 1 : 0;
+}
+
+template <class C>
+static int t_decompress_points(int serialized, const uint8_t* in, size_t n, uint8_t* out, size_t stride, uint8_t* status) {
+  using E = typename C::E;
+  typename E::Md md;
+  constexpr size_t CB = E::WORDS * 4;
+  if (serialized) stride = 2 * CB;
+  if (stride < 2 * CB + (serialized ? 0 : 1) || (stride & 3)) return -1;
+  for (size_t i = 0; i < n; i++) {
+    uint32_t w[E::WORDS], o[2 * E::WORDS];
+    uint8_t inf = 0;
+    memcpy(w, in + i * CB, CB);
+    status[i] = serialized ? decompress_point<E, true>(o, inf, w, md) : decompress_point<E, false>(o, inf, w, md);
+    memset(out + i * stride, 0, stride);
+    memcpy(out + i * stride, o, 2 * CB);
+    if (!serialized) out[i * stride + 2 * CB] = inf;
+  }
+  return 0;
+}
+
+template <class C>
+static int t_compress_points(int serialized, const uint8_t* in, size_t stride, size_t n, uint8_t* out, uint8_t* status) {
+  using E = typename C::E;
+  typename E::Md md;
+  constexpr size_t CB = E::WORDS * 4;
+  if (serialized) stride = 2 * CB;
+  if (stride < 2 * CB + (serialized ? 0 : 1)) return -1;
+  for (size_t i = 0; i < n; i++) {
+    uint32_t w[2 * E::WORDS], o[E::WORDS];
+    uint8_t inf = 0;
+    memcpy(w, in + i * stride, 2 * CB);
+    const uint8_t flag = serialized ? 0 : in[i * stride + 2 * CB];
+    status[i] = serialized ? compress_point<E, true>(o, inf, w, flag, md) : compress_point<E, false>(o, inf, w, flag, md);
+    memcpy(out + i * CB, o, CB);
+  }
+  return 0;
+}
+
+extern "C" {
+
+// curve 0 / 1: Fp of BLS12-377 / BLS12-381 (48-byte images)
+int ht_fe_sqrt(int curve, const uint8_t* a, uint8_t* out, int* has_root) {
+  if (!a || !out || !has_root) return -1;
+  switch (curve) {
+    case 0: t_el_sqrt<Bls12_377_G1>(a, out, has_root); return 0;
+    case 1: t_el_sqrt<Bls12_381_G1>(a, out, has_root); return 0;
+    default: return -1;
+  }
+}
+// curve 2 / 3: Fp2 of BLS12-377 / BLS12-381 (96-byte images)
+int ht_fe2_sqrt(int curve, const uint8_t* a, uint8_t* out, int* has_root) {
+  if (!a || !out || !has_root) return -1;
+  switch (curve) {
+    case 2: t_el_sqrt<Bls12_377_G2>(a, out, has_root); return 0;
+    case 3: t_el_sqrt<Bls12_381_G2>(a, out, has_root); return 0;
+    default: return -1;
+  }
+}
+// the coordinate field of curve 0..3
+int ht_lex_largest(int curve, const uint8_t* a, int* larger) {
+  if (!a || !larger) return -1;
+  DISPATCH_C(curve, t_lex_largest, a, larger)
+}
+int ht_decompress_points(int curve, int serialized, const uint8_t* in, size_t n, uint8_t* out, size_t stride, uint8_t* status) {
+  if (curve < 0 || curve > 3 || (n && (!in || !out || !status))) return -1;
+  switch (curve) {
+    case 0: return t_decompress_points<Bls12_377_G1>(serialized, in, n, out, stride, status);
+    case 1: return t_decompress_points<Bls12_381_G1>(serialized, in, n, out, stride, status);
+    case 2: return t_decompress_points<Bls12_377_G2>(serialized, in, n, out, stride, status);
+    default: return t_decompress_points<Bls12_381_G2>(serialized, in, n, out, stride, status);
+  }
+}
+int ht_compress_points(int curve, int serialized, const uint8_t* in, size_t stride, size_t n, uint8_t* out, uint8_t* status) {
+  if (curve < 0 || curve > 3 || (n && (!in || !out || !status))) return -1;
+  switch (curve) {
+    case 0: return t_compress_points<Bls12_377_G1>(serialized, in, stride, n, out, status);
+    case 1: return t_compress_points<Bls12_381_G1>(serialized, in, stride, n, out, status);
+    case 2: return t_compress_points<Bls12_377_G2>(serialized, in, stride, n, out, status);
+    default: return t_compress_points<Bls12_381_G2>(serialized, in, stride, n, out, status);
+  }
+}
+
+}  // extern "C"

@@ -376,6 +376,8 @@ struct mi355_msm_ctx {
   long opt_table_levels = 0;      // with precompute: table levels k (0 = one per window); windows g, g + G, ... share bucket set g
   long opt_validate_bases = 0;   // 1: set_bases* classify the new base set first (check_bases_impl) and refuse it, keeping the old one, if a point is invalid
   bool bases_validated = false;   // the current base set passed that check
+  long opt_codec_chunk = 0;      // records per launch of the point codec (msm_codec.hpp); 0 = the default, 2^22
+  DevBuf codec_in, codec_out, codec_stat[2];   // one chunk of compressed records / of images or uncompressed records / of status bytes
   long opt_assume_subgroup = 0;   // 1: every base is in the order-r subgroup (r P = O), so a scalar k in (r/2, r) may run as (r - k)(-P)
   long opt_anchor = 1;            // option "anchor_window": 1 = end the signed-digit carry chain at the last full window where that saves additions
   bool anchor_armed = false;      // ... for the run under way: the sum of its bases is at hand (run_device_t)
@@ -2069,7 +2071,8 @@ RustError mi355_msm_destroy(mi355_msm_ctx* ctx) {
     }
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->own_stream);
-    DevBuf* bufs[] = {&ctx->bases, &ctx->inf, &ctx->scalars, &ctx->te_bases, &ctx->flags, &ctx->stateless_raw[0], &ctx->stateless_raw[1], &ctx->stateless_raw[2]};
+    DevBuf* bufs[] = {&ctx->bases, &ctx->inf, &ctx->scalars, &ctx->te_bases, &ctx->flags, &ctx->stateless_raw[0], &ctx->stateless_raw[1], &ctx->stateless_raw[2],
+                      &ctx->codec_in, &ctx->codec_out, &ctx->codec_stat[0], &ctx->codec_stat[1]};
     for (DevBuf* b : bufs) b->release();
     release_work_buffers(ctx);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -2332,6 +2335,10 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value) 
       ctx->opt_scalars_to_montgomery = value != 0;
     } else if (k == "validate_bases") {
       ctx->opt_validate_bases = value != 0;
+    } else if (k == "codec_chunk") {
+      // records per launch of decompress_points / compress_points / set_bases_compressed (0 = the default, 2^22): a test puts seams at small n
+      if (value < 0 || value >= (1l << 31)) bad_arg("codec_chunk %ld out of range [0, 2^31)", value);
+      ctx->opt_codec_chunk = value;
     } else if (k == "assume_subgroup") {
       ctx->opt_assume_subgroup = value != 0;
     } else if (k == "carry") {
@@ -2476,6 +2483,8 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
       *value = ctx->opt_assume_subgroup ? 1 : 0;
     else if (k == "validate_bases")
       *value = ctx->opt_validate_bases ? 1 : 0;
+    else if (k == "codec_chunk")
+      *value = ctx->opt_codec_chunk > 0 ? (uint64_t)ctx->opt_codec_chunk : (uint64_t)1 << 22;
     else if (k == "bases_validated")
       *value = ctx->bases_validated ? 1 : 0;
     else if (k == "carry")
@@ -2716,3 +2725,4 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 
 #include "msm_stream.hpp"
 #include "msm_fixed.hpp"
+#include "msm_codec.hpp"

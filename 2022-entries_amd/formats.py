@@ -27,15 +27,40 @@ import numpy as np
 from .msm import MultiScalarMultContext, _check, _curve_id, _COORD_BYTES, load_library, projective_bytes
 
 
-def record_bytes(curve) -> int:
-    """Bytes of one uncompressed serialized affine point (96 for G1, 192 for G2)."""
-    return 2 * _COORD_BYTES[_curve_id(curve)]
+def record_bytes(curve, compressed: bool = False) -> int:
+    """Bytes of one serialized affine point: uncompressed 96 for G1, 192 for G2; ``compressed`` (x and two flag bits) 48 / 96."""
+    return (1 if compressed else 2) * _COORD_BYTES[_curve_id(curve)]
 
 
-def read_points_bin(path: str, curve="bls12_377_g1", validate: bool = False) -> Tuple[bytes, int]:
-    """``points.bin`` -> (records without the length prefix, count).  ``validate=True`` is arkworks' ``deserialize_uncompressed``
+def _read_compressed_points_bin(path: str, curve, validate: bool) -> Tuple[bytes, int]:
+    rb = record_bytes(curve, compressed=True)
+    with open(path, "rb") as f:
+        head = f.read(8)
+        if len(head) != 8:
+            raise ValueError(f"{path}: no element count")
+        (n,) = struct.unpack("<Q", head)
+        data = f.read(n * rb)
+    if len(data) != n * rb:
+        raise ValueError(f"{path}: expected {n} compressed records of {rb} bytes, file is short")
+    from .msm import CODEC_STATUS_TEXT, decompress_points
+
+    res = decompress_points(data, curve=curve, uncompressed=True, validate=validate)
+    if not res.ok:
+        i = res.first_invalid
+        raise ValueError(f"{path}: record {i} is not a valid point (status {int(res.status[i])}: {CODEC_STATUS_TEXT[int(res.status[i])]}); "
+                         f"{n - res.counts['valid']} of {n} records are invalid")
+    return res.points, n
+
+
+def read_points_bin(path: str, curve="bls12_377_g1", validate: bool = False, compressed: bool = False) -> Tuple[bytes, int]:
+    """``points.bin`` -> (uncompressed records without the length prefix, count).  ``validate=True`` is arkworks' ``deserialize_uncompressed``
     beside the default ``deserialize_unchecked``: the records go through the GPU check (msm.check_points) and a ValueError names the
-    first record that has a non-canonical coordinate, is off the curve or lies outside the order-r subgroup."""
+    first record that has a non-canonical coordinate, is off the curve or lies outside the order-r subgroup.
+    ``compressed=True``: the file holds COMPRESSED records (arkworks' plain ``serialize``); they are decoded on the GPU
+    (msm.decompress_points) into the same uncompressed records, a record that does not decode raises ValueError, and with
+    ``validate=True`` the subgroup check runs after decoding (``deserialize`` beside ``deserialize_compressed_unchecked``)."""
+    if compressed:
+        return _read_compressed_points_bin(path, curve, validate)
     rb = record_bytes(curve)
     with open(path, "rb") as f:
         head = f.read(8)
@@ -56,12 +81,22 @@ def read_points_bin(path: str, curve="bls12_377_g1", validate: bool = False) -> 
     return data, n
 
 
-def write_points_bin(path: str, records: bytes, curve="bls12_377_g1") -> None:
+def write_points_bin(path: str, records: bytes, curve="bls12_377_g1", compressed: bool = False) -> None:
+    """Uncompressed records -> ``Vec<Affine>`` file.  ``compressed=True`` writes the COMPRESSED form of the same points (encoded on
+    the GPU, msm.compress_points); a record with a non-canonical coordinate raises ValueError."""
     rb = record_bytes(curve)
     if len(records) % rb:
         raise ValueError("records length is not a multiple of the record size")
+    n = len(records) // rb
+    if compressed:
+        from .msm import compress_points
+
+        res = compress_points(records, curve=curve, serialized=True)
+        if not res.ok:
+            raise ValueError(f"record {res.first_invalid} has a coordinate that is not below p")
+        records = res.points
     with open(path, "wb") as f:
-        f.write(struct.pack("<Q", len(records) // rb))
+        f.write(struct.pack("<Q", n))
         f.write(records)
 
 
@@ -149,14 +184,16 @@ def set_bases_serialized(ctx: MultiScalarMultContext, records: bytes) -> None:
     ctx.npoints = n
 
 
-def point_to_serialized(projective: bytes, curve="bls12_377_g1") -> bytes:
-    """A result (Projective image) as one uncompressed serialized affine record, comparable with arkworks_results.bin."""
+def point_to_serialized(projective: bytes, curve="bls12_377_g1", compressed: bool = False) -> bytes:
+    """A result (Projective image) as one uncompressed serialized affine record, comparable with arkworks_results.bin;
+    ``compressed``: as one compressed record (x and the two flag bits)."""
     lib = load_library()
     if len(projective) != projective_bytes(curve):
         raise ValueError("wrong projective image size")
-    out = ctypes.create_string_buffer(record_bytes(curve))
+    out = ctypes.create_string_buffer(record_bytes(curve, compressed))
     buf = ctypes.create_string_buffer(projective, len(projective))
-    _check(lib.mi355_msm_point_to_serialized(_curve_id(curve), buf, out))
+    fn = lib.mi355_msm_point_to_compressed if compressed else lib.mi355_msm_point_to_serialized
+    _check(fn(_curve_id(curve), buf, out))
     return out.raw
 
 

@@ -106,6 +106,12 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_plan": [ci, sz, ci, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_set_bases_serialized": [vp, vp, sz],
         "mi355_msm_point_to_serialized": [ci, vp, vp],
+        "mi355_msm_decompress_points": [vp, vp, sz, vp, sz, ctypes.c_uint, vp, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_decompress_points_device": [vp, vp, sz, vp, sz, ctypes.c_uint, vp, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_compress_points": [vp, vp, sz, sz, ctypes.c_uint, vp, vp, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_compress_points_device": [vp, vp, sz, sz, ctypes.c_uint, vp, vp, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_set_bases_compressed": [vp, vp, sz],
+        "mi355_msm_point_to_compressed": [ci, vp, vp],
         "mi355_msm_last_stateless": [ctypes.POINTER(ctypes.c_double), sz],
         "mi355_msm_stream_create": [ctypes.POINTER(vp), ci, ci, sz, ci],
         "mi355_msm_stream_set_option": [vp, ctypes.c_char_p, ctypes.c_long],
@@ -219,6 +225,39 @@ class CheckResult:
         return f"CheckResult(ok={self.ok}, counts={self.counts}, first_invalid={self.first_invalid}, method={self.method!r}, device_us={self.device_us})"
 
 
+CODEC_STATUS_TEXT = ("decoded", "malformed: x is not below p or both flag bits are set", "no point has this x",
+                     "outside the order-r subgroup")
+
+
+class CodecResult:
+    """What decompress_points / compress_points produced: `points` (decompress: Affine images or uncompressed records; compress: the
+    compressed records) in the kind of container the input came in, `status` one byte per record (decompress: 0 decoded or flagged
+    infinity, 1 malformed, 2 no point has this x, 3 outside the order-r subgroup when validation was asked for; compress: 1 = a
+    coordinate is not canonical), `counts`, `first_invalid` (None when every status is 0)."""
+
+    def __init__(self, points, ok, counts, first_invalid, status, method, device_us):
+        self.points, self.ok, self.counts, self.first_invalid, self.status = points, ok, counts, first_invalid, status
+        self.method, self.device_us = method, device_us
+
+    @property
+    def records(self):
+        return self.points
+
+    def __repr__(self):
+        return f"CodecResult(ok={self.ok}, counts={self.counts}, first_invalid={self.first_invalid}, device_us={self.device_us})"
+
+
+def _like_input(src, out_np, shape):
+    """A NumPy result in the container kind of `src`: torch CPU tensor, NumPy array or bytes."""
+    if hasattr(src, "data_ptr") and hasattr(src, "is_cuda"):
+        import torch
+
+        return torch.from_numpy(out_np.reshape(shape))
+    if hasattr(src, "__array_interface__"):
+        return out_np.reshape(shape)
+    return out_np.tobytes()
+
+
 class MultiScalarMultContext:
     """``#[repr(C)] struct MultiScalarMultContext { context: *mut c_void }`` (P1A 6block/src/lib.rs:18-21)."""
 
@@ -291,6 +330,93 @@ class MultiScalarMultContext:
         first = int(out[5])
         return CheckResult(ok=first == n, counts=counts, first_invalid=None if first == n else first, status=status,
                            method="endomorphism" if out[6] else "exact", device_us=int(out[7]))
+
+    def _codec_result(self, points, out, n, kind) -> "CodecResult":
+        counts = {"valid": int(out[0]), "flagged_infinity": int(out[1]), "malformed" if kind == "decode" else "not_canonical": int(out[2])}
+        if kind == "decode":
+            counts.update(no_point=int(out[3]), off_subgroup=int(out[4]))
+        first = int(out[5])
+        return CodecResult(points, first == n, counts, None if first == n else first, None,
+                           "endomorphism" if out[6] else "exact", int(out[7]))
+
+    def decompress_points(self, records, uncompressed: bool = False, validate: bool = False, exact: bool = False,
+                          stride: Optional[int] = None) -> "CodecResult":
+        """arkworks COMPRESSED records (x + two flag bits: 48 bytes per G1 point, 96 per G2 point) -> in-memory Affine images `stride`
+        bytes apart (default: the image size), or with `uncompressed` uncompressed CanonicalSerialize records, decoded on the
+        context's device (mi355_msm_decompress_points).  `validate`: also run the subgroup check of check_bases over the decoded
+        points (status 3; `exact`: by [r]P == O).  bytes, NumPy and torch CPU inputs give the same kind back; a torch GPU tensor is
+        read in place and gives a GPU tensor.  A record that fails decodes to zeros (see CodecResult.status)."""
+        import numpy as np
+
+        cid = self.curve
+        cb = projective_bytes(cid) // 3
+        rec = 2 * cb if uncompressed else (affine_stride(cid) if stride is None else int(stride))
+        if not uncompressed and (rec % 4 or rec < 2 * cb + 1):
+            raise ValueError(f"stride {rec} must be a multiple of 4 and at least {2 * cb + 1}")
+        b = _Buf(records)
+        if b.nbytes % cb:
+            raise ValueError(f"records of {b.nbytes} bytes are not a multiple of the {cb}-byte compressed record")
+        n = b.nbytes // cb
+        self._check_device(b, "records")
+        status = np.zeros(n, dtype=np.uint8)
+        out8 = (ctypes.c_uint64 * 8)()
+        flags = (1 if uncompressed else 0) | (2 if validate else 0) | (4 if exact else 0)
+        sp = status.ctypes.data_as(ctypes.c_void_p) if n else None
+        if b.is_device:
+            import torch
+
+            pts = torch.zeros((n, rec), dtype=torch.uint8, device=b.keep.device)
+            _check(self._lib.mi355_msm_decompress_points_device(self.context, b.ptr, n, pts.data_ptr() if n else None, rec, flags, sp, out8))
+        else:
+            o = np.zeros(n * rec, dtype=np.uint8)
+            _check(self._lib.mi355_msm_decompress_points(self.context, b.ptr, n, o.ctypes.data if n else None, rec, flags, sp, out8))
+            pts = _like_input(records, o, (n, rec))
+        res = self._codec_result(pts, out8, n, "decode")
+        res.status = status
+        return res
+
+    def compress_points(self, points, serialized: bool = False, stride: Optional[int] = None) -> "CodecResult":
+        """In-memory Affine images (`stride` bytes apart) or, with `serialized`, uncompressed records -> compressed records
+        (mi355_msm_compress_points): what arkworks' plain `serialize` writes.  Containers as in decompress_points.  Status 1: a
+        coordinate is not canonical (the record is then all zeros); there is no curve test, as in arkworks."""
+        import numpy as np
+
+        cid = self.curve
+        cb = projective_bytes(cid) // 3
+        rec = 2 * cb if serialized else (affine_stride(cid) if stride is None else int(stride))
+        b = _Buf(points)
+        if b.nbytes % rec:
+            raise ValueError(f"points image of {b.nbytes} bytes is not a multiple of the {rec}-byte record")
+        n = b.nbytes // rec
+        self._check_device(b, "points")
+        status = np.zeros(n, dtype=np.uint8)
+        out8 = (ctypes.c_uint64 * 8)()
+        sp = status.ctypes.data_as(ctypes.c_void_p) if n else None
+        if b.is_device:
+            import torch
+
+            recs = torch.zeros((n, cb), dtype=torch.uint8, device=b.keep.device)
+            _check(self._lib.mi355_msm_compress_points_device(self.context, b.ptr, n, rec, 1 if serialized else 0, recs.data_ptr() if n else None, sp, out8))
+        else:
+            o = np.zeros(n * cb, dtype=np.uint8)
+            _check(self._lib.mi355_msm_compress_points(self.context, b.ptr, n, rec, 1 if serialized else 0, o.ctypes.data if n else None, sp, out8))
+            recs = _like_input(points, o, (n, cb))
+        res = self._codec_result(recs, out8, n, "encode")
+        res.status = status
+        return res
+
+    def set_bases_compressed(self, records) -> None:
+        """Upload bases as compressed records in host memory (mi355_msm_set_bases_compressed): the square roots run on the GPU.  A
+        record that does not decode raises MsmError naming its index and status, and the previous bases stay in force."""
+        cb = projective_bytes(self.curve) // 3
+        b = _Buf(records)
+        if b.is_device:
+            raise TypeError("set_bases_compressed takes host records; decode a device tensor with decompress_points and pass the images to set_bases")
+        if b.nbytes % cb:
+            raise ValueError(f"records must be {cb}-byte compressed points")
+        n = b.nbytes // cb
+        _check(self._lib.mi355_msm_set_bases_compressed(self.context, b.ptr, n))
+        self.npoints = n
 
     def run(self, scalars, npoints: Optional[int] = None) -> List[bytes]:
         b = _Buf(scalars)
@@ -398,6 +524,30 @@ def check_points(points, curve="bls12_377_g1", stride: Optional[int] = None, ser
     ctx = MultiScalarMultContext(curve, device)
     try:
         return ctx.check_bases(points, stride=stride, serialized=serialized, exact=exact)
+    finally:
+        ctx.close()
+
+
+def decompress_points(records, curve="bls12_377_g1", uncompressed: bool = False, validate: bool = False, exact: bool = False,
+                      stride: Optional[int] = None, device: Optional[int] = None) -> CodecResult:
+    """MultiScalarMultContext.decompress_points on a throwaway context (on the tensor's device for a GPU tensor)."""
+    if device is None and getattr(records, "is_cuda", False):
+        device = records.device.index
+    ctx = MultiScalarMultContext(curve, device)
+    try:
+        return ctx.decompress_points(records, uncompressed=uncompressed, validate=validate, exact=exact, stride=stride)
+    finally:
+        ctx.close()
+
+
+def compress_points(points, curve="bls12_377_g1", serialized: bool = False, stride: Optional[int] = None,
+                    device: Optional[int] = None) -> CodecResult:
+    """MultiScalarMultContext.compress_points on a throwaway context (on the tensor's device for a GPU tensor)."""
+    if device is None and getattr(points, "is_cuda", False):
+        device = points.device.index
+    ctx = MultiScalarMultContext(curve, device)
+    try:
+        return ctx.compress_points(points, serialized=serialized, stride=stride)
     finally:
         ctx.close()
 

@@ -135,6 +135,48 @@ RustError mi355_msm_set_bases_serialized(mi355_msm_ctx* ctx, const void* records
  * comparable byte-for-byte with the harness's `arkworks_results.bin` entries. */
 RustError mi355_msm_point_to_serialized(int curve, const void* projective, void* out_record);
 
+/* arkworks COMPRESSED records -- what plain `serialize` / `deserialize` mean (ARK ec/src/models/short_weierstrass.rs:1120-1126,
+ * 1188-1201), the form SRS files and proving keys ship in: x as a little-endian normal-form integer (48 B for G1; c0 | c1, 96 B,
+ * for G2) with SWFlags in the top two bits of the last byte -- bit 6 infinity, bit 7 "y is the larger of y and -y" (Fp: the integer
+ * exceeds (p - 1)/2; Fp2: c1 decides unless it is zero, then c0).  Decoded and encoded on the context's device and stream, in chunks
+ * of option "codec_chunk" records (default 2^22) through buffers the context keeps; the context's bases are not touched.
+ *
+ * decompress: `records` -> `out`, npoints * stride bytes of arkworks in-memory Affine images (Montgomery R = 2^384, flag byte, every
+ * pad byte of the stride written as zero, infinity as (0, 0, flag 1)), or with flags bit 0 npoints uncompressed records (stride
+ * ignored; infinity as (0, 1) with bit 6, the record mi355_msm_point_to_serialized writes).  One status byte per record:
+ *   0  decoded, or flagged infinity (the flag is authoritative: a flagged record is valid whatever its x bits hold)
+ *   1  malformed: x (a component) is not below p after the flag bits are masked, or BOTH flag bits are set (arkworks refuses that
+ *      encoding, and so does this decoder -- unlike the check of uncompressed records above, which stays lenient)
+ *   2  no point has this x (x^3 + b has no square root)
+ *   3  decoded, but outside the order-r subgroup -- only with flags bit 1, which runs mi355_msm_check_bases' kernel over the decoded
+ *      records (flags bit 2: its exact method); a record that failed to decode keeps status 1 / 2
+ * The lowest applicable status wins.  A record that fails is written as an all-zero record with flag 0, which mi355_msm_check_bases
+ * reports as off the curve: never a silent infinity.
+ * status: HOST memory, npoints bytes, may be NULL.  out8: laid out like mi355_msm_check_bases' out -- valid, of those flagged infinity,
+ * status 1, 2, 3, index of the first failing record (npoints if none), method of the subgroup check (0 exact or none, 1 endomorphism),
+ * device microseconds of the codec kernels alone (no copies, no subgroup check).
+ * _device: `d_records` and `d_out` are device memory of the context's device, 4-byte aligned; nothing but the status bytes is staged.
+ *
+ * compress: images `stride` bytes apart, or with flags bit 0 uncompressed records, -> npoints compressed records.  Status 1 for a
+ * non-canonical coordinate (the record is then all zeros); no curve test -- arkworks' `serialize` has none.
+ *
+ * Both return 0 when the codec RAN, whatever it found; -1 for a sharded context, unknown flags, a stride too small or not a multiple of 4. */
+RustError mi355_msm_decompress_points(mi355_msm_ctx* ctx, const void* records, size_t npoints, void* out, size_t stride, unsigned flags,
+                                      uint8_t* status, uint64_t* out8);
+RustError mi355_msm_decompress_points_device(mi355_msm_ctx* ctx, const void* d_records, size_t npoints, void* d_out, size_t stride,
+                                             unsigned flags, uint8_t* status, uint64_t* out8);
+RustError mi355_msm_compress_points(mi355_msm_ctx* ctx, const void* points, size_t npoints, size_t stride, unsigned flags, void* out_records,
+                                    uint8_t* status, uint64_t* out8);
+RustError mi355_msm_compress_points_device(mi355_msm_ctx* ctx, const void* d_points, size_t npoints, size_t stride, unsigned flags,
+                                           void* d_out_records, uint8_t* status, uint64_t* out8);
+/* Bases as compressed records in host memory (WITHOUT a leading element count): decoded on the device, then handed to the path of
+ * mi355_msm_set_bases_device, so tables, the Edwards conversion, the anchored sum and option "validate_bases" behave as for any other
+ * input.  A record with a non-zero decode status fails the call with -1 and a message naming the first bad index and its status;
+ * the context keeps its previous bases.  A sharded context refuses the call (-1). */
+RustError mi355_msm_set_bases_compressed(mi355_msm_ctx* ctx, const void* records, size_t npoints);
+/* A Projective image (any Z) -> one compressed record (host arithmetic), beside mi355_msm_point_to_serialized. */
+RustError mi355_msm_point_to_compressed(int curve, const void* projective, void* out_record);
+
 /* `batches` MSMs over the SAME bases: scalars holds batches * npoints entries, out receives `batches`
  * projective images (P1A 6block/src/lib.rs:85-109: batch_size = scalars.len() / points.len()).
  * npoints may be smaller than the number of uploaded bases (prefix). */

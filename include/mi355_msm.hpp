@@ -84,6 +84,38 @@ inline CheckResult check_bases_device(MultiScalarMultContext& ctx, const void* d
   return r;
 }
 
+// arkworks compressed G1 records (48 bytes each, mi355_msm_decompress_points) -> Affine images; `r.status[i]`: 0 decoded, 1 malformed,
+// 2 no point has this x, 3 (validate) outside the order-r subgroup.  The counters of CheckResult read: not_canonical = status 1,
+// off_curve = status 2.
+inline CheckResult decompress_points(MultiScalarMultContext& ctx, const std::vector<uint8_t>& records, std::vector<G1Affine>& out, bool validate = false) {
+  CheckResult r;
+  uint64_t o[8] = {0};
+  const size_t n = records.size() / 48;
+  out.resize(n);
+  r.status.resize(n);
+  check(mi355_msm_decompress_points(ctx.context, records.data(), n, out.data(), sizeof(G1Affine), validate ? 2u : 0u, r.status.data(), o));
+  r.valid = o[0]; r.flagged_infinity = o[1]; r.not_canonical = o[2]; r.off_curve = o[3]; r.off_subgroup = o[4];
+  r.first_invalid = o[5]; r.method = o[6]; r.device_us = o[7];
+  r.ok = o[5] == n;
+  return r;
+}
+// Affine images -> compressed records (mi355_msm_compress_points); status 1: a coordinate is not canonical
+inline CheckResult compress_points(MultiScalarMultContext& ctx, const std::vector<G1Affine>& points, std::vector<uint8_t>& out_records) {
+  CheckResult r;
+  uint64_t o[8] = {0};
+  out_records.resize(points.size() * 48);
+  r.status.resize(points.size());
+  check(mi355_msm_compress_points(ctx.context, points.data(), points.size(), sizeof(G1Affine), 0u, out_records.data(), r.status.data(), o));
+  r.valid = o[0]; r.flagged_infinity = o[1]; r.not_canonical = o[2]; r.first_invalid = o[5]; r.device_us = o[7];
+  r.ok = o[5] == points.size();
+  return r;
+}
+// bases from compressed records in host memory (mi355_msm_set_bases_compressed)
+inline void set_bases_compressed(MultiScalarMultContext& ctx, const std::vector<uint8_t>& records) {
+  check(mi355_msm_set_bases_compressed(ctx.context, records.data(), records.size() / 48));
+  ctx.npoints = records.size() / 48;
+}
+
 inline MultiScalarMultContext multi_scalar_mult_init(const std::vector<G1Affine>& points, int curve = MI355_BLS12_377_G1) {
   MultiScalarMultContext ctx;
   check(mi355_msm_create(&ctx.context, curve, -1));

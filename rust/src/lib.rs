@@ -132,6 +132,21 @@ pub mod sys {
         pub fn mi355_msm(curve: c_int, out_projective: *mut c_void, affine: *const c_void, npoints: usize, scalars: *const c_void, ffi_affine_sz: usize) -> Error;
         pub fn mi355_msm_fold(curve: c_int, out_projective: *mut c_void, projective: *const c_void, count: usize) -> Error;
         pub fn mi355_msm_point_to_serialized(curve: c_int, projective: *const c_void, out_record: *mut c_void) -> Error;
+        /// arkworks compressed records (x + SWFlags; 48 B per G1 point, 96 B per G2 point) -> Affine images `stride` bytes apart, or
+        /// (flags bit 0) uncompressed records; flags bit 1: subgroup check of the decoded points, bit 2: its exact method.  One status
+        /// byte per record (0 decoded, 1 malformed, 2 no point has this x, 3 outside the subgroup); `out8` as mi355_msm_check_bases.
+        pub fn mi355_msm_decompress_points(ctx: *mut c_void, records: *const c_void, npoints: usize, out: *mut c_void, stride: usize,
+                                           flags: c_uint, status: *mut u8, out8: *mut u64) -> Error;
+        pub fn mi355_msm_decompress_points_device(ctx: *mut c_void, d_records: *const c_void, npoints: usize, d_out: *mut c_void, stride: usize,
+                                                  flags: c_uint, status: *mut u8, out8: *mut u64) -> Error;
+        /// Affine images or (flags bit 0) uncompressed records -> compressed records; status 1: a coordinate is not canonical.
+        pub fn mi355_msm_compress_points(ctx: *mut c_void, points: *const c_void, npoints: usize, stride: usize, flags: c_uint,
+                                         out_records: *mut c_void, status: *mut u8, out8: *mut u64) -> Error;
+        pub fn mi355_msm_compress_points_device(ctx: *mut c_void, d_points: *const c_void, npoints: usize, stride: usize, flags: c_uint,
+                                                d_out_records: *mut c_void, status: *mut u8, out8: *mut u64) -> Error;
+        /// Bases from compressed records in host memory: decoded on the device; a record that does not decode fails the call.
+        pub fn mi355_msm_set_bases_compressed(ctx: *mut c_void, records: *const c_void, npoints: usize) -> Error;
+        pub fn mi355_msm_point_to_compressed(curve: c_int, projective: *const c_void, out_record: *mut c_void) -> Error;
         pub fn mi355_msm_shard_timings(ctx: *mut c_void, shard: c_int, ms: *mut f32, info: *mut u64) -> Error;
         pub fn mi355_msm_last_stateless(out: *mut f64, count: usize) -> Error;
         pub fn mi355_msm_trim() -> Error;
