@@ -31,6 +31,9 @@ from .msm import (  # noqa: F401
     FixedBase,
     WindowTable,
     fixed_base_msm,
+    mul_points,
+    mul_points_by,
+    mul_by_cofactor,
 )
 from .dist import all_gather_partials, shard_bounds, sharded_msm  # noqa: F401,E402
 from . import formats  # noqa: F401,E402

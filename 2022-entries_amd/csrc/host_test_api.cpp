@@ -854,3 +854,143 @@ int ht_compress_points(int curve, int serialized, const uint8_t* in, size_t stri
 }
 
 }  // extern "C"
+
+// ---- batch variable-base multiplication (point_mul.hpp) with the limb-bound checker armed ---------------------------------------
+// The SAME MSM_HD functions the kernels of kernels_pmul.hip wrap: signed digits, the per-point table, the windowed walk, the
+// non-adjacent form and the one-scalar walk; records by fb_host_records (the restatement of k_pre_normalize above), output by
+// fb_normalize_run.  The walk starts at the scalar's own top window (the device takes the maximum over a wave).
+#include "point_mul.hpp"
+
+template <class E, class Dev>
+static void pm_host_output(const std::vector<Dev>& res, unsigned flags, uint8_t* out, size_t out_stride, const typename E::Md& md) {
+  const size_t n = res.size();
+  std::vector<typename E::T> prefix(n);
+  for (size_t lo = 0; lo < n; lo += FB_NORM_RUN) {
+    const size_t hi = lo + FB_NORM_RUN < n ? lo + FB_NORM_RUN : n;
+    if (flags & 2)
+      fb_normalize_run<E, true>(res.data(), lo, hi, prefix.data(), out, out_stride, md);
+    else
+      fb_normalize_run<E, false>(res.data(), lo, hi, prefix.data(), out, out_stride, md);
+  }
+}
+
+// 1P .. 2^(w-1) P of one point as arkworks Affine images
+template <class C>
+static int t_pm_table(const uint8_t* img, int w, uint8_t* out, size_t stride) {
+  using E = typename C::E;
+  using El = typename E::T;
+  typename E::Md md;
+  const uint32_t entries = pm_table_entries((uint32_t)w);
+  uint32_t rec[2 * E::WORDS];
+  memcpy(rec, img, 8 * E::WORDS);
+  std::vector<XyzzT<El>> x(entries);
+  pm_table<E>(x.data(), 1, rec, img[8 * E::WORDS], entries, md);
+  std::vector<XyzzDevT<El>> dev(entries);
+  for (uint32_t e = 0; e < entries; e++) dev[e].p = x[e];
+  pm_host_output<E>(dev, 0, out, stride, md);
+  return 0;
+}
+
+template <class C>
+static int t_pm_mul(const uint8_t* points, size_t stride, size_t n, const uint8_t* scalars, int w, unsigned flags, uint8_t* out, size_t out_stride) {
+  using E = typename C::E;
+  using El = typename E::T;
+  typename E::Md md;
+  const uint32_t entries = pm_table_entries((uint32_t)w);
+  std::vector<XyzzDevT<El>> res(n);
+  std::vector<XyzzT<El>> x(entries);
+  std::vector<AffineDevT<El>> table(entries);
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t* img = points + i * stride;
+    uint32_t rec[2 * E::WORDS], s[8];
+    memcpy(rec, img, 8 * E::WORDS);
+    pm_table<E>(x.data(), 1, rec, img[8 * E::WORDS], entries, md);
+    fb_host_records<E>(table.data(), x.data(), entries, md);
+    memcpy(s, scalars + 32 * i, 32);
+    if (flags & 1) fr_from_montgomery<typename CheckConsts<E>::FR>(s);
+    pm_windowed_mul<E>(res[i].p, table.data(), 1, s, (uint32_t)w, pm_top_window(pm_bit_length(s), (uint32_t)w), md);
+  }
+  pm_host_output<E>(res, flags, out, out_stride, md);
+  return 0;
+}
+
+template <class C>
+static int t_pm_mul_uniform(const uint8_t* points, size_t stride, size_t n, const PmNaf* naf, unsigned flags, uint8_t* out, size_t out_stride) {
+  using E = typename C::E;
+  using El = typename E::T;
+  typename E::Md md;
+  std::vector<XyzzDevT<El>> res(n);
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t* img = points + i * stride;
+    uint32_t rec[2 * E::WORDS];
+    memcpy(rec, img, 8 * E::WORDS);
+    pm_mul_uniform<E>(res[i].p, rec, img[8 * E::WORDS], *naf, md);
+  }
+  pm_host_output<E>(res, flags, out, out_stride, md);
+  return 0;
+}
+
+#include "cofactor_consts.inc"
+
+extern "C" {
+// the signed digits of one 32-byte scalar for window size w: pm_digits(w) values
+int ht_pm_digits(const uint8_t* scalar, int w, int32_t* out) {
+  if (!scalar || !out || w < 1 || w > (int)PM_MAX_WINDOW) return -1;
+  uint32_t s[8];
+  memcpy(s, scalar, 32);
+  const uint32_t nd = pm_digits((uint32_t)w);
+  for (uint32_t j = 0; j < nd; j++) out[j] = pm_digit(s, j, (uint32_t)w);
+  return (int)nd;
+}
+// the highest window the walk starts at for this scalar
+int ht_pm_top_window(const uint8_t* scalar, int w) {
+  if (!scalar || w < 1 || w > (int)PM_MAX_WINDOW) return -1;
+  uint32_t s[8];
+  memcpy(s, scalar, 32);
+  return (int)pm_top_window(pm_bit_length(s), (uint32_t)w);
+}
+// the non-adjacent form of a little-endian integer of nbytes bytes (a multiple of 4, at most 64): 544 digits in {-1, 0, 1};
+// returns the index of the top non-zero digit, -1 for zero, -2 for bad arguments
+int ht_pm_naf(const uint8_t* k, size_t nbytes, int8_t* out) {
+  if (!k || !out || nbytes % 4 || nbytes < 4 || nbytes > 64) return -2;
+  uint32_t w[16] = {0};
+  memcpy(w, k, nbytes);
+  PmNaf naf;
+  pm_naf_recode(naf, w, 16);
+  for (uint32_t i = 0; i < 32 * PM_NAF_WORDS; i++) {
+    const int nz = (naf.nz[i >> 5] >> (i & 31)) & 1, ng = (naf.neg[i >> 5] >> (i & 31)) & 1;
+    out[i] = (int8_t)(nz ? (ng ? -1 : 1) : 0);
+  }
+  return naf.top;
+}
+// the cofactor of curve 0..3 as 64 little-endian bytes
+int ht_pm_cofactor(int curve, uint8_t* out) {
+  if (curve < 0 || curve > 3 || !out) return -1;
+  memcpy(out, kCofactorWords[curve], 64);
+  return (int)kCofactorBits[curve];
+}
+int ht_pm_table(int curve, const uint8_t* img, int w, uint8_t* out, size_t stride) {
+  if (!img || !out || w < 1 || w > (int)PM_MAX_WINDOW || stride % 4) return -1;
+  DISPATCH_C(curve, t_pm_table, img, w, out, stride)
+}
+// flags as mi355_msm_mul_points: bit 0 Fr Montgomery scalars, bit 1 Projective images
+int ht_pm_mul(int curve, const uint8_t* points, size_t stride, size_t n, const uint8_t* scalars, int w, unsigned flags, uint8_t* out, size_t out_stride) {
+  if ((n && (!points || !scalars || !out)) || w < 1 || w > (int)PM_MAX_WINDOW || out_stride % 4 || (flags & ~3u)) return -1;
+  DISPATCH_C(curve, t_pm_mul, points, stride, n, scalars, w, flags, out, out_stride)
+}
+// one scalar for all points: k as in ht_pm_naf; flags bit 1 Projective images, bit 3 the curve's cofactor (k is then ignored)
+int ht_pm_mul_uniform(int curve, const uint8_t* points, size_t stride, size_t n, const uint8_t* k, size_t nbytes, unsigned flags, uint8_t* out,
+                      size_t out_stride) {
+  if ((n && (!points || !out)) || out_stride % 4 || (flags & ~10u) || curve < 0 || curve > 3) return -1;
+  uint32_t w[16] = {0};
+  if (flags & 8) {
+    memcpy(w, kCofactorWords[curve], 64);
+  } else {
+    if (!k || nbytes % 4 || nbytes < 4 || nbytes > 64) return -1;
+    memcpy(w, k, nbytes);
+  }
+  PmNaf naf;
+  pm_naf_recode(naf, w, 16);
+  DISPATCH_C(curve, t_pm_mul_uniform, points, stride, n, &naf, flags, out, out_stride)
+}
+}

@@ -378,6 +378,11 @@ struct mi355_msm_ctx {
   bool bases_validated = false;   // the current base set passed that check
   long opt_codec_chunk = 0;      // records per launch of the point codec (msm_codec.hpp); 0 = the default, 2^22
   DevBuf codec_in, codec_out, codec_stat[2];   // one chunk of compressed records / of images or uncompressed records / of status bytes
+  long opt_mul_chunk = 0, opt_mul_window = 0;   // points per chunk / window bits of mul_points (msm_pmul.hpp); 0 = the defaults
+  DevBuf pm_stage, pm_rec, pm_prefix, pm_inf;   // one chunk of mul_points: table entries in XYZZ (then the results), their records, scratch, flags
+  DevBuf pm_points, pm_scalars, pm_out;         // host-pointer calls: one chunk of staged points / scalars / packed output images
+  hipEvent_t pm_ev[2] = {nullptr, nullptr};     // around the device work of a call, on the stream it runs on
+  uint64_t last_mul_us = 0, last_mul_device_us = 0;
   long opt_assume_subgroup = 0;   // 1: every base is in the order-r subgroup (r P = O), so a scalar k in (r/2, r) may run as (r - k)(-P)
   long opt_anchor = 1;            // option "anchor_window": 1 = end the signed-digit carry chain at the last full window where that saves additions
   bool anchor_armed = false;      // ... for the run under way: the sum of its bases is at hand (run_device_t)
@@ -561,6 +566,10 @@ struct mi355_msm_ctx {
 namespace {
 
 void ensure_device(mi355_msm_ctx* ctx) { HIP_OK(hipSetDevice(ctx->device)); }
+
+// what mul_points runs with (msm_pmul.hpp): the window bits and the points per chunk the options come to
+uint32_t pmul_window(const mi355_msm_ctx* ctx);
+size_t pmul_chunk(const mi355_msm_ctx* ctx);
 
 // Every compute entry point starts here: no device, no service (this library has no CPU fallback).  Returns the device count.
 int require_device() {
@@ -2072,8 +2081,11 @@ RustError mi355_msm_destroy(mi355_msm_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->own_stream);
     DevBuf* bufs[] = {&ctx->bases, &ctx->inf, &ctx->scalars, &ctx->te_bases, &ctx->flags, &ctx->stateless_raw[0], &ctx->stateless_raw[1], &ctx->stateless_raw[2],
-                      &ctx->codec_in, &ctx->codec_out, &ctx->codec_stat[0], &ctx->codec_stat[1]};
+                      &ctx->codec_in, &ctx->codec_out, &ctx->codec_stat[0], &ctx->codec_stat[1],
+                      &ctx->pm_stage, &ctx->pm_rec, &ctx->pm_prefix, &ctx->pm_inf, &ctx->pm_points, &ctx->pm_scalars, &ctx->pm_out};
     for (DevBuf* b : bufs) b->release();
+    for (auto& ev : ctx->pm_ev)
+      if (ev) (void)hipEventDestroy(ev);
     release_work_buffers(ctx);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
@@ -2339,6 +2351,14 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value) 
       // records per launch of decompress_points / compress_points / set_bases_compressed (0 = the default, 2^22): a test puts seams at small n
       if (value < 0 || value >= (1l << 31)) bad_arg("codec_chunk %ld out of range [0, 2^31)", value);
       ctx->opt_codec_chunk = value;
+    } else if (k == "mul_chunk") {
+      // points per chunk of mul_points (0 = the default: msm_pmul.hpp); results do not depend on it: a test puts seams at small n
+      if (value < 0 || value >= (1l << 31)) bad_arg("mul_chunk %ld out of range [0, 2^31)", value);
+      ctx->opt_mul_chunk = value;
+    } else if (k == "mul_window") {
+      // window bits of pairwise mul_points (0 = the default, 4); results do not depend on it: a test hook
+      if (value < 0 || value > 6) bad_arg("mul_window %ld out of range [1, 6] (0 = the default)", value);
+      ctx->opt_mul_window = value;
     } else if (k == "assume_subgroup") {
       ctx->opt_assume_subgroup = value != 0;
     } else if (k == "carry") {
@@ -2485,6 +2505,16 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
       *value = ctx->opt_validate_bases ? 1 : 0;
     else if (k == "codec_chunk")
       *value = ctx->opt_codec_chunk > 0 ? (uint64_t)ctx->opt_codec_chunk : (uint64_t)1 << 22;
+    else if (k == "mul_window")
+      *value = pmul_window(ctx);
+    else if (k == "mul_chunk")
+      *value = pmul_chunk(ctx);
+    else if (k == "mul_work_bytes")
+      *value = ctx->pm_stage.bytes + ctx->pm_rec.bytes + ctx->pm_prefix.bytes + ctx->pm_inf.bytes + ctx->pm_points.bytes + ctx->pm_scalars.bytes + ctx->pm_out.bytes;
+    else if (k == "last_mul_us")
+      *value = ctx->last_mul_us;
+    else if (k == "last_mul_device_us")
+      *value = ctx->last_mul_device_us;
     else if (k == "bases_validated")
       *value = ctx->bases_validated ? 1 : 0;
     else if (k == "carry")
@@ -2726,3 +2756,4 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 #include "msm_stream.hpp"
 #include "msm_fixed.hpp"
 #include "msm_codec.hpp"
+#include "msm_pmul.hpp"

@@ -112,6 +112,8 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_compress_points_device": [vp, vp, sz, sz, ctypes.c_uint, vp, vp, ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_set_bases_compressed": [vp, vp, sz],
         "mi355_msm_point_to_compressed": [ci, vp, vp],
+        "mi355_msm_mul_points": [vp, vp, sz, sz, vp, sz, ctypes.c_uint, vp, sz],
+        "mi355_msm_mul_points_device": [vp, vp, sz, sz, vp, sz, ctypes.c_uint, vp, sz, vp],
         "mi355_msm_last_stateless": [ctypes.POINTER(ctypes.c_double), sz],
         "mi355_msm_stream_create": [ctypes.POINTER(vp), ci, ci, sz, ci],
         "mi355_msm_stream_set_option": [vp, ctypes.c_char_p, ctypes.c_long],
@@ -418,6 +420,74 @@ class MultiScalarMultContext:
         _check(self._lib.mi355_msm_set_bases_compressed(self.context, b.ptr, n))
         self.npoints = n
 
+    def _mul_points(self, points, scalars, scalar_bytes, flags, stride, out_stride):
+        """mi355_msm_mul_points[_device]: `scalars` is a _Buf of pairwise scalars, or the bytes of one scalar (flag bit 2), or None."""
+        import numpy as np
+
+        cid = self.curve
+        size = projective_bytes(cid) if flags & 2 else affine_stride(cid)
+        stride = affine_stride(cid) if stride is None else int(stride)
+        out_stride = size if out_stride is None else int(out_stride)
+        if stride % 4 or stride < 2 * (projective_bytes(cid) // 3) + 1:
+            raise ValueError(f"stride {stride} must be a multiple of 4 and hold two coordinates and the flag byte")
+        if out_stride % 4 or out_stride < size:
+            raise ValueError(f"out_stride {out_stride} must be a multiple of 4 and at least the {size}-byte image")
+        b = _Buf(points)
+        if b.nbytes % stride:
+            raise ValueError(f"points image of {b.nbytes} bytes is not a multiple of the {stride}-byte stride")
+        n = b.nbytes // stride
+        self._check_device(b, "points")
+        pairwise = isinstance(scalars, _Buf)
+        if pairwise:
+            if scalars.nbytes != n * SCALAR_BYTES:
+                raise ValueError(f"{n} points need {n * SCALAR_BYTES} bytes of scalars, not {scalars.nbytes}")
+            if scalars.is_device != b.is_device:
+                raise TypeError("points and scalars must both be host data or both be GPU tensors")
+            self._check_device(scalars, "scalars")
+            sptr = scalars.ptr
+        elif scalars is None:
+            sptr = None
+        else:
+            keep = (ctypes.c_char * len(scalars)).from_buffer_copy(scalars)
+            sptr = ctypes.addressof(keep)
+        if b.is_device:
+            import torch
+
+            out = torch.zeros((n, out_stride), dtype=torch.uint8, device=b.keep.device)
+            if n:
+                _check(self._lib.mi355_msm_mul_points_device(self.context, b.ptr, n, stride, sptr, scalar_bytes, flags, out.data_ptr(), out_stride, b.stream))
+            return out
+        o = np.zeros(n * out_stride, dtype=np.uint8)
+        if n:
+            _check(self._lib.mi355_msm_mul_points(self.context, b.ptr, n, stride, sptr, scalar_bytes, flags, o.ctypes.data, out_stride))
+        return _like_input(points, o, (n, out_stride))
+
+    def mul_points(self, points, scalars, montgomery: bool = False, projective: bool = False, stride: Optional[int] = None,
+                   out_stride: Optional[int] = None):
+        """``out[i] = scalars[i] * points[i]`` on the context's device (mi355_msm_mul_points): arkworks' ``mul_bigint`` over a vector,
+        then ``batch_normalization_into_affine``.  ``points``: Affine images ``stride`` bytes apart, ANY curve points (no curve or
+        subgroup test; the flag byte is authoritative).  ``scalars``: 32-byte little-endian integers, all 256 bits significant (the
+        integer multiple, never reduced mod r); ``montgomery``: arkworks ``Fr`` images.  Affine images out (``projective``: normalised
+        Projective images), ``out_stride`` bytes apart.  bytes / NumPy / torch CPU in give the same kind out; GPU tensors (points and
+        scalars) are read in place on the current torch stream and give a GPU tensor, ready for ``set_bases``."""
+        return self._mul_points(points, _Buf(scalars), SCALAR_BYTES, (1 if montgomery else 0) | (2 if projective else 0), stride, out_stride)
+
+    def mul_points_by(self, points, k, projective: bool = False, stride: Optional[int] = None, out_stride: Optional[int] = None):
+        """``out[i] = k * points[i]`` for ONE integer k of up to 512 bits (an int, or little-endian bytes whose length is a multiple of 4
+        from 4 to 64): no table, one doubling per bit and one addition per non-zero digit of k's non-adjacent form."""
+        if isinstance(k, int):
+            if k < 0 or k >> 512:
+                raise ValueError("k must be an integer in [0, 2^512)")
+            k = k.to_bytes(max(4, (k.bit_length() + 31) // 32 * 4), "little")
+        k = bytes(k)
+        if len(k) % 4 or not 4 <= len(k) <= 64:
+            raise ValueError("k as bytes is a multiple of 4 from 4 to 64 bytes long")
+        return self._mul_points(points, k, len(k), 4 | (2 if projective else 0), stride, out_stride)
+
+    def mul_by_cofactor(self, points, projective: bool = False, stride: Optional[int] = None, out_stride: Optional[int] = None):
+        """``out[i] = COFACTOR * points[i]``: arkworks' ``mul_by_cofactor`` (NOT ``clear_cofactor``, which for BLS12-381 is another map)."""
+        return self._mul_points(points, None, 0, 8 | (2 if projective else 0), stride, out_stride)
+
     def run(self, scalars, npoints: Optional[int] = None) -> List[bytes]:
         b = _Buf(scalars)
         self._check_device(b, "scalars")
@@ -550,6 +620,35 @@ def compress_points(points, curve="bls12_377_g1", serialized: bool = False, stri
         return ctx.compress_points(points, serialized=serialized, stride=stride)
     finally:
         ctx.close()
+
+
+def _throwaway(points, curve, device, call):
+    if device is None and getattr(points, "is_cuda", False):
+        device = points.device.index
+    ctx = MultiScalarMultContext(curve, device)
+    try:
+        return call(ctx)
+    finally:
+        ctx.close()
+
+
+def mul_points(points, scalars, curve="bls12_377_g1", montgomery: bool = False, projective: bool = False, stride: Optional[int] = None,
+               out_stride: Optional[int] = None, device: Optional[int] = None):
+    """MultiScalarMultContext.mul_points on a throwaway context (on the tensor's device for a GPU tensor)."""
+    return _throwaway(points, curve, device, lambda c: c.mul_points(points, scalars, montgomery=montgomery, projective=projective, stride=stride,
+                                                                   out_stride=out_stride))
+
+
+def mul_points_by(points, k, curve="bls12_377_g1", projective: bool = False, stride: Optional[int] = None, out_stride: Optional[int] = None,
+                  device: Optional[int] = None):
+    """MultiScalarMultContext.mul_points_by on a throwaway context."""
+    return _throwaway(points, curve, device, lambda c: c.mul_points_by(points, k, projective=projective, stride=stride, out_stride=out_stride))
+
+
+def mul_by_cofactor(points, curve="bls12_377_g1", projective: bool = False, stride: Optional[int] = None, out_stride: Optional[int] = None,
+                    device: Optional[int] = None):
+    """MultiScalarMultContext.mul_by_cofactor on a throwaway context."""
+    return _throwaway(points, curve, device, lambda c: c.mul_by_cofactor(points, projective=projective, stride=stride, out_stride=out_stride))
 
 
 def multi_scalar_mult(ctx: MultiScalarMultContext, points, scalars) -> List[bytes]:

@@ -384,6 +384,45 @@ RustError mi355_msm_fixed_set_option(mi355_msm_fixed* fb, const char* key, long 
 RustError mi355_msm_fixed_query(mi355_msm_fixed* fb, const char* key, uint64_t* value);
 RustError mi355_msm_fixed_destroy(mi355_msm_fixed* fb);
 
+/* ---- batch variable-base scalar multiplication (ARK ec/src/lib.rs:188,294,305-319, models/short_weierstrass.rs:413-422) ----------
+ * out[i] = s_i * P_i: AffineRepr::mul_bigint / mul_by_cofactor over a whole vector, followed by batch_normalization_into_affine --
+ * what a ceremony contribution runs over the previous transcript, and the second half of drawing random subgroup points (solve for y,
+ * then multiply by the cofactor).  The calls sit on a single-device context (a sharded one refuses them with -1).
+ *   points   arkworks Affine images, `stride` bytes apart (a multiple of 4, at least 2 coordinates + the flag byte), read exactly as
+ *            mi355_msm_set_bases reads them.  The flag byte is authoritative (a flagged infinity may carry junk coordinates).  The
+ *            point may be off the subgroup or of small order: there is no curve test and no subgroup test, as mul_bigint has none.  A
+ *            record that is on no curve gives an unspecified result; the call still finishes without a fault.
+ *   scalars  default (pairwise): npoints x 32 B little-endian integers, scalar_bytes = 32.  ALL 256 bits count -- the result is the
+ *            integer multiple, never reduced modulo r (the fixed-base contract, for the same reason).  Flag bit 0: the 32 B are
+ *            arkworks Fr images (a * 2^256 mod r) and are converted first; defined for any 256-bit image.
+ *            Flag bit 2, one scalar for all points: `scalars` is a HOST pointer (also in the _device call) to ONE little-endian
+ *            integer of scalar_bytes bytes, a multiple of 4 from 4 to 64 (the G2 cofactors are 502 and 507 bits long).  Bit 0 is
+ *            refused together with bit 2.
+ *            Flag bit 3 (implies bit 2): the scalar is the curve's COFACTOR -- arkworks' mul_by_cofactor; `scalars` must be NULL and
+ *            scalar_bytes 0.  This is NOT clear_cofactor, which for BLS12-381 is a different map with a different result.
+ *   out      one image per point, in input order, out_stride bytes apart (a multiple of 4, at least the image size; bytes between two
+ *            images are not written).  Default: arkworks Affine images -- x, y canonical, every flag and pad byte written, infinity all
+ *            zeros with flag 1.  Flag bit 1: normalised Projective images, byte for byte what mi355_msm_run writes for the one-pair
+ *            MSM (P_i, s_i).  `out` must NOT overlap `points`.
+ * Pairwise: per point a table 1P .. 2^(w-1) P, normalised, then ceil(257 / w) signed w-bit digits from the top (w doublings and one
+ * mixed addition each), starting at the highest window that is non-zero in any of the 64 points of a wave.  One scalar: its
+ * non-adjacent form, one doubling per digit and one mixed addition per non-zero digit, no table.
+ * Results never depend on chunking, on the window size, or on host versus device pointers.  npoints = 0 succeeds and writes nothing.
+ * Work memory does not grow with npoints: calls run in chunks through buffers the context keeps until it is destroyed.  Options
+ * (mi355_msm_set_option): "mul_chunk", points per chunk (0 restores the default: the largest power of two whose work buffers stay
+ * within 2 GiB -- 2^19 for G1, 2^18 for G2; a wider window lowers it), "mul_window" 1..6 (0 restores the default, 4; a test hook).
+ * Queries: "mul_window", "mul_chunk", "mul_work_bytes" (chunk buffers held), "last_mul_us" (host clock around the most recent call),
+ * "last_mul_device_us" (the same call between events on the stream it ran on).
+ * mi355_msm_mul_points takes HOST pointers; mi355_msm_mul_points_device DEVICE pointers (4-byte aligned) for points, pairwise scalars
+ * and out, and the hipStream_t on which they become ready (NULL = the default stream): its work is enqueued there and the call returns
+ * when the output is written.
+ * Errors: -1 with a message for null pointers, a stride too small or not a multiple of 4, a scalar_bytes value the mode does not allow,
+ * unknown or contradictory flag bits -- decided before any device call; hipErrorNoDevice without a GPU. */
+RustError mi355_msm_mul_points(mi355_msm_ctx* ctx, const void* points, size_t npoints, size_t stride, const void* scalars, size_t scalar_bytes,
+                               unsigned flags, void* out, size_t out_stride);
+RustError mi355_msm_mul_points_device(mi355_msm_ctx* ctx, const void* d_points, size_t npoints, size_t stride, const void* scalars,
+                                      size_t scalar_bytes, unsigned flags, void* d_out, size_t out_stride, void* stream);
+
 /* Sum `count` projective images (any Z) into one normalised image: the multi-GPU combine step
  * ("final 8-point curve add").  Pure host arithmetic on <= a few dozen points; no device needed. */
 RustError mi355_msm_fold(int curve, void* out_projective, const void* projective, size_t count);

@@ -110,6 +110,28 @@ inline CheckResult compress_points(MultiScalarMultContext& ctx, const std::vecto
   r.ok = o[5] == points.size();
   return r;
 }
+// out[i] = scalars[i] * points[i] (mi355_msm_mul_points): 32-byte little-endian integers, all 256 bits significant; `montgomery`: arkworks
+// Fr images.  Any curve points: no curve test, no subgroup test.  Affine images out.
+inline std::vector<G1Affine> mul_points(MultiScalarMultContext& ctx, const std::vector<G1Affine>& points, const std::vector<uint8_t>& scalars,
+                                        bool montgomery = false) {
+  if (scalars.size() != 32 * points.size()) throw std::runtime_error("mul_points: one 32-byte scalar per point");
+  std::vector<G1Affine> out(points.size());
+  check(mi355_msm_mul_points(ctx.context, points.data(), points.size(), sizeof(G1Affine), scalars.data(), 32, montgomery ? 1u : 0u, out.data(),
+                             sizeof(G1Affine)));
+  return out;
+}
+// out[i] = k * points[i] for ONE little-endian integer k of 4 .. 64 bytes (a multiple of 4)
+inline std::vector<G1Affine> mul_points_by(MultiScalarMultContext& ctx, const std::vector<G1Affine>& points, const std::vector<uint8_t>& k) {
+  std::vector<G1Affine> out(points.size());
+  check(mi355_msm_mul_points(ctx.context, points.data(), points.size(), sizeof(G1Affine), k.data(), k.size(), 4u, out.data(), sizeof(G1Affine)));
+  return out;
+}
+// arkworks' mul_by_cofactor over a vector (not clear_cofactor)
+inline std::vector<G1Affine> mul_by_cofactor(MultiScalarMultContext& ctx, const std::vector<G1Affine>& points) {
+  std::vector<G1Affine> out(points.size());
+  check(mi355_msm_mul_points(ctx.context, points.data(), points.size(), sizeof(G1Affine), nullptr, 0, 8u, out.data(), sizeof(G1Affine)));
+  return out;
+}
 // bases from compressed records in host memory (mi355_msm_set_bases_compressed)
 inline void set_bases_compressed(MultiScalarMultContext& ctx, const std::vector<uint8_t>& records) {
   check(mi355_msm_set_bases_compressed(ctx.context, records.data(), records.size() / 48));

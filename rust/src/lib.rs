@@ -147,6 +147,13 @@ pub mod sys {
         /// Bases from compressed records in host memory: decoded on the device; a record that does not decode fails the call.
         pub fn mi355_msm_set_bases_compressed(ctx: *mut c_void, records: *const c_void, npoints: usize) -> Error;
         pub fn mi355_msm_point_to_compressed(curve: c_int, projective: *const c_void, out_record: *mut c_void) -> Error;
+        /// out[i] = s_i * P_i over Affine images `stride` bytes apart (mul_bigint over a vector, then batch normalisation): pairwise
+        /// 32-byte scalars (flags bit 0: Fr images), or ONE host scalar of `scalar_bytes` bytes for all points (bit 2), or the curve's
+        /// cofactor (bit 3, `scalars` null, `scalar_bytes` 0); bit 1: normalised Projective images out.  `out` must not overlap `points`.
+        pub fn mi355_msm_mul_points(ctx: *mut c_void, points: *const c_void, npoints: usize, stride: usize, scalars: *const c_void,
+                                    scalar_bytes: usize, flags: c_uint, out: *mut c_void, out_stride: usize) -> Error;
+        pub fn mi355_msm_mul_points_device(ctx: *mut c_void, d_points: *const c_void, npoints: usize, stride: usize, scalars: *const c_void,
+                                           scalar_bytes: usize, flags: c_uint, d_out: *mut c_void, out_stride: usize, stream: *mut c_void) -> Error;
         pub fn mi355_msm_shard_timings(ctx: *mut c_void, shard: c_int, ms: *mut f32, info: *mut u64) -> Error;
         pub fn mi355_msm_last_stateless(out: *mut f64, count: usize) -> Error;
         pub fn mi355_msm_trim() -> Error;
