@@ -34,6 +34,7 @@ from .msm import (  # noqa: F401
     mul_points,
     mul_points_by,
     mul_by_cofactor,
+    Radix2EvaluationDomain,
 )
 from .dist import all_gather_partials, shard_bounds, sharded_msm  # noqa: F401,E402
 from . import formats  # noqa: F401,E402

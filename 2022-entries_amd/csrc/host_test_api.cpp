@@ -994,3 +994,149 @@ int ht_pm_mul_uniform(int curve, const uint8_t* points, size_t stride, size_t n,
   DISPATCH_C(curve, t_pm_mul_uniform, points, stride, n, &naf, flags, out, out_stride)
 }
 }
+
+// ---- scalar fields and radix-2 domains (fr.hpp, ntt.hpp): the kernels' per-element functions, a block's loops run in order ------
+#include <vector>
+#include "ntt.hpp"
+
+template <class FR>
+static void t_fr_table(std::vector<Fr>& out, const Fr& base, uint32_t n) {
+  out.resize(n);
+  for (uint32_t i = 0; i < n; i++) ntt_table_entry<FR>(out[i], base, i);
+}
+
+template <class FR>
+static void t_ntt_two_level(std::vector<Fr>& lo, std::vector<Fr>& hi, const Fr& base, uint32_t k) {
+  const uint32_t h = ntt_lo_log(k);
+  Fr hb;
+  ntt_hi_base<FR>(hb, base, h);
+  t_fr_table<FR>(lo, base, 1u << h);
+  t_fr_table<FR>(hi, hb, 1u << (k - h));
+}
+
+template <class FR>
+static int t_ntt_transform(uint32_t k, uint32_t pass_log, unsigned kind, unsigned flags, const uint8_t* offset, const uint8_t* in, uint32_t in_len,
+                           uint32_t batch, uint8_t* out) {
+  const size_t n = (size_t)1 << k;
+  Fr root, small_root, g;
+  ntt_root<FR>(root, k);
+  ntt_root<FR>(small_root, NTT_SMALL_LOG);
+  if (offset) {
+    uint32_t w[8];
+    memcpy(w, offset, 32);
+    fr_from_abi<FR>(g, w, (flags & kNttCallNormal) != 0);
+    fr_reduce<FR>(g);
+  } else {
+    fr_set<FR>(g, FR::GENERATOR);
+  }
+  if (kind & kNttKindInverse) {
+    fr_inv<FR>(root, root);
+    fr_inv<FR>(small_root, small_root);
+    fr_inv<FR>(g, g);
+  }
+  std::vector<Fr> wlo, whi, glo, ghi, small;
+  t_ntt_two_level<FR>(wlo, whi, root, k);
+  t_ntt_two_level<FR>(glo, ghi, g, k);
+  t_fr_table<FR>(small, small_root, 1u << (NTT_SMALL_LOG - 1));
+  uint32_t radix[NTT_MAX_LOG];
+  const uint32_t npass = ntt_plan(k, pass_log, radix);
+  std::vector<uint32_t> bufa(n * 8), bufb(n * 8);
+  std::vector<Fr> lds(NTT_TILE);
+  for (uint32_t b = 0; b < batch; b++) {
+    const uint32_t* src = (const uint32_t*)(in + b * n * 32);
+    for (uint32_t i = 0; i < npass; i++) {
+      NttPass ps;
+      ntt_pass_shape(ps, k, radix, npass, i, kind, flags, in_len);
+      ps.w = NttTable{wlo.data(), whi.data()};
+      ps.g = NttTable{glo.data(), ghi.data()};
+      ps.small = small.data();
+      if (ps.has_scale) ntt_size_inv<FR>(ps.scale, k);
+      uint32_t* dst = i + 1 == npass ? (uint32_t*)(out + b * n * 32) : (i & 1) ? bufb.data() : bufa.data();
+      const uint32_t elems = 1u << (ps.p + ps.log_c), tiles = 1u << (k - ps.p - ps.log_c);
+      for (uint32_t tile = 0; tile < tiles; tile++) {
+        for (uint32_t e = 0; e < elems; e++) ntt_load<FR>(lds[e], ps, src, tile, e);
+        for (uint32_t l = 0; l < ps.p; l++)
+          for (uint32_t u = 0; u < elems / 2; u++) ntt_butterfly<FR>(lds.data(), ps, l, u);
+        for (uint32_t e = 0; e < elems; e++) ntt_store<FR>(lds.data(), ps, dst, tile, e);
+      }
+      src = dst;
+    }
+  }
+  return 0;
+}
+
+template <class FR>
+static int t_fr_op(int op, const uint8_t* a, const uint8_t* b, int normal, uint8_t* out) {
+  uint32_t wa[8], wb[8], wo[8];
+  memcpy(wa, a, 32);
+  memcpy(wb, b, 32);
+  if (op == 0) {
+    fr_mul_abi<FR>(wo, wa, wb, normal != 0);
+  } else {
+    Fr x, y, z;
+    fr_from_abi<FR>(x, wa, normal != 0);
+    fr_from_abi<FR>(y, wb, normal != 0);
+    if (op == 1) fr_add(z, x, y); else fr_sub<FR>(z, x, y);
+    fr_carry(z);
+    fr_to_abi<FR>(wo, z, normal != 0);
+  }
+  memcpy(out, wo, 32);
+  return 0;
+}
+
+template <class FR>
+static int t_ntt_element(uint32_t k, uint64_t i, uint8_t* out) {
+  Fr root, r;
+  ntt_root<FR>(root, k);
+  uint32_t e[8] = {(uint32_t)i, (uint32_t)(i >> 32), 0, 0, 0, 0, 0, 0}, w[8];
+  fr_pow_words<FR>(r, root, e);
+  fr_to_abi<FR>(w, r, false);
+  memcpy(out, w, 32);
+  return 0;
+}
+
+// the worst case the butterfly chain may reach: a level-10 chain on limbs at their bounds; only the checker matters
+template <class FR>
+static int t_fr_extreme() {
+  Fr a, b, w, t, d;
+  for (int i = 0; i < FR_NL - 1; i++) a.v[i] = b.v[i] = FR_MASK;
+  a.v[FR_NL - 1] = b.v[FR_NL - 1] = 2 * FR::P[FR_NL - 1] + 1;   // just under 2r + 2^232: the top of class M
+  for (int i = 0; i < FR_NL; i++) w.v[i] = FR::P[i];
+  w.v[0] -= 1;                                                   // r - 1: the largest twiddle
+  for (int l = 0; l < (int)NTT_MAX_PASS_LOG; l++) {
+    fr_mul<FR>(t, b, w);
+    for (int i = 0; i < FR_NL - 1; i++) t.v[i] = FR_MASK;        // the largest normalised limbs a product can leave
+    fr_sub<FR>(d, a, t);
+    fr_add(a, a, t);
+    fr_carry(a);
+    fr_carry(d);
+    b = d;                                                       // the difference is the faster-growing side
+    a = d;
+  }
+  fr_mul<FR>(t, b, w);
+  return 0;
+}
+
+extern "C" {
+// field: 0 BLS12-377 Fr, 1 BLS12-381 Fr.  op 0 product, 1 sum, 2 difference of two 32-byte elements (any 256-bit value), ABI form in and out
+int ht_fr_op(int field, int op, const uint8_t* a, const uint8_t* b, int normal, uint8_t* out) {
+  if (!a || !b || !out || op < 0 || op > 2) return -1;
+  return field == 0 ? t_fr_op<Bls12_377_Fr29>(op, a, b, normal, out) : field == 1 ? t_fr_op<Bls12_381_Fr29>(op, a, b, normal, out) : -1;
+}
+int ht_fr_extreme(int field) { return field == 0 ? t_fr_extreme<Bls12_377_Fr29>() : field == 1 ? t_fr_extreme<Bls12_381_Fr29>() : -1; }
+// one call of mi355_msm_domain_transform on the host: kind 0 forward, 1 inverse, 2 coset forward, 3 coset inverse; flags bit 0 normal
+// form, bit 1 bit-reversed output (forward), bit 2 bit-reversed input (inverse); offset NULL: GENERATOR
+int ht_ntt_transform(int field, unsigned k, unsigned pass_log, unsigned kind, unsigned flags, const uint8_t* offset, const uint8_t* in, unsigned in_len,
+                     unsigned batch, uint8_t* out) {
+  if (k > 20 || pass_log < 1 || pass_log > NTT_MAX_PASS_LOG || kind > 3 || (flags & ~7u) || !in || !out || in_len > (1u << k)) return -1;
+  if (((flags & kNttCallNR) && (kind & kNttKindInverse)) || ((flags & kNttCallRN) && !(kind & kNttKindInverse))) return -1;
+  return field == 0   ? t_ntt_transform<Bls12_377_Fr29>(k, pass_log, kind, flags, offset, in, in_len, batch, out)
+         : field == 1 ? t_ntt_transform<Bls12_381_Fr29>(k, pass_log, kind, flags, offset, in, in_len, batch, out)
+                      : -1;
+}
+// element(i) = omega^i of the domain of size 2^k, as an arkworks image
+int ht_ntt_element(int field, unsigned k, uint64_t i, uint8_t* out) {
+  if (!out) return -1;
+  return field == 0 ? t_ntt_element<Bls12_377_Fr29>(k, i, out) : field == 1 ? t_ntt_element<Bls12_381_Fr29>(k, i, out) : -1;
+}
+}

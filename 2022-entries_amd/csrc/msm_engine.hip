@@ -2757,3 +2757,4 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 #include "msm_fixed.hpp"
 #include "msm_codec.hpp"
 #include "msm_pmul.hpp"
+#include "msm_ntt.hpp"

@@ -127,6 +127,15 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_fixed_set_option": [vp, ctypes.c_char_p, ctypes.c_long],
         "mi355_msm_fixed_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_fixed_destroy": [vp],
+        "mi355_msm_domain_create": [ctypes.POINTER(vp), ci, ci, sz],
+        "mi355_msm_domain_transform": [vp, vp, vp, sz, sz, ctypes.c_uint, ctypes.c_uint, vp],
+        "mi355_msm_domain_transform_device": [vp, vp, vp, sz, sz, ctypes.c_uint, ctypes.c_uint, vp, vp],
+        "mi355_msm_domain_mul": [vp, vp, vp, vp, sz, ctypes.c_uint],
+        "mi355_msm_domain_mul_device": [vp, vp, vp, vp, sz, ctypes.c_uint, vp],
+        "mi355_msm_domain_set_option": [vp, ctypes.c_char_p, ctypes.c_long],
+        "mi355_msm_domain_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_domain_element": [vp, ctypes.c_uint64, vp],
+        "mi355_msm_domain_destroy": [vp],
         "mi355_msm_trim": [],
         "mi355_msm_pool_stats": [ctypes.POINTER(ctypes.c_uint64), sz],
     }
@@ -871,6 +880,170 @@ class WindowTable:
     def close(self) -> None:
         if self.handle:
             _check(self._lib.mi355_msm_fixed_destroy(self.handle))
+            self.handle = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+FR_MODULUS = {
+    0: 8444461749428370424248824938781546531375899335154063827935233455917409239041,   # BLS12-377 Fr
+    1: 52435875175126190479447740508185965837690552500527637822603658699938581184513,  # BLS12-381 Fr
+}
+
+
+class Radix2EvaluationDomain:
+    """``Radix2EvaluationDomain::<Fr>::new(num_coeffs)`` (ARK poly/src/domain/radix2/mod.rs) on one GPU (mi355_msm_domain_*): the
+    domain of the smallest power of two >= ``num_coeffs`` over the scalar field of ``curve``'s family.
+
+    ``fft``, ``ifft``, ``coset_fft``, ``coset_ifft`` take vectors of 32-byte elements -- bytes, a NumPy array or a torch tensor of shape
+    ``(n, 32)`` or ``(batch, n, 32)``; fewer than ``size`` elements per vector are zero-extended (single vectors only) -- and return
+    the same kind of container; a torch GPU tensor is read in place on its current stream and gives a GPU tensor, which
+    ``MultiScalarMultContext.run`` takes as it is under the option ``scalars_montgomery``.  ``montgomery=True`` (default): arkworks
+    ``Fr`` images; ``False``: plain little-endian integers.  ``order``: "NN" (default), "NR" (forward: bit-reversed output) or "RN"
+    (inverse: bit-reversed input).  ``offset``: the coset offset as an integer (default: the field's GENERATOR).  ``out``: a GPU
+    tensor to write into (may be the input)."""
+
+    FORWARD, INVERSE, COSET_FORWARD, COSET_INVERSE = 0, 1, 2, 3
+
+    def __init__(self, num_coeffs: int, curve="bls12_377_g1", device: Optional[int] = None):
+        self.curve = _curve_id(curve)
+        self.modulus = FR_MODULUS[self.curve & 1]
+        self.handle = ctypes.c_void_p()
+        self._lib = load_library()
+        if num_coeffs < 0 or num_coeffs >= 1 << 63:
+            raise ValueError("num_coeffs out of range")
+        _check(self._lib.mi355_msm_domain_create(ctypes.byref(self.handle), self.curve, -1 if device is None else device, int(num_coeffs)))
+        self.size = self.query("size")
+        self.log_size_of_group = self.query("log_size")
+        self.device = self.query("device")
+
+    def element(self, i: int) -> int:
+        """omega^i as an integer"""
+        out = ctypes.create_string_buffer(32)
+        _check(self._lib.mi355_msm_domain_element(self.handle, int(i) % self.size, out))
+        return int.from_bytes(out.raw, "little") * pow(1 << 256, -1, self.modulus) % self.modulus
+
+    @property
+    def group_gen(self) -> int:
+        return self.element(1)
+
+    @property
+    def size_inv(self) -> int:
+        return pow(self.size, -1, self.modulus)
+
+    def _flags(self, kind, montgomery, order):
+        flags = 0 if montgomery else 1
+        if order == "NR":
+            flags |= 2
+        elif order == "RN":
+            flags |= 4
+        elif order != "NN":
+            raise ValueError(f"order {order!r}: one of 'NN', 'NR', 'RN'")
+        return flags
+
+    def _offset(self, offset, montgomery):
+        if offset is None:
+            return None
+        v = int(offset) % self.modulus
+        return ((v << 256) % self.modulus if montgomery else v).to_bytes(32, "little")
+
+    def _shape(self, src, nbytes):
+        """(batch, in_len, result shape or None for bytes) of an input"""
+        shape = getattr(src, "shape", None)
+        if shape is not None and len(shape) == 3:
+            if shape[2] != 32 or shape[1] != self.size:
+                raise ValueError(f"a batch has shape (batch, {self.size}, 32), not {tuple(shape)}")
+            return int(shape[0]), self.size, (int(shape[0]), self.size, 32)
+        if nbytes % 32:
+            raise ValueError("the input is not a multiple of 32 bytes")
+        return 1, nbytes // 32, (self.size, 32)
+
+    def _transform(self, kind, values, montgomery=True, order="NN", offset=None, out=None):
+        if not self.handle:
+            raise MsmError(-1, "the domain is closed")
+        flags = self._flags(kind, montgomery, order)
+        off = self._offset(offset, montgomery)
+        b = _Buf(values)
+        batch, in_len, shape = self._shape(values, b.nbytes)
+        if b.is_device:
+            import torch
+
+            if b.device_index != self.device:
+                raise MsmError(-1, f"the input lives on cuda:{b.device_index} but this domain is bound to device {self.device}")
+            if out is None:
+                out = torch.empty(shape, dtype=torch.uint8, device=b.keep.device)
+            ob = _Buf(out)
+            if not ob.is_device or ob.nbytes != batch * self.size * 32 or ob.keep is not out:
+                raise ValueError(f"out must be a contiguous uint8 GPU tensor of {batch * self.size * 32} bytes")
+            _check(self._lib.mi355_msm_domain_transform_device(self.handle, ob.ptr, b.ptr, in_len, batch, kind, flags, off, b.stream))
+            return out
+        if out is not None:
+            raise ValueError("out= goes with GPU tensors")
+        import numpy as np
+
+        res = np.zeros(batch * self.size * 32, dtype=np.uint8)
+        _check(self._lib.mi355_msm_domain_transform(self.handle, res.ctypes.data, b.ptr, in_len, batch, kind, flags, off))
+        return _like_input(values, res, shape)
+
+    def fft(self, coeffs, **kw):
+        return self._transform(self.FORWARD, coeffs, **kw)
+
+    def ifft(self, evals, **kw):
+        return self._transform(self.INVERSE, evals, **kw)
+
+    def coset_fft(self, coeffs, **kw):
+        return self._transform(self.COSET_FORWARD, coeffs, **kw)
+
+    def coset_ifft(self, evals, **kw):
+        return self._transform(self.COSET_INVERSE, evals, **kw)
+
+    def mul(self, a, b, montgomery: bool = True, out=None):
+        """``out[i] = a[i] * b[i]`` (mul_polynomials_in_evaluation_domain); any number of elements"""
+        if not self.handle:
+            raise MsmError(-1, "the domain is closed")
+        ba, bb = _Buf(a), _Buf(b)
+        if ba.nbytes != bb.nbytes or ba.nbytes % 32 or ba.is_device != bb.is_device:
+            raise ValueError("a and b must hold the same number of 32-byte elements, in the same kind of memory")
+        n = ba.nbytes // 32
+        flags = 0 if montgomery else 1
+        if ba.is_device:
+            import torch
+
+            if out is None:
+                out = torch.empty(tuple(a.shape), dtype=torch.uint8, device=ba.keep.device)
+            ob = _Buf(out)
+            if not ob.is_device or ob.nbytes != ba.nbytes or ob.keep is not out:
+                raise ValueError("out must be a contiguous uint8 GPU tensor of the inputs' size")
+            _check(self._lib.mi355_msm_domain_mul_device(self.handle, ob.ptr, ba.ptr, bb.ptr, n, flags, ba.stream))
+            return out
+        import numpy as np
+
+        res = np.zeros(ba.nbytes, dtype=np.uint8)
+        _check(self._lib.mi355_msm_domain_mul(self.handle, res.ctypes.data, ba.ptr, bb.ptr, n, flags))
+        return _like_input(a, res, getattr(a, "shape", None) or (n, 32))
+
+    def set_option(self, key: str, value: int) -> None:
+        _check(self._lib.mi355_msm_domain_set_option(self.handle, key.encode(), int(value)))
+
+    def query(self, key: str) -> int:
+        """ "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "device", "last_us", "last_device_us" """
+        v = ctypes.c_uint64(0)
+        _check(self._lib.mi355_msm_domain_query(self.handle, key.encode(), ctypes.byref(v)))
+        return int(v.value)
+
+    def close(self) -> None:
+        if self.handle:
+            _check(self._lib.mi355_msm_domain_destroy(self.handle))
             self.handle = ctypes.c_void_p()
 
     def __enter__(self):

@@ -423,6 +423,59 @@ RustError mi355_msm_mul_points(mi355_msm_ctx* ctx, const void* points, size_t np
 RustError mi355_msm_mul_points_device(mi355_msm_ctx* ctx, const void* d_points, size_t npoints, size_t stride, const void* scalars,
                                       size_t scalar_bytes, unsigned flags, void* d_out, size_t out_stride, void* stream);
 
+/* ---- radix-2 evaluation domains over the scalar fields (ARK poly/src/domain/radix2/mod.rs, domain/mod.rs:78-170, :233) ------------
+ * Radix2EvaluationDomain::{fft, ifft, coset_fft, coset_ifft} and the pointwise product, on the device: the step before the MSM in a
+ * prover (evaluations -> ifft -> commit).  The output of a transform in device memory is what mi355_msm_run_device reads under the
+ * option "scalars_montgomery", so nothing crosses PCIe between the two.
+ * A handle is ONE domain size n = 2^k on one device.  Any of the four curve ids selects its family's Fr (BLS12-377: 253 bits, 2-adicity
+ * 47; BLS12-381: 255 bits, 2-adicity 32).  num_coeffs is rounded up to a power of two, as Radix2EvaluationDomain::new does; the call
+ * fails with -1 above the field's 2-adicity and above 2^28.  omega = get_root_of_unity(n): TWO_ADIC_ROOT_OF_UNITY squared s - k times.
+ *   kind     0 forward    out[i] = sum_{j<n} in[j] * omega^(i j)
+ *            1 inverse    out[j] = n^-1 * sum_{i<n} in[i] * omega^(-i j)
+ *            2 coset forward   out[i] = sum_j in[j] * (g omega^i)^j            (distribute_powers, then forward)
+ *            3 coset inverse   out[j] = g^-j * n^-1 * sum_i in[i] * omega^(-i j)   (inverse, then distribute_powers_and_mul_by_const)
+ *   offset   g: a HOST pointer (also in the _device call) to one 32-byte element in the form of the call; NULL = GENERATOR (22 / 7).
+ *            Kinds 2 and 3 only; zero is refused.  The handle keeps the tables of the most recent offset.
+ *   elements 32 bytes.  Default: arkworks Fr images (a * 2^256 mod r, what a Vec<Fr> holds).  Flag bit 0: plain little-endian
+ *            integers on both sides.  ANY 256-bit input is read as its residue modulo r; every output is canonical (< r).
+ *   in_len   <= n; elements from in_len on (in the order they are stored) are read as zero and never touched -- arkworks' resize in
+ *            fft_in_place.  in_len > n is an error, not a truncation.  in may be NULL when in_len is 0.
+ *   batch    vectors, n elements apart in both `in` and `out` (the reference's NTT_batch); at most 65535.  batch = 0 succeeds and
+ *            writes nothing.
+ *   order    natural in, natural out by default.  Flag bit 1 (kinds 0, 2): the output in bit-reversed order; flag bit 2 (kinds 1, 3):
+ *            the input in bit-reversed order -- the pair round a pointwise step.
+ *   out == in is allowed; any other overlap of the bytes read (up to element in_len of the last vector) with the bytes written
+ *            (batch whole vectors) is an error.
+ * A transform is ceil(k / pass_log) launches.  Each is one Stockham pass that reads and writes natural order, so no launch permutes;
+ * a block takes 1024 points through up to 10 butterfly levels in LDS.  The powers of g, the factor n^-1 and the conversions of the
+ * element form are folded into the first load and the last store.  Twiddles come from two-level tables (omega^lo, omega^(hi 2^14)),
+ * built on the device by mi355_msm_domain_create: 3.6 MB at k = 28.
+ * Work memory: one vector per vector in flight (batch * n * 32 bytes), kept by the handle; a host-pointer call stages one vector at a
+ * time through one more.  A handle serves one call at a time.
+ * mi355_msm_domain_mul: out[i] = a[i] * b[i] over n elements (any n; mul_polynomials_in_evaluation_domain), flag bit 0 as above; out may
+ * be a or b.
+ * mi355_msm_domain_element: omega^i as an arkworks image (host arithmetic).
+ * The calls without _device take HOST pointers; the _device calls DEVICE pointers (4-byte aligned) and the hipStream_t on which the
+ * input becomes ready (NULL = the default stream): the work is enqueued there and the call returns when the output is written.
+ * Option "pass_log" 1..10 (0 restores the default, 8): butterfly levels per pass -- a test hook.  Results never depend on it, nor on
+ * host versus device pointers, nor on batching.
+ * Queries: "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "device", "last_us" (host clock around the most recent
+ * call), "last_device_us" (the same call between events on the stream it ran on).
+ * Errors: -1 with a message for null pointers, in_len > n, a partial overlap, unknown or misplaced flag bits, an unknown kind, an offset
+ * on a plain transform, a size above the limits -- decided before any device call; hipErrorNoDevice without a GPU. */
+typedef struct mi355_msm_domain mi355_msm_domain;
+RustError mi355_msm_domain_create(mi355_msm_domain** out, int curve, int device, size_t num_coeffs);
+RustError mi355_msm_domain_transform(mi355_msm_domain* d, void* out, const void* in, size_t in_len, size_t batch, unsigned kind, unsigned flags,
+                                     const void* offset);
+RustError mi355_msm_domain_transform_device(mi355_msm_domain* d, void* d_out, const void* d_in, size_t in_len, size_t batch, unsigned kind,
+                                            unsigned flags, const void* offset, void* stream);
+RustError mi355_msm_domain_mul(mi355_msm_domain* d, void* out, const void* a, const void* b, size_t n, unsigned flags);
+RustError mi355_msm_domain_mul_device(mi355_msm_domain* d, void* d_out, const void* d_a, const void* d_b, size_t n, unsigned flags, void* stream);
+RustError mi355_msm_domain_set_option(mi355_msm_domain* d, const char* key, long value);
+RustError mi355_msm_domain_query(mi355_msm_domain* d, const char* key, uint64_t* value);
+RustError mi355_msm_domain_element(mi355_msm_domain* d, uint64_t i, void* out32);
+RustError mi355_msm_domain_destroy(mi355_msm_domain* d);
+
 /* Sum `count` projective images (any Z) into one normalised image: the multi-GPU combine step
  * ("final 8-point curve add").  Pure host arithmetic on <= a few dozen points; no device needed. */
 RustError mi355_msm_fold(int curve, void* out_projective, const void* projective, size_t count);

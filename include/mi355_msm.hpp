@@ -264,4 +264,46 @@ struct FixedBase {
   }
 };
 
+// ark-poly's Radix2EvaluationDomain over the curve family's Fr (ARK poly/src/domain/radix2/mod.rs): vectors of Fr values (Montgomery
+// form, what a Vec<Fr> holds), zero-extended to the domain size, transformed on the GPU.
+struct Radix2EvaluationDomain {
+  mi355_msm_domain* handle = nullptr;
+  explicit Radix2EvaluationDomain(size_t num_coeffs, int curve = MI355_BLS12_377_G1) { check(mi355_msm_domain_create(&handle, curve, -1, num_coeffs)); }
+  Radix2EvaluationDomain(const Radix2EvaluationDomain&) = delete;
+  Radix2EvaluationDomain& operator=(const Radix2EvaluationDomain&) = delete;
+  Radix2EvaluationDomain(Radix2EvaluationDomain&& o) noexcept : handle(o.handle) { o.handle = nullptr; }
+  uint64_t query(const char* key) const {
+    uint64_t v = 0;
+    check(mi355_msm_domain_query(handle, key, &v));
+    return v;
+  }
+  size_t size() const { return (size_t)query("size"); }
+  BigInteger256 element(uint64_t i) const {
+    BigInteger256 e;
+    check(mi355_msm_domain_element(handle, i, &e));
+    return e;
+  }
+  std::vector<BigInteger256> transform(const std::vector<BigInteger256>& v, unsigned kind) const {
+    std::vector<BigInteger256> out(size());
+    check(mi355_msm_domain_transform(handle, out.data(), v.data(), v.size(), 1, kind, 0, nullptr));
+    return out;
+  }
+  std::vector<BigInteger256> fft(const std::vector<BigInteger256>& coeffs) const { return transform(coeffs, 0); }
+  std::vector<BigInteger256> ifft(const std::vector<BigInteger256>& evals) const { return transform(evals, 1); }
+  std::vector<BigInteger256> coset_fft(const std::vector<BigInteger256>& coeffs) const { return transform(coeffs, 2); }
+  std::vector<BigInteger256> coset_ifft(const std::vector<BigInteger256>& evals) const { return transform(evals, 3); }
+  // mul_polynomials_in_evaluation_domain
+  std::vector<BigInteger256> mul(const std::vector<BigInteger256>& a, const std::vector<BigInteger256>& b) const {
+    std::vector<BigInteger256> out(a.size());
+    check(mi355_msm_domain_mul(handle, out.data(), a.data(), b.data(), a.size() < b.size() ? a.size() : b.size(), 0));
+    return out;
+  }
+  ~Radix2EvaluationDomain() {
+    if (handle) {
+      RustError e = mi355_msm_domain_destroy(handle);
+      if (e.message) std::free(e.message);
+    }
+  }
+};
+
 }  // namespace mi355

@@ -175,6 +175,20 @@ pub mod sys {
         pub fn mi355_msm_fixed_set_option(fb: *mut c_void, key: *const c_char, value: c_long) -> Error;
         pub fn mi355_msm_fixed_query(fb: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
         pub fn mi355_msm_fixed_destroy(fb: *mut c_void) -> Error;
+        // radix-2 evaluation domains over Fr (ark-poly Radix2EvaluationDomain): kind 0 fft, 1 ifft, 2 coset_fft, 3 coset_ifft;
+        // flags bit 0 normal-form elements, bit 1 bit-reversed output, bit 2 bit-reversed input; offset: one element on the host or null
+        pub fn mi355_msm_domain_create(out: *mut *mut c_void, curve: c_int, device: c_int, num_coeffs: usize) -> Error;
+        pub fn mi355_msm_domain_transform(d: *mut c_void, out: *mut c_void, input: *const c_void, in_len: usize, batch: usize, kind: c_uint,
+                                          flags: c_uint, offset: *const c_void) -> Error;
+        pub fn mi355_msm_domain_transform_device(d: *mut c_void, d_out: *mut c_void, d_in: *const c_void, in_len: usize, batch: usize,
+                                                 kind: c_uint, flags: c_uint, offset: *const c_void, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_mul(d: *mut c_void, out: *mut c_void, a: *const c_void, b: *const c_void, n: usize, flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_mul_device(d: *mut c_void, d_out: *mut c_void, d_a: *const c_void, d_b: *const c_void, n: usize, flags: c_uint,
+                                           stream: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_set_option(d: *mut c_void, key: *const c_char, value: c_long) -> Error;
+        pub fn mi355_msm_domain_query(d: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
+        pub fn mi355_msm_domain_element(d: *mut c_void, i: u64, out32: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_destroy(d: *mut c_void) -> Error;
     }
 }
 

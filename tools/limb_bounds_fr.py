@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Worst-case limbs, columns and values of the butterfly chain of csrc/ntt.hpp on the 9 x 29 scalar fields (csrc/fr.hpp).
+
+A pass loads class-M values (normalised limbs, value < 2r), runs up to NTT_MAX_PASS_LOG = 10 levels of
+
+    t = w * b (fr_mul, w canonical);  a' = a + t;  b' = a + BIAS4 - t;  one carry pass on each
+
+and ends with products by canonical table entries.  This script carries an upper bound per limb and on the value through that chain
+exactly as the code performs it and prints, per field and level, the margin of
+
+  * every product-scanning column against 2^64:  col_k <= sum_{i+j=k} A_i W_j + (2^29 - 1) sum_{i+j=k, j>=1} r_j + (2^29 - 1) + carry,
+  * every limb against the 2^31 that fr_mul accepts and every limb-wise sum against 2^32,
+  * every limb of BIAS4 against the limb of t it meets,
+  * the value of a product's first operand against R = 2^261 (what keeps the product below 2r), and 2r against the 2^256 of a stored
+    element.
+
+All margins must be positive (tests/test_fr_consts.py runs it); the host build checks the same sums on every product (MSM_CHECK).
+
+    python tools/limb_bounds_fr.py
+"""
+import sys
+
+N, B = 9, 29
+MASK = (1 << B) - 1
+R = 1 << (N * B)
+LEVELS = 10
+FIELDS = {
+    "Bls12_377_Fr29": 8444461749428370424248824938781546531375899335154063827935233455917409239041,
+    "Bls12_381_Fr29": 52435875175126190479447740508185965837690552500527637822603658699938581184513,
+}
+
+
+def limbs(x):
+    return [(x >> (B * i)) & MASK for i in range(N - 1)] + [x >> (B * (N - 1))]
+
+
+def bias4(r):
+    v = limbs(4 * r)
+    return [v[0] + (1 << B)] + [v[i] + (1 << B) - 1 for i in range(1, N - 1)] + [v[N - 1] - 1]
+
+
+def columns(a, w, rl):
+    """the largest value every column of fr_mul can reach for first-operand limb bounds a and second-operand limb bounds w"""
+    cols, carry = [], 0
+    for k in range(2 * N - 1):
+        c = carry + sum(a[i] * w[k - i] for i in range(N) if 0 <= k - i < N)
+        c += MASK * sum(rl[k - i] for i in range(N) if 1 <= k - i < N)
+        if k < N:
+            c += MASK          # m_k * r_0, r_0 = 1
+        cols.append(c)
+        carry = c >> B
+    return cols
+
+
+def carry_pass(l):
+    return [MASK] + [MASK + (l[i - 1] >> B) for i in range(1, N - 1)] + [l[N - 1] + (l[N - 2] >> B)]
+
+
+def analyse(name, r, out):
+    rl = limbs(r)
+    ok = True
+    margins = []
+
+    def margin(what, have, limit):
+        nonlocal ok
+        m = limit - have
+        margins.append((what, m))
+        ok &= m > 0
+        out.append("  %-58s %s (limit 2^%.2f, margin %.3e)" % (what, "ok " if m > 0 else "BAD", __import__("math").log2(limit), m))
+
+    out.append("%s: r = %.3f * 2^252, R / r = %.2f" % (name, r / 2**252, R / r))
+    top_m = (2 * r) >> (B * (N - 1))                      # the top limb of a class-M value
+    class_m = [MASK] * (N - 1) + [top_m]
+    w = [MASK] * (N - 1) + [rl[N - 1]]                    # a canonical table entry
+    bias = bias4(r)
+    margin("2r against a stored element (2^256)", 2 * r, 1 << 256)
+    for i in range(N):
+        margin("BIAS4 limb %d covers the limb of t" % i, class_m[i], bias[i] + 1)
+    # the conversion of any 256-bit input: value < 2^256, the product below r + 2^256 r / R
+    margin("input conversion: 2^256 against R", 1 << 256, R)
+    margin("pointwise product: (2^256)^2 / R against r", (1 << 512) // R, r)
+    a_l, val = list(class_m), 2                            # limb bounds and the value in units of r
+    for lvl in range(LEVELS + 1):
+        # every element is a product's first operand at this level (as b) or at the store
+        margin("level %2d: value %3dr against R" % (lvl, val), val * r, R)
+        margin("level %2d: largest limb against 2^31" % lvl, max(a_l), 1 << 31)
+        margin("level %2d: largest column against 2^64" % lvl, max(columns(a_l, w, rl)), 1 << 64)
+        if lvl == LEVELS:
+            break
+        s = [a_l[i] + class_m[i] for i in range(N)]
+        d = [a_l[i] + bias[i] for i in range(N)]
+        margin("level %2d: limb-wise sums against 2^32" % lvl, max(max(s), max(d)), 1 << 32)
+        a_l = [max(x, y) for x, y in zip(carry_pass(s), carry_pass(d))]
+        val += 4
+    return ok
+
+
+def main():
+    out = []
+    ok = all([analyse(name, r, out) for name, r in FIELDS.items()])
+    print("\n".join(out))
+    print("all margins positive" if ok else "A MARGIN IS NOT POSITIVE")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
