@@ -107,6 +107,31 @@ def decode(field, raw, normal):
     return [int.from_bytes(raw[i:i + 32], "little") * f % r for i in range(0, len(raw), 32)]
 
 
+def oracle_ntt(lib, field, k, kind, flags, raw, in_len=None, offset=None, threads=0):
+    """One vector through the CPU oracle's NTT (oracle/ntt_oracle.c; `lib` is the `oracle` fixture): `raw` is bytes or a NumPy uint8
+    array of in_len (default: all of it) elements, `offset` 32 bytes in the form of the call or None for the generator.  Returns a
+    NumPy uint8 array of shape (2^k, 32).  threads 0: as many as there are CPUs (the oracle stops at 16)."""
+    import ctypes
+    import os
+
+    import numpy as np
+
+    lib.oracle_ntt.argtypes = [ctypes.c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                               ctypes.c_void_p, ctypes.c_int]
+    lib.oracle_ntt.restype = ctypes.c_int
+    if isinstance(raw, (bytes, bytearray)):
+        raw = np.frombuffer(raw, dtype=np.uint8)
+    raw = np.ascontiguousarray(raw).reshape(-1)
+    assert raw.dtype == np.uint8 and raw.size % 32 == 0
+    in_len = raw.size // 32 if in_len is None else in_len
+    assert in_len * 32 <= raw.size
+    out = np.empty((1 << k, 32), dtype=np.uint8)
+    rc = lib.oracle_ntt(FIELD_IDS[field], k, kind, flags, offset, raw.ctypes.data if in_len else None, in_len, out.ctypes.data,
+                        threads or min(16, os.cpu_count() or 1))
+    assert rc == 0, (field, k, kind, flags, in_len)
+    return out
+
+
 def edge_values(field):
     r = modulus(field)
     return [0, 1, r - 1, r, r + 1, (1 << 256) - 1]
