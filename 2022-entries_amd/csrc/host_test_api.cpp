@@ -1140,3 +1140,234 @@ int ht_ntt_element(int field, unsigned k, uint64_t i, uint8_t* out) {
   return field == 0 ? t_ntt_element<Bls12_377_Fr29>(k, i, out) : field == 1 ? t_ntt_element<Bls12_381_Fr29>(k, i, out) : -1;
 }
 }
+
+// ---- the steps between a transform and an MSM (poly.hpp): the kernels' per-element functions, a block's loops run in order, and the
+// chains of launches the engine runs ------------------------------------------------------------------------------------------------
+#include "poly.hpp"
+
+template <class FR>
+struct HostPolyRun {
+  std::vector<Fr> lds, sa, sb, na, nb;
+  HostPolyRun() : lds(POLY_MAX_TILE), sa(POLY_MAX_LANES), sb(POLY_MAX_LANES), na(POLY_MAX_LANES), nb(POLY_MAX_LANES) {}
+  void eval(const PolyEval& p) {
+    const uint32_t T = 1u << p.t.tile_log, lanes = poly_lanes(p.t.tile_log);
+    for (uint64_t tile = 0; tile < poly_tiles(p.t.n, p.t.tile_log); tile++) {
+      for (uint32_t i = 0; i < T; i++) poly_load<FR>(lds[i], p.t, (tile << p.t.tile_log) + i);
+      for (uint32_t l = 0; l < lanes; l++) poly_eval_lane<FR>(lds.data(), p.z, l);
+      for (uint32_t s = 0; (2u << s) <= lanes; s++)
+        for (uint32_t j = 0; j < (lanes >> (s + 1)); j++) poly_eval_tree<FR>(lds.data(), p.z, s, j);
+      poly_store_m<FR>(p.dst + tile, lds[0]);
+    }
+  }
+  void div(const PolyDiv& p) {
+    const uint32_t T = 1u << p.t.tile_log, lanes = poly_lanes(p.t.tile_log);
+    std::vector<PolyDivLane> st(lanes);
+    for (uint64_t tile = 0; tile < poly_tiles(p.t.n, p.t.tile_log); tile++) {
+      for (uint32_t i = 0; i < T; i++) poly_load<FR>(lds[i], p.t, (tile << p.t.tile_log) + i);
+      for (uint32_t l = 0; l < lanes; l++) poly_div_lane<FR>(st[l], lds.data(), sa.data(), p, tile, l);
+      for (uint32_t s = 0; (1u << s) < lanes; s++) {
+        for (uint32_t l = 0; l < lanes; l++) poly_div_scan<FR>(na[l], sa.data(), p.z, lanes, s, l);
+        for (uint32_t l = 0; l < lanes; l++) sa[l] = na[l];
+      }
+      for (uint32_t l = 0; l < lanes; l++) poly_div_finish<FR>(st[l], lds.data(), sa.data(), p.z, lanes, l);
+      for (uint32_t i = 0; i < T; i++) poly_div_store<FR>(lds.data(), p, tile, i);
+    }
+  }
+  void inv_prod(const PolyInv& p) {
+    const uint32_t T = 1u << p.t.tile_log, lanes = poly_lanes(p.t.tile_log);
+    for (uint64_t tile = 0; tile < poly_tiles(p.t.n, p.t.tile_log); tile++) {
+      bool zero;
+      for (uint32_t i = 0; i < T; i++) poly_inv_load<FR>(lds[i], zero, p.t, (tile << p.t.tile_log) + i);
+      for (uint32_t l = 0; l < lanes; l++) poly_prod_lane<FR>(lds.data(), l);
+      for (uint32_t s = 0; (2u << s) <= lanes; s++)
+        for (uint32_t j = 0; j < (lanes >> (s + 1)); j++) poly_prod_tree<FR>(lds.data(), s, j);
+      p.tiles[tile] = lds[0];
+    }
+  }
+  void inv_tiles(Fr* tiles, uint64_t count, const Fr& coeff) {
+    for (uint64_t t = 0; t < count; t++) poly_inv_tile<FR>(tiles, coeff, t);
+  }
+  void inv_apply(const PolyInv& p) {
+    const uint32_t T = 1u << p.t.tile_log, lanes = poly_lanes(p.t.tile_log);
+    std::vector<PolyInvLane> st(lanes);
+    std::vector<char> zeros(T);
+    for (uint64_t tile = 0; tile < poly_tiles(p.t.n, p.t.tile_log); tile++) {
+      for (uint32_t i = 0; i < T; i++) {
+        bool zero;
+        poly_inv_load<FR>(lds[i], zero, p.t, (tile << p.t.tile_log) + i);
+        zeros[i] = zero;
+      }
+      for (uint32_t l = 0; l < lanes; l++) poly_inv_lane<FR>(st[l], lds.data(), sa.data(), sb.data(), l);
+      for (uint32_t s = 0; (1u << s) < lanes; s++) {
+        for (uint32_t l = 0; l < lanes; l++) poly_inv_scan<FR>(na[l], nb[l], sa.data(), sb.data(), lanes, s, l);
+        for (uint32_t l = 0; l < lanes; l++) {
+          sa[l] = na[l];
+          sb[l] = nb[l];
+        }
+      }
+      for (uint32_t l = 0; l < lanes; l++) poly_inv_finish<FR>(st[l], lds.data(), sa.data(), sb.data(), p.tiles[tile], lanes, l);
+      for (uint32_t i = 0; i < T; i++) poly_inv_store<FR>(lds.data(), p, tile, i, zeros[i] != 0);
+    }
+  }
+};
+
+template <class FR>
+static int t_poly_inverse(uint32_t tile_log, unsigned flags, const uint8_t* coeff, const uint8_t* in, uint64_t n, uint8_t* out) {
+  if (n == 0) return 0;
+  std::vector<Fr> work(poly_work_elems(n, tile_log));
+  std::vector<uint32_t> src(n * 8);
+  memcpy(src.data(), in, n * 32);
+  Fr c;
+  if (coeff) poly_scalar<FR>(c, coeff, (flags & kPolyNormal) != 0); else fr_set<FR>(c, FR::ONE);
+  HostPolyRun<FR> run;
+  poly_chain_inverse<FR>(run, src.data(), src.data(), n, (flags & kPolyNormal) != 0, tile_log, c, work.data());   // in place, as out == in
+  memcpy(out, src.data(), n * 32);
+  return 0;
+}
+
+template <class FR>
+static int t_poly_evaluate(uint32_t tile_log, unsigned flags, const uint8_t* coeffs, uint64_t n, const uint8_t* z, uint8_t* out32) {
+  memset(out32, 0, 32);
+  if (n == 0) return 0;
+  std::vector<Fr> work(poly_work_elems(n, tile_log));
+  std::vector<uint32_t> src(n * 8);
+  memcpy(src.data(), coeffs, n * 32);
+  Fr zz;
+  poly_scalar<FR>(zz, z, (flags & kPolyNormal) != 0);
+  HostPolyRun<FR> run;
+  const Fr* res = poly_chain_evaluate<FR>(run, src.data(), n, (flags & kPolyNormal) != 0, tile_log, zz, work.data());
+  poly_scalar_out<FR>(out32, *res, (flags & kPolyNormal) != 0);
+  return 0;
+}
+
+template <class FR>
+static int t_poly_divide(uint32_t tile_log, unsigned flags, const uint8_t* coeffs, uint64_t n, const uint8_t* z, uint8_t* q, uint8_t* rem32) {
+  memset(rem32, 0, 32);
+  if (n == 0) return 0;
+  std::vector<Fr> work(poly_work_elems(n, tile_log));
+  std::vector<uint32_t> src(n * 8), dst(n * 8);
+  memcpy(src.data(), coeffs, n * 32);
+  Fr zz;
+  poly_scalar<FR>(zz, z, (flags & kPolyNormal) != 0);
+  HostPolyRun<FR> run;
+  const Fr* res = poly_chain_divide<FR>(run, dst.data(), src.data(), n, (flags & kPolyNormal) != 0, tile_log, zz, work.data());
+  poly_scalar_out<FR>(rem32, *res, (flags & kPolyNormal) != 0);
+  if (n > 1) memcpy(q, dst.data(), (n - 1) * 32);
+  return 0;
+}
+
+template <class FR>
+static int t_poly_vec_op(unsigned flags, unsigned op, const uint8_t* a, const uint8_t* b, const uint8_t* c, uint64_t n, uint8_t* out) {
+  std::vector<uint32_t> va(n * 8 + 8), vb(n * 8 + 8), vc(n * 8 + 8), vo(n * 8 + 8);
+  memcpy(va.data(), a, n * 32);
+  if (op != kPolyScale) memcpy(vb.data(), b, n * 32);
+  if (op == kPolyMulSub) memcpy(vc.data(), c, n * 32);
+  PolyVecOp p{va.data(), vb.data(), vc.data(), vo.data(), n, op, (flags & kPolyNormal) ? 1u : 0u, Fr{}};
+  if (op == kPolyScale) poly_scalar<FR>(p.s, b, (flags & kPolyNormal) != 0);
+  for (uint64_t i = 0; i < n; i++) poly_vec_op<FR>(p, i);
+  memcpy(out, vo.data(), n * 32);
+  return 0;
+}
+
+// 1 / Z(g) for the offset g (NULL: GENERATOR); -1 when g is zero or lies in the domain
+template <class FR>
+static int t_poly_coset_factor(uint32_t k, unsigned flags, const uint8_t* offset, uint8_t* out32) {
+  Fr g, zg, zero, s;
+  fr_zero(zero);
+  if (offset) poly_scalar<FR>(g, offset, (flags & kPolyNormal) != 0); else fr_set<FR>(g, FR::GENERATOR);
+  if (memcmp(g.v, zero.v, sizeof g.v) == 0) return -1;
+  poly_vanishing<FR>(zg, g, k);
+  if (memcmp(zg.v, zero.v, sizeof zg.v) == 0) return -1;
+  fr_inv<FR>(s, zg);
+  poly_scalar_out<FR>(out32, s, (flags & kPolyNormal) != 0);
+  return 0;
+}
+
+template <class FR>
+static int t_poly_vanishing(uint32_t k, unsigned flags, const uint8_t* tau, uint8_t* out32) {
+  Fr x, zt;
+  poly_scalar<FR>(x, tau, (flags & kPolyNormal) != 0);
+  poly_vanishing<FR>(zt, x, k);
+  poly_scalar_out<FR>(out32, zt, (flags & kPolyNormal) != 0);
+  return 0;
+}
+
+template <class FR>
+static int t_poly_lagrange(uint32_t k, uint32_t tile_log, unsigned flags, const uint8_t* tau, uint8_t* out) {
+  const uint64_t n = (uint64_t)1 << k;
+  const bool normal = (flags & kPolyNormal) != 0;
+  Fr root, iroot, zt, zero, size_inv;
+  fr_zero(zero);
+  ntt_root<FR>(root, k);
+  fr_inv<FR>(iroot, root);
+  ntt_size_inv<FR>(size_inv, k);
+  std::vector<Fr> wlo, whi, ilo, ihi;
+  t_ntt_two_level<FR>(wlo, whi, root, k);
+  t_ntt_two_level<FR>(ilo, ihi, iroot, k);
+  std::vector<uint32_t> dst(n * 8);
+  PolyLagrange p{};
+  p.dst = dst.data();
+  p.k = k;
+  p.normal = normal ? 1u : 0u;
+  p.w = NttTable{wlo.data(), whi.data()};
+  p.wi = NttTable{ilo.data(), ihi.data()};
+  poly_scalar<FR>(p.tau, tau, normal);
+  poly_vanishing<FR>(zt, p.tau, k);
+  p.in_domain = memcmp(zt.v, zero.v, sizeof zt.v) == 0;
+  p.c = zero;
+  if (!p.in_domain) {
+    fr_mul<FR>(zt, zt, size_inv);
+    fr_reduce<FR>(zt);
+    fr_inv<FR>(p.c, zt);
+  }
+  for (uint32_t i = 0; i < n; i++) poly_lagrange_entry<FR>(p, i);
+  if (!p.in_domain) {
+    std::vector<Fr> work(poly_work_elems(n, tile_log));
+    Fr one;
+    fr_set<FR>(one, FR::ONE);
+    HostPolyRun<FR> run;
+    poly_chain_inverse<FR>(run, dst.data(), dst.data(), n, normal, tile_log, one, work.data());
+  }
+  memcpy(out, dst.data(), n * 32);
+  return 0;
+}
+
+#define POLY_FIELD(fn, ...) (field == 0 ? fn<Bls12_377_Fr29>(__VA_ARGS__) : field == 1 ? fn<Bls12_381_Fr29>(__VA_ARGS__) : -1)
+static bool poly_args_ok(unsigned tile_log, unsigned flags, uint64_t n) {
+  return tile_log >= POLY_TILE_LOG_MIN && tile_log <= POLY_TILE_LOG_MAX && !(flags & ~kPolyNormal) && n <= ((uint64_t)1 << 24);
+}
+
+extern "C" {
+// the calls of msm_poly.hpp on the host, a block's loops in order.  field: 0 BLS12-377 Fr, 1 BLS12-381 Fr; flags bit 0: normal form;
+// tile_log 4 .. 10; scalars are one 32-byte element in the form of the call
+int ht_poly_batch_inverse(int field, unsigned tile_log, unsigned flags, const uint8_t* coeff, const uint8_t* in, uint64_t n, uint8_t* out) {
+  if (!poly_args_ok(tile_log, flags, n) || (n && (!in || !out))) return -1;
+  return POLY_FIELD(t_poly_inverse, tile_log, flags, coeff, in, n, out);
+}
+int ht_poly_evaluate(int field, unsigned tile_log, unsigned flags, const uint8_t* coeffs, uint64_t n, const uint8_t* z, uint8_t* out32) {
+  if (!poly_args_ok(tile_log, flags, n) || (n && !coeffs) || !z || !out32) return -1;
+  return POLY_FIELD(t_poly_evaluate, tile_log, flags, coeffs, n, z, out32);
+}
+int ht_poly_divide_by_linear(int field, unsigned tile_log, unsigned flags, const uint8_t* coeffs, uint64_t n, const uint8_t* z, uint8_t* q, uint8_t* rem32) {
+  if (!poly_args_ok(tile_log, flags, n) || (n && !coeffs) || (n > 1 && !q) || !z || !rem32) return -1;
+  return POLY_FIELD(t_poly_divide, tile_log, flags, coeffs, n, z, q, rem32);
+}
+// op 0 a + b, 1 a - b, 2 a*b - c, 3 b[0] * a (b: one element)
+int ht_poly_vec_op(int field, unsigned flags, unsigned op, const uint8_t* a, const uint8_t* b, const uint8_t* c, uint64_t n, uint8_t* out) {
+  if (!poly_args_ok(POLY_DEFAULT_TILE_LOG, flags, n) || op > kPolyScale || !a || !b || (op == kPolyMulSub && !c) || !out) return -1;
+  return POLY_FIELD(t_poly_vec_op, flags, op, a, b, c, n, out);
+}
+int ht_poly_lagrange(int field, unsigned k, unsigned tile_log, unsigned flags, const uint8_t* tau, uint8_t* out) {
+  if (!poly_args_ok(tile_log, flags, 0) || k > 16 || !tau || !out) return -1;
+  return POLY_FIELD(t_poly_lagrange, k, tile_log, flags, tau, out);
+}
+int ht_poly_vanishing(int field, unsigned k, unsigned flags, const uint8_t* tau, uint8_t* out32) {
+  if ((flags & ~kPolyNormal) || k > 28 || !tau || !out32) return -1;
+  return POLY_FIELD(t_poly_vanishing, k, flags, tau, out32);
+}
+// the factor of divide_by_vanishing_on_coset, 1 / (g^(2^k) - 1); -1 for an offset that is zero or lies in the domain
+int ht_poly_coset_factor(int field, unsigned k, unsigned flags, const uint8_t* offset, uint8_t* out32) {
+  if ((flags & ~kPolyNormal) || k > 28 || !out32) return -1;
+  return POLY_FIELD(t_poly_coset_factor, k, flags, offset, out32);
+}
+}

@@ -2758,3 +2758,4 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 #include "msm_codec.hpp"
 #include "msm_pmul.hpp"
 #include "msm_ntt.hpp"
+#include "msm_poly.hpp"

@@ -9,6 +9,7 @@
 #pragma once
 
 #include "launch_ntt.hpp"
+#include "launch_poly.hpp"
 
 struct mi355_msm_domain {
   int curve = 0;
@@ -17,6 +18,8 @@ struct mi355_msm_domain {
   hipStream_t own_stream = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
   DevBuf tables, work, stage;
+  DevBuf poly, pstage;    // msm_poly.hpp: the partial vectors of the scans; the staged vectors of its host-pointer calls
+  uint32_t poly_tile_log = POLY_DEFAULT_TILE_LOG;
   Fr size_inv{};
   Fr g_have{};            // the (inverted, for the inverse kinds) offset the offset tables hold
   bool g_valid = false;
@@ -57,7 +60,7 @@ void with_fr(int curve, Fn&& fn) {
 }
 
 void domain_release(mi355_msm_domain* d) {
-  for (DevBuf* b : {&d->tables, &d->work, &d->stage}) b->release();
+  for (DevBuf* b : {&d->tables, &d->work, &d->stage, &d->poly, &d->pstage}) b->release();
   for (hipEvent_t& e : d->ev)
     if (e) { (void)hipEventDestroy(e); e = nullptr; }
   if (d->own_stream) { (void)hipStreamDestroy(d->own_stream); d->own_stream = nullptr; }
@@ -349,6 +352,10 @@ RustError mi355_msm_domain_set_option(mi355_msm_domain* d, const char* key, long
     if (k == "pass_log") {   // butterfly levels per pass; 0 restores the default.  Results do not depend on it (a test hook)
       if (value < 0 || value > (long)NTT_MAX_PASS_LOG) bad_arg("pass_log %ld out of range [1, %u] (0 = default)", value, NTT_MAX_PASS_LOG);
       d->pass_log = value ? (uint32_t)value : NTT_DEFAULT_PASS_LOG;
+    } else if (k == "poly_tile_log") {   // elements of a tile of the scans of msm_poly.hpp, as a power of two; 0 restores the default (a test hook)
+      if (value != 0 && (value < (long)POLY_TILE_LOG_MIN || value > (long)POLY_TILE_LOG_MAX))
+        bad_arg("poly_tile_log %ld out of range [%u, %u] (0 = default)", value, POLY_TILE_LOG_MIN, POLY_TILE_LOG_MAX);
+      d->poly_tile_log = value ? (uint32_t)value : POLY_DEFAULT_TILE_LOG;
     } else
       bad_arg("unknown domain option '%s'", key);
   });
@@ -365,6 +372,8 @@ RustError mi355_msm_domain_query(mi355_msm_domain* d, const char* key, uint64_t*
     else if (k == "pass_log") *value = d->pass_log;
     else if (k == "table_bytes") *value = d->tables.bytes;
     else if (k == "work_bytes") *value = d->work.bytes + d->stage.bytes;
+    else if (k == "poly_work_bytes") *value = d->poly.bytes + d->pstage.bytes;
+    else if (k == "poly_tile_log") *value = d->poly_tile_log;
     else if (k == "device") *value = (uint64_t)d->device;
     else if (k == "last_us") *value = d->last_us;
     else if (k == "last_device_us") *value = d->last_device_us;

@@ -136,6 +136,19 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_domain_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_domain_element": [vp, ctypes.c_uint64, vp],
         "mi355_msm_domain_destroy": [vp],
+        "mi355_msm_domain_batch_inverse": [vp, vp, vp, sz, vp, ctypes.c_uint],
+        "mi355_msm_domain_batch_inverse_device": [vp, vp, vp, sz, vp, ctypes.c_uint, vp],
+        "mi355_msm_domain_vec_op": [vp, vp, vp, vp, vp, sz, ctypes.c_uint, ctypes.c_uint],
+        "mi355_msm_domain_vec_op_device": [vp, vp, vp, vp, vp, sz, ctypes.c_uint, ctypes.c_uint, vp],
+        "mi355_msm_domain_evaluate": [vp, vp, vp, sz, vp, ctypes.c_uint],
+        "mi355_msm_domain_evaluate_device": [vp, vp, vp, sz, vp, ctypes.c_uint, vp],
+        "mi355_msm_domain_divide_by_linear": [vp, vp, vp, vp, sz, vp, ctypes.c_uint],
+        "mi355_msm_domain_divide_by_linear_device": [vp, vp, vp, vp, sz, vp, ctypes.c_uint, vp],
+        "mi355_msm_domain_lagrange": [vp, vp, vp, ctypes.c_uint],
+        "mi355_msm_domain_lagrange_device": [vp, vp, vp, ctypes.c_uint, vp],
+        "mi355_msm_domain_vanishing": [vp, vp, vp, ctypes.c_uint],
+        "mi355_msm_domain_divide_by_vanishing_on_coset": [vp, vp, vp, sz, vp, ctypes.c_uint],
+        "mi355_msm_domain_divide_by_vanishing_on_coset_device": [vp, vp, vp, sz, vp, ctypes.c_uint, vp],
         "mi355_msm_trim": [],
         "mi355_msm_pool_stats": [ctypes.POINTER(ctypes.c_uint64), sz],
     }
@@ -1032,11 +1045,170 @@ class Radix2EvaluationDomain:
         _check(self._lib.mi355_msm_domain_mul(self.handle, res.ctypes.data, ba.ptr, bb.ptr, n, flags))
         return _like_input(a, res, getattr(a, "shape", None) or (n, 32))
 
+    # ---- between a transform and an MSM (mi355_msm_domain_batch_inverse .. _divide_by_vanishing_on_coset) -------------------------
+    # Vectors are bytes, NumPy arrays or torch tensors of n 32-byte elements (any n; the Lagrange call alone is tied to ``size``); a
+    # torch GPU tensor is read in place on its current stream and gives a GPU tensor (``out=`` as in ``mul``).  Scalars (``z``,
+    # ``tau``, ``coeff``, ``s``, ``offset``) are Python integers and so are scalar results.
+
+    def _scalar(self, v, montgomery):
+        v = int(v) % self.modulus
+        return ((v << 256) % self.modulus if montgomery else v).to_bytes(32, "little")
+
+    def _scalar_out(self, raw, montgomery):
+        v = int.from_bytes(raw, "little")
+        return v * pow(1 << 256, -1, self.modulus) % self.modulus if montgomery else v
+
+    def _vectors(self, *vs):
+        """the buffers of same-sized inputs in one kind of memory, and their element count"""
+        if not self.handle:
+            raise MsmError(-1, "the domain is closed")
+        bufs = [_Buf(v) for v in vs]
+        b0 = bufs[0]
+        for b in bufs:
+            if b.nbytes != b0.nbytes or b.nbytes % 32 or b.is_device != b0.is_device:
+                raise ValueError("the vectors must hold the same number of 32-byte elements, in the same kind of memory")
+            if b.is_device and b.device_index != self.device:
+                raise MsmError(-1, f"the input lives on cuda:{b.device_index} but this domain is bound to device {self.device}")
+        return bufs, b0.nbytes // 32
+
+    def _out(self, src, b, out, n):
+        """(result container, its _Buf) for n elements: a GPU tensor for GPU inputs, else a NumPy array"""
+        if b.is_device:
+            import torch
+
+            if out is None:
+                out = torch.empty((n, 32), dtype=torch.uint8, device=b.keep.device)
+            ob = _Buf(out)
+            if not ob.is_device or ob.nbytes != n * 32 or ob.keep is not out:
+                raise ValueError(f"out must be a contiguous uint8 GPU tensor of {n * 32} bytes")
+            return out, ob
+        if out is not None:
+            raise ValueError("out= goes with GPU tensors")
+        import numpy as np
+
+        res = np.zeros(max(n, 1) * 32, dtype=np.uint8)[:n * 32]
+        return res, _Buf(res)
+
+    def _map(self, name, src, b, n, out, tail, shape=None):
+        """one vector in, one vector out: name(handle, out, in, n, *tail[, stream])"""
+        res, ob = self._out(src, b, out, n)
+        if b.is_device:
+            _check(getattr(self._lib, name + "_device")(self.handle, ob.ptr, b.ptr, n, *tail, b.stream))
+            return res
+        _check(getattr(self._lib, name)(self.handle, ob.ptr, b.ptr, n, *tail))
+        return _like_input(src, res, shape or (n, 32))
+
+    def batch_inversion_and_mul(self, v, coeff=None, montgomery: bool = True, out=None):
+        """``out[i] = coeff / v[i]`` (``coeff`` None: 1); elements that are zero stay zero, as arkworks skips them.  ``out`` may be ``v``."""
+        (b,), n = self._vectors(v)
+        c = None if coeff is None else self._scalar(coeff, montgomery)
+        return self._map("mi355_msm_domain_batch_inverse", v, b, n, out, (c, 0 if montgomery else 1))
+
+    def batch_inversion(self, v, montgomery: bool = True, out=None):
+        return self.batch_inversion_and_mul(v, None, montgomery=montgomery, out=out)
+
+    ADD, SUB, MUL_SUB, SCALE = 0, 1, 2, 3
+
+    def _vec_op(self, op, a, b, c, montgomery, out):
+        flags = 0 if montgomery else 1
+        if op == self.SCALE:
+            (ba,), n = self._vectors(a)
+            ptrs = (self._scalar(b, montgomery), None)
+        elif op == self.MUL_SUB:
+            (ba, bb, bc), n = self._vectors(a, b, c)
+            ptrs = (bb.ptr, bc.ptr)
+        else:
+            (ba, bb), n = self._vectors(a, b)
+            ptrs = (bb.ptr, None)
+        res, ob = self._out(a, ba, out, n)
+        if ba.is_device:
+            _check(self._lib.mi355_msm_domain_vec_op_device(self.handle, ob.ptr, ba.ptr, ptrs[0], ptrs[1], n, op, flags, ba.stream))
+            return res
+        _check(self._lib.mi355_msm_domain_vec_op(self.handle, ob.ptr, ba.ptr, ptrs[0], ptrs[1], n, op, flags))
+        return _like_input(a, res, (n, 32))
+
+    def add(self, a, b, montgomery: bool = True, out=None):
+        """``a[i] + b[i]``; ``out`` may be any input"""
+        return self._vec_op(self.ADD, a, b, None, montgomery, out)
+
+    def sub(self, a, b, montgomery: bool = True, out=None):
+        """``a[i] - b[i]``"""
+        return self._vec_op(self.SUB, a, b, None, montgomery, out)
+
+    def mul_sub(self, a, b, c, montgomery: bool = True, out=None):
+        """``a[i] * b[i] - c[i]``: the numerator of the quotient polynomial"""
+        return self._vec_op(self.MUL_SUB, a, b, c, montgomery, out)
+
+    def scale(self, a, s: int, montgomery: bool = True, out=None):
+        """``s * a[i]`` for one integer ``s``"""
+        return self._vec_op(self.SCALE, a, s, None, montgomery, out)
+
+    def evaluate(self, coeffs, z: int, montgomery: bool = True) -> int:
+        """``DensePolynomial::evaluate``: ``sum coeffs[i] z^i`` as an integer"""
+        (b,), n = self._vectors(coeffs)
+        res = ctypes.create_string_buffer(32)
+        zz, flags = self._scalar(z, montgomery), 0 if montgomery else 1
+        if b.is_device:
+            _check(self._lib.mi355_msm_domain_evaluate_device(self.handle, res, b.ptr, n, zz, flags, b.stream))
+        else:
+            _check(self._lib.mi355_msm_domain_evaluate(self.handle, res, b.ptr, n, zz, flags))
+        return self._scalar_out(res.raw, montgomery)
+
+    def divide_by_linear(self, coeffs, z: int, montgomery: bool = True, out=None):
+        """``(p - p(z)) / (X - z)`` and ``p(z)``: (the n - 1 quotient coefficients, the remainder as an integer).  ``out`` must not
+        overlap ``coeffs``."""
+        (b,), n = self._vectors(coeffs)
+        qn = max(n - 1, 0)
+        q, qb = self._out(coeffs, b, out, qn)
+        rem = ctypes.create_string_buffer(32)
+        zz, flags = self._scalar(z, montgomery), 0 if montgomery else 1
+        if b.is_device:
+            _check(self._lib.mi355_msm_domain_divide_by_linear_device(self.handle, qb.ptr if qn else None, rem, b.ptr, n, zz, flags, b.stream))
+        else:
+            _check(self._lib.mi355_msm_domain_divide_by_linear(self.handle, qb.ptr if qn else None, rem, b.ptr, n, zz, flags))
+            q = _like_input(coeffs, q, (qn, 32))
+        return q, self._scalar_out(rem.raw, montgomery)
+
+    def evaluate_all_lagrange_coefficients(self, tau: int, montgomery: bool = True, out=None, device: bool = False):
+        """the ``size`` values ``L_i(tau)``; ``tau`` in the domain gives the unit vector.  A NumPy array, or with ``out=`` / ``device=True``
+        a GPU tensor written on the current stream."""
+        if not self.handle:
+            raise MsmError(-1, "the domain is closed")
+        t, flags = self._scalar(tau, montgomery), 0 if montgomery else 1
+        if out is not None or device:
+            import torch
+
+            if out is None:
+                out = torch.empty((self.size, 32), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            ob = _Buf(out)
+            if not ob.is_device or ob.nbytes != self.size * 32 or ob.keep is not out or ob.device_index != self.device:
+                raise ValueError(f"out must be a contiguous uint8 tensor of {self.size * 32} bytes on cuda:{self.device}")
+            _check(self._lib.mi355_msm_domain_lagrange_device(self.handle, ob.ptr, t, flags, ob.stream))
+            return out
+        import numpy as np
+
+        res = np.zeros((self.size, 32), dtype=np.uint8)
+        _check(self._lib.mi355_msm_domain_lagrange(self.handle, res.ctypes.data, t, flags))
+        return res
+
+    def evaluate_vanishing_polynomial(self, tau: int) -> int:
+        """``tau^size - 1`` (host arithmetic)"""
+        res = ctypes.create_string_buffer(32)
+        _check(self._lib.mi355_msm_domain_vanishing(self.handle, res, self._scalar(tau, False), 1))
+        return int.from_bytes(res.raw, "little")
+
+    def divide_by_vanishing_poly_on_coset(self, evals, offset=None, montgomery: bool = True, out=None):
+        """``evals[i] / (g^size - 1)`` for the coset offset ``g`` (default: GENERATOR); ``out`` may be ``evals``"""
+        (b,), n = self._vectors(evals)
+        off = None if offset is None else self._scalar(offset, montgomery)
+        return self._map("mi355_msm_domain_divide_by_vanishing_on_coset", evals, b, n, out, (off, 0 if montgomery else 1))
+
     def set_option(self, key: str, value: int) -> None:
         _check(self._lib.mi355_msm_domain_set_option(self.handle, key.encode(), int(value)))
 
     def query(self, key: str) -> int:
-        """ "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "device", "last_us", "last_device_us" """
+        """ "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "poly_tile_log", "device", "last_us",
+        "last_device_us" """
         v = ctypes.c_uint64(0)
         _check(self._lib.mi355_msm_domain_query(self.handle, key.encode(), ctypes.byref(v)))
         return int(v.value)

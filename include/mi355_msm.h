@@ -459,7 +459,7 @@ RustError mi355_msm_mul_points_device(mi355_msm_ctx* ctx, const void* d_points, 
  * input becomes ready (NULL = the default stream): the work is enqueued there and the call returns when the output is written.
  * Option "pass_log" 1..10 (0 restores the default, 8): butterfly levels per pass -- a test hook.  Results never depend on it, nor on
  * host versus device pointers, nor on batching.
- * Queries: "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "device", "last_us" (host clock around the most recent
+ * Queries: "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "poly_tile_log", "device", "last_us" (host clock around the most recent
  * call), "last_device_us" (the same call between events on the stream it ran on).
  * Errors: -1 with a message for null pointers, in_len > n, a partial overlap, unknown or misplaced flag bits, an unknown kind, an offset
  * on a plain transform, a size above the limits -- decided before any device call; hipErrorNoDevice without a GPU. */
@@ -475,6 +475,62 @@ RustError mi355_msm_domain_set_option(mi355_msm_domain* d, const char* key, long
 RustError mi355_msm_domain_query(mi355_msm_domain* d, const char* key, uint64_t* value);
 RustError mi355_msm_domain_element(mi355_msm_domain* d, uint64_t i, void* out32);
 RustError mi355_msm_domain_destroy(mi355_msm_domain* d);
+
+/* ---- between a transform and an MSM: batch inversion, evaluation, division by X - z, Lagrange coefficients, element-wise calls ---------
+ * (ARK ff/src/fields/mod.rs:811-873 batch_inversion_and_mul; poly/src/polynomial/univariate/dense.rs:41-94 evaluate;
+ * poly/src/polynomial/univariate/mod.rs:102 divide_with_q_and_r by X - z; poly/src/domain/radix2/mod.rs:141-216
+ * evaluate_all_lagrange_coefficients, evaluate_vanishing_polynomial; poly/src/domain/mod.rs:190-197
+ * divide_by_vanishing_poly_on_coset_in_place.)  With them the Groth16 / Marlin quotient
+ * h = coset_ifft((coset_fft(a) * coset_fft(b) - coset_fft(c)) / Z(g)) and a KZG opening (p(z), (p - p(z)) / (X - z), then the MSM of
+ * the quotient) run from coefficients to commitment in device memory.
+ * All of them live on the domain handle and follow its conventions: 32-byte elements, arkworks Fr images or, with flag bit 0 (the only
+ * flag), plain integers; ANY 256-bit input is read as its residue and every output is canonical; the calls without _device take HOST
+ * pointers and stage whole vectors through buffers the handle keeps, the _device calls take DEVICE pointers (4-byte aligned) and the
+ * stream on which the input becomes ready, and return when the output is written.  The scalars z, tau, coeff, offset and the factor
+ * of the scaling are ONE HOST element in the form of the call, also in the _device calls, and so are the results out32 / rem32.
+ * Vector lengths are any n up to 2^30 and have nothing to do with the domain's size, except for the Lagrange call.
+ *   batch_inverse   out[i] = coeff / in[i]; coeff NULL = 1.  An element that is 0 modulo r (the byte patterns r, 2r, .. included)
+ *                   gives canonical 0, as arkworks skips zeros.  out == in is allowed; any other overlap is refused.
+ *   vec_op          op 0: a + b;  1: a - b;  2: a * b - c;  3: s * a, where b points to the one HOST element s.  c is read by op 2
+ *                   only.  out may be any of the input vectors exactly; a partial overlap is refused.  (mi355_msm_domain_mul stays.)
+ *   evaluate        out32 = sum_i coeffs[i] z^i.  n = 0 gives 0; z = 0 gives coeffs[0].
+ *   divide_by_linear  q_out[i] = sum_(j > i) coeffs[j] z^(j - i - 1) for i < n - 1: the n - 1 coefficients of (p - p(z)) / (X - z),
+ *                   leading zeros kept; rem32 = p(z) (may be NULL).  Any overlap of q_out with coeffs is refused.  n <= 1 writes no
+ *                   quotient (q_out may be NULL).
+ *   lagrange        the `size` values L_i(tau) = Z(tau) omega^i / (size (tau - omega^i)); tau in the domain gives the unit vector.
+ *   vanishing       out32 = tau^size - 1, in host arithmetic like mi355_msm_domain_element.
+ *   divide_by_vanishing_on_coset  out[i] = in[i] / (g^size - 1) for the coset offset g (NULL = GENERATOR): the scaling with a factor
+ *                   derived on the host.  out == in is allowed.  An offset that is zero or lies in the domain (Z(g) = 0) is an error.
+ * The three scans share one tiled scheme (csrc/poly.hpp): a block takes a tile of 1024 consecutive elements through LDS, 256 lanes own 4
+ * neighbours each.  The inversion is three launches: the product of every tile; one Fermat inversion per TILE, one lane each; then
+ * Montgomery's trick inside the tile.  The evaluation reduces every tile to one partial and runs again on the partials; the division
+ * is that way up, then a way down on which every tile is read again with the carry that enters it.  Levels are separate launches on
+ * one stream: no block waits on another, nothing is atomic.  Work memory: the partials and carries, 2 (n / 1024 + n / 1024^2 + ..)
+ * elements of 36 bytes, allocated on the first such call and kept by the handle, plus the staged vectors of host-pointer calls --
+ * query "poly_work_bytes" ("work_bytes" keeps its meaning).  Option "poly_tile_log" 4..10 (0 restores the default, 10): a test hook,
+ * results never depend on it; also a query.
+ * Errors: -1 with a message for null pointers, a partial overlap, unknown flag bits, an unknown op, n above 2^30, a bad offset and, last,
+ * a null handle -- decided before any device call; hipErrorNoDevice without a GPU (no handle can be created). */
+RustError mi355_msm_domain_batch_inverse(mi355_msm_domain* d, void* out, const void* in, size_t n, const void* coeff, unsigned flags);
+RustError mi355_msm_domain_batch_inverse_device(mi355_msm_domain* d, void* d_out, const void* d_in, size_t n, const void* coeff, unsigned flags,
+                                                void* stream);
+RustError mi355_msm_domain_vec_op(mi355_msm_domain* d, void* out, const void* a, const void* b, const void* c, size_t n, unsigned op, unsigned flags);
+RustError mi355_msm_domain_vec_op_device(mi355_msm_domain* d, void* d_out, const void* d_a, const void* d_b, const void* d_c, size_t n, unsigned op,
+                                         unsigned flags, void* stream);
+RustError mi355_msm_domain_evaluate(mi355_msm_domain* d, void* out32, const void* coeffs, size_t n, const void* z, unsigned flags);
+RustError mi355_msm_domain_evaluate_device(mi355_msm_domain* d, void* out32, const void* d_coeffs, size_t n, const void* z, unsigned flags,
+                                           void* stream);
+RustError mi355_msm_domain_divide_by_linear(mi355_msm_domain* d, void* q_out, void* rem32, const void* coeffs, size_t n, const void* z,
+                                            unsigned flags);
+RustError mi355_msm_domain_divide_by_linear_device(mi355_msm_domain* d, void* d_q_out, void* rem32, const void* d_coeffs, size_t n, const void* z,
+                                                   unsigned flags, void* stream);
+RustError mi355_msm_domain_lagrange(mi355_msm_domain* d, void* out, const void* tau, unsigned flags);
+RustError mi355_msm_domain_lagrange_device(mi355_msm_domain* d, void* d_out, const void* tau, unsigned flags, void* stream);
+RustError mi355_msm_domain_vanishing(mi355_msm_domain* d, void* out32, const void* tau, unsigned flags);
+RustError mi355_msm_domain_divide_by_vanishing_on_coset(mi355_msm_domain* d, void* out, const void* in, size_t n, const void* offset,
+                                                        unsigned flags);
+RustError mi355_msm_domain_divide_by_vanishing_on_coset_device(mi355_msm_domain* d, void* d_out, const void* d_in, size_t n, const void* offset,
+                                                               unsigned flags, void* stream);
 
 /* Sum `count` projective images (any Z) into one normalised image: the multi-GPU combine step
  * ("final 8-point curve add").  Pure host arithmetic on <= a few dozen points; no device needed. */

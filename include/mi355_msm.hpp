@@ -298,6 +298,60 @@ struct Radix2EvaluationDomain {
     check(mi355_msm_domain_mul(handle, out.data(), a.data(), b.data(), a.size() < b.size() ? a.size() : b.size(), 0));
     return out;
   }
+  // ark-ff batch_inversion_and_mul: coeff / v[i], zeros stay zero
+  std::vector<BigInteger256> batch_inversion_and_mul(const std::vector<BigInteger256>& v, const BigInteger256* coeff = nullptr) const {
+    std::vector<BigInteger256> out(v.size());
+    check(mi355_msm_domain_batch_inverse(handle, out.data(), v.data(), v.size(), coeff, 0));
+    return out;
+  }
+  std::vector<BigInteger256> batch_inversion(const std::vector<BigInteger256>& v) const { return batch_inversion_and_mul(v); }
+  // op 0 a + b, 1 a - b, 2 a * b - c
+  std::vector<BigInteger256> vec_op(unsigned op, const std::vector<BigInteger256>& a, const std::vector<BigInteger256>& b,
+                                    const std::vector<BigInteger256>* c = nullptr) const {
+    std::vector<BigInteger256> out(a.size());
+    size_t n = a.size() < b.size() ? a.size() : b.size();
+    if (c && c->size() < n) n = c->size();
+    check(mi355_msm_domain_vec_op(handle, out.data(), a.data(), b.data(), c ? c->data() : nullptr, n, op, 0));
+    return out;
+  }
+  std::vector<BigInteger256> add(const std::vector<BigInteger256>& a, const std::vector<BigInteger256>& b) const { return vec_op(0, a, b); }
+  std::vector<BigInteger256> sub(const std::vector<BigInteger256>& a, const std::vector<BigInteger256>& b) const { return vec_op(1, a, b); }
+  std::vector<BigInteger256> mul_sub(const std::vector<BigInteger256>& a, const std::vector<BigInteger256>& b, const std::vector<BigInteger256>& c) const {
+    return vec_op(2, a, b, &c);
+  }
+  std::vector<BigInteger256> scale(const std::vector<BigInteger256>& a, const BigInteger256& s) const {
+    std::vector<BigInteger256> out(a.size());
+    check(mi355_msm_domain_vec_op(handle, out.data(), a.data(), &s, nullptr, a.size(), 3, 0));
+    return out;
+  }
+  // DensePolynomial::evaluate
+  BigInteger256 evaluate(const std::vector<BigInteger256>& coeffs, const BigInteger256& z) const {
+    BigInteger256 out;
+    check(mi355_msm_domain_evaluate(handle, &out, coeffs.data(), coeffs.size(), &z, 0));
+    return out;
+  }
+  // (p - p(z)) / (X - z): coeffs.size() - 1 coefficients; *rem = p(z)
+  std::vector<BigInteger256> divide_by_linear(const std::vector<BigInteger256>& coeffs, const BigInteger256& z, BigInteger256* rem = nullptr) const {
+    std::vector<BigInteger256> q(coeffs.empty() ? 0 : coeffs.size() - 1);
+    check(mi355_msm_domain_divide_by_linear(handle, q.data(), rem, coeffs.data(), coeffs.size(), &z, 0));
+    return q;
+  }
+  std::vector<BigInteger256> evaluate_all_lagrange_coefficients(const BigInteger256& tau) const {
+    std::vector<BigInteger256> out(size());
+    check(mi355_msm_domain_lagrange(handle, out.data(), &tau, 0));
+    return out;
+  }
+  BigInteger256 evaluate_vanishing_polynomial(const BigInteger256& tau) const {
+    BigInteger256 out;
+    check(mi355_msm_domain_vanishing(handle, &out, &tau, 0));
+    return out;
+  }
+  // divide_by_vanishing_poly_on_coset_in_place; offset NULL: GENERATOR
+  std::vector<BigInteger256> divide_by_vanishing_poly_on_coset(const std::vector<BigInteger256>& evals, const BigInteger256* offset = nullptr) const {
+    std::vector<BigInteger256> out(evals.size());
+    check(mi355_msm_domain_divide_by_vanishing_on_coset(handle, out.data(), evals.data(), evals.size(), offset, 0));
+    return out;
+  }
   ~Radix2EvaluationDomain() {
     if (handle) {
       RustError e = mi355_msm_domain_destroy(handle);

@@ -189,6 +189,30 @@ pub mod sys {
         pub fn mi355_msm_domain_query(d: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
         pub fn mi355_msm_domain_element(d: *mut c_void, i: u64, out32: *mut c_void) -> Error;
         pub fn mi355_msm_domain_destroy(d: *mut c_void) -> Error;
+        // between a transform and an MSM (ark-ff batch_inversion_and_mul, ark-poly evaluate / divide by X - z / Lagrange coefficients):
+        // flags bit 0 = plain integers; coeff, z, tau, offset and the results out32 / rem32 are one HOST element; op 0 a + b, 1 a - b,
+        // 2 a * b - c, 3 s * a with b pointing to the host element s
+        pub fn mi355_msm_domain_batch_inverse(d: *mut c_void, out: *mut c_void, input: *const c_void, n: usize, coeff: *const c_void, flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_batch_inverse_device(d: *mut c_void, d_out: *mut c_void, d_in: *const c_void, n: usize, coeff: *const c_void,
+                                                     flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_vec_op(d: *mut c_void, out: *mut c_void, a: *const c_void, b: *const c_void, c: *const c_void, n: usize, op: c_uint,
+                                       flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_vec_op_device(d: *mut c_void, d_out: *mut c_void, d_a: *const c_void, d_b: *const c_void, d_c: *const c_void, n: usize,
+                                              op: c_uint, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_evaluate(d: *mut c_void, out32: *mut c_void, coeffs: *const c_void, n: usize, z: *const c_void, flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_evaluate_device(d: *mut c_void, out32: *mut c_void, d_coeffs: *const c_void, n: usize, z: *const c_void, flags: c_uint,
+                                                stream: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_divide_by_linear(d: *mut c_void, q_out: *mut c_void, rem32: *mut c_void, coeffs: *const c_void, n: usize,
+                                                 z: *const c_void, flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_divide_by_linear_device(d: *mut c_void, d_q_out: *mut c_void, rem32: *mut c_void, d_coeffs: *const c_void, n: usize,
+                                                        z: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_lagrange(d: *mut c_void, out: *mut c_void, tau: *const c_void, flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_lagrange_device(d: *mut c_void, d_out: *mut c_void, tau: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_vanishing(d: *mut c_void, out32: *mut c_void, tau: *const c_void, flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_divide_by_vanishing_on_coset(d: *mut c_void, out: *mut c_void, input: *const c_void, n: usize, offset: *const c_void,
+                                                             flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_divide_by_vanishing_on_coset_device(d: *mut c_void, d_out: *mut c_void, d_in: *const c_void, n: usize,
+                                                                    offset: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
     }
 }
 

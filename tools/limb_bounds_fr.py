@@ -17,6 +17,7 @@ exactly as the code performs it and prints, per field and level, the margin of
 All margins must be positive (tests/test_fr_consts.py runs it); the host build checks the same sums on every product (MSM_CHECK).
 
     python tools/limb_bounds_fr.py
+    python tools/limb_bounds_fr.py --poly     (the chains of csrc/poly.hpp: analyse_poly below)
 """
 import sys
 
@@ -95,8 +96,77 @@ def analyse(name, r, out):
     return ok
 
 
+POLY_SCAN_LEVELS = 8     # a tile of csrc/poly.hpp has at most 256 lanes
+
+
+def analyse_poly(name, r, out):
+    """The chains of csrc/poly.hpp (python tools/limb_bounds_fr.py --poly): products of products (the runs, trees and scans of the
+    batch inversion, the powers), Horner steps (a product plus an element, fed into the next product) and the sums of the LDS tree
+    and scan (one class-M product more per level, one carry pass after it), carried exactly as the code performs them."""
+    import math
+
+    rl = limbs(r)
+    ok = True
+
+    def margin(what, have, limit):
+        nonlocal ok
+        m = limit - have
+        ok &= m > 0
+        out.append("  %-66s %s (limit 2^%.2f, margin %.3e)" % (what, "ok " if m > 0 else "BAD", math.log2(limit), m))
+
+    def first_operand(what, l, val, second):
+        """an element with limb bounds l and value < val r as the first operand of fr_mul; the product must be class M again"""
+        margin(what + ": value %dr against R" % val, val * r, R)
+        margin(what + ": largest limb against 2^31", max(l), 1 << 31)
+        margin(what + ": largest column against 2^64", max(columns(l, second, rl)), 1 << 64)
+        sec_val = 2 * r if second is class_m else r
+        margin(what + ": product r + a b / R against 2r", r + val * r * sec_val // R + 1, 2 * r)
+
+    out.append("%s: r = %.3f * 2^252, R / r = %.2f  (the chains of poly.hpp)" % (name, r / 2**252, R / r))
+    top_m = (2 * r) >> (B * (N - 1))
+    class_m = [MASK] * (N - 1) + [top_m]
+    w = [MASK] * (N - 1) + [rl[N - 1]]
+    bias = bias4(r)
+    margin("second operand: limbs of a class-M value against 2^29 + 8", max(class_m), (1 << B) + 8)
+    # the batch inversion: nothing but class-M values multiplied together, to any depth (runs, trees, scans, x^(r - 2))
+    first_operand("product of class-M by class-M", class_m, 2, class_m)
+    # Horner: acc' = acc * z + c with z canonical and c class M, no carry pass in between
+    horner = [class_m[i] + class_m[i] for i in range(N)]
+    margin("Horner step: limb-wise sum against 2^32", max(horner), 1 << 32)
+    first_operand("Horner step acc z + c as the next first operand", horner, 4, w)
+    # the sums of the tree (evaluation) and of the suffix scan (division): v' = v + (a product), then one carry pass
+    a_l, val = list(horner), 4
+    for lvl in range(POLY_SCAN_LEVELS + 1):
+        first_operand("tree / scan level %d: the element times a power of z" % lvl, a_l, val, w)
+        if lvl == POLY_SCAN_LEVELS:
+            break
+        sm = [a_l[i] + class_m[i] for i in range(N)]
+        margin("tree / scan level %d: limb-wise sum against 2^32" % lvl, max(sm), 1 << 32)
+        margin("tree / scan level %d: top limb into the carry pass against 2^31" % lvl, sm[N - 1] + (sm[N - 2] >> B), 1 << 31)
+        a_l = carry_pass(sm)
+        val += 2
+    # the division's last step: S = s_j (a Horner value) + z^(4 - j) * (scan value), carried, then converted or brought to class M
+    fin = [horner[i] + class_m[i] for i in range(N)]
+    margin("division finish: limb-wise sum against 2^32", max(fin), 1 << 32)
+    first_operand("division finish S as the first operand of the conversion", carry_pass(fin), 6, w)
+    # differences: tau - w^i (Lagrange), a - b, a*b - c: a class-M value + BIAS4 - a class-M value, one carry pass
+    for i in range(N):
+        margin("BIAS4 limb %d covers the limb of a class-M value" % i, class_m[i], bias[i] + 1)
+    diff = [class_m[i] + bias[i] for i in range(N)]
+    margin("difference: limb-wise sum against 2^32", max(diff), 1 << 32)
+    first_operand("difference a + 4r - b as a first operand", carry_pass(diff), 7, w)
+    # the element-wise sum
+    first_operand("sum a + b as a first operand", carry_pass(horner), 4, w)
+    return ok
+
+
 def main():
     out = []
+    if "--poly" in sys.argv[1:]:
+        ok = all([analyse_poly(name, r, out) for name, r in FIELDS.items()])
+        print("\n".join(out))
+        print("all margins positive" if ok else "A MARGIN IS NOT POSITIVE")
+        return 0 if ok else 1
     ok = all([analyse(name, r, out) for name, r in FIELDS.items()])
     print("\n".join(out))
     print("all margins positive" if ok else "A MARGIN IS NOT POSITIVE")
