@@ -1371,3 +1371,161 @@ int ht_poly_coset_factor(int field, unsigned k, unsigned flags, const uint8_t* o
   return POLY_FIELD(t_poly_coset_factor, k, flags, offset, out32);
 }
 }
+
+// ---- transforms of vectors of points (group_fft.hpp) with the limb-bound checker armed ------------------------------------------
+// The SAME MSM_HD functions the kernels of kernels_gfft.hip wrap: the index maps, the twiddle exponent, the twiddle and the factor as
+// canonical words, the table of a butterfly's B, the walk and the butterfly; records by fb_host_records, the vector between two
+// stages and the output by fb_normalize_run, in the order msm_gfft.hpp launches them (one chunk).
+#include "group_fft.hpp"
+
+template <class E>
+static void gf_host_emit(const std::vector<XyzzDevT<typename E::T>>& res, bool projective, uint8_t* out, size_t out_stride, const typename E::Md& md) {
+  pm_host_output<E>(res, projective ? 2u : 0u, out, out_stride, md);
+}
+
+template <class E>
+static void gf_host_scale(const GfVec& v, size_t count, const GfScale& fs, uint32_t k, uint32_t w, bool projective, uint8_t* dst, size_t dstride,
+                          const typename E::Md& md) {
+  using El = typename E::T;
+  const uint32_t entries = pm_table_entries(w);
+  std::vector<XyzzT<El>> x(entries);
+  std::vector<AffineDevT<El>> table(entries);
+  std::vector<XyzzDevT<El>> res(count);
+  for (size_t j = 0; j < count; j++) {
+    uint32_t sc[8];
+    gf_scale_words<GfFr<E>>(sc, fs, k, (uint32_t)j);
+    gf_table<E>(x.data(), 1, v, (uint32_t)j, entries, md);
+    fb_host_records<E>(table.data(), x.data(), entries, md);
+    pm_windowed_mul<E>(res[j].p, table.data(), 1, sc, w, pm_top_window(pm_bit_length(sc), w), md);
+  }
+  gf_host_emit<E>(res, projective, dst, dstride, md);
+}
+
+template <class C>
+static int t_gf_transform(uint32_t k, unsigned kind, const uint8_t* offset, const uint8_t* in, size_t stride, uint32_t in_len, uint32_t w, unsigned flags,
+                          uint8_t* out, size_t out_stride) {
+  using E = typename C::E;
+  using El = typename E::T;
+  using FR = GfFr<E>;
+  typename E::Md md;
+  const size_t n = (size_t)1 << k, half = n / 2, img0 = 8 * E::WORDS + 8;
+  const bool inverse = (kind & kNttKindInverse) != 0, coset = (kind & kNttKindCoset) != 0, projective = (flags & kGfProjective) != 0;
+  const uint32_t entries = pm_table_entries(w);
+  Fr root, g;
+  ntt_root<FR>(root, k);
+  if (offset) {
+    uint32_t ow[8];
+    memcpy(ow, offset, 32);
+    fr_from_abi<FR>(g, ow, false);
+    fr_reduce<FR>(g);
+  } else {
+    fr_set<FR>(g, FR::GENERATOR);
+  }
+  if (inverse) {
+    fr_inv<FR>(root, root);
+    fr_inv<FR>(g, g);
+  }
+  std::vector<Fr> wlo, whi, glo, ghi;
+  t_ntt_two_level<FR>(wlo, whi, root, k);
+  t_ntt_two_level<FR>(glo, ghi, g, k);
+  const NttTable tw{wlo.data(), whi.data()};
+  GfScale fs{};
+  fs.g = NttTable{glo.data(), ghi.data()};
+  ntt_size_inv<FR>(fs.scale, k);
+  fs.has_g = coset;
+  fs.has_scale = inverse;
+  GfVec src{in, stride, in_len};
+  if (k == 0) {
+    std::vector<XyzzT<El>> x(1);
+    gf_table<E>(x.data(), 1, src, 0, 1, md);
+    std::vector<XyzzDevT<El>> res(1);
+    res[0].p = x[0];
+    gf_host_emit<E>(res, projective, out, out_stride, md);
+    return 0;
+  }
+  std::vector<uint8_t> vec[2] = {std::vector<uint8_t>(n * img0), std::vector<uint8_t>(n * img0)};
+  int cur = -1;
+  if (coset && !inverse) {
+    gf_host_scale<E>(src, in_len, fs, k, w, false, vec[0].data(), img0, md);
+    cur = 0;
+    src = GfVec{vec[0].data(), img0, in_len};
+  }
+  std::vector<XyzzT<El>> x(entries);
+  std::vector<AffineDevT<El>> table(entries);
+  std::vector<XyzzDevT<El>> res(n);
+  for (uint32_t s = 0; s < k; s++) {
+    const bool to_out = s + 1 == k && !inverse;
+    const int nxt = cur == 0 ? 1 : 0;
+    for (size_t b = 0; b < half; b++) {
+      if (s == 0) {
+        gf_butterfly_first<E>(&res[b].p, &res[half + b].p, src, k, (uint32_t)b, md);
+        continue;
+      }
+      uint32_t sc[8];
+      gf_twiddle_words<FR>(sc, tw, k, gf_twiddle_exp(k, s, (uint32_t)b));
+      gf_table<E>(x.data(), 1, src, gf_index_b(k, s, (uint32_t)b), entries, md);
+      fb_host_records<E>(table.data(), x.data(), entries, md);
+      gf_butterfly_mul<E>(&res[b].p, &res[half + b].p, src, table.data(), 1, sc, w, pm_top_window(pm_bit_length(sc), w), k, s, (uint32_t)b, md);
+    }
+    if (to_out) {
+      gf_host_emit<E>(res, projective, out, out_stride, md);
+    } else {
+      gf_host_emit<E>(res, false, vec[nxt].data(), img0, md);
+      cur = nxt;
+      src = GfVec{vec[cur].data(), img0, (uint32_t)n};
+    }
+  }
+  if (inverse) gf_host_scale<E>(src, n, fs, k, w, projective, out, out_stride, md);
+  return 0;
+}
+
+template <class FR>
+static int t_gf_twiddles(uint32_t k, int inverse, const uint32_t* exps, size_t count, uint8_t* out) {
+  Fr root;
+  ntt_root<FR>(root, k);
+  if (inverse) fr_inv<FR>(root, root);
+  std::vector<Fr> lo, hi;
+  t_ntt_two_level<FR>(lo, hi, root, k);
+  const NttTable tw{lo.data(), hi.data()};
+  for (size_t i = 0; i < count; i++) {
+    if (exps[i] >> k) return -1;
+    uint32_t w[8];
+    gf_twiddle_words<FR>(w, tw, k, exps[i]);
+    memcpy(out + 32 * i, w, 32);
+  }
+  return 0;
+}
+
+extern "C" {
+// butterfly b of stage s of a transform of 2^k points: out = {index of A, index of B, twiddle exponent}
+int ht_gf_index(unsigned k, unsigned s, unsigned b, uint32_t* out) {
+  if (!out || k < 1 || k > 28 || s >= k || b >= (1u << (k - 1))) return -1;
+  out[0] = gf_index_a(k, s, b);
+  out[1] = gf_index_b(k, s, b);
+  out[2] = gf_twiddle_exp(k, s, b);
+  return 0;
+}
+// root^e of the domain of 2^k points (the inverse root's for inverse != 0) through the two-level tables, as canonical 32-byte integers
+int ht_gf_twiddle_words(int field, unsigned k, int inverse, const uint32_t* exps, size_t count, uint8_t* out) {
+  if (!exps || !out || k > 20) return -1;
+  return field == 0 ? t_gf_twiddles<Bls12_377_Fr29>(k, inverse, exps, count, out) : field == 1 ? t_gf_twiddles<Bls12_381_Fr29>(k, inverse, exps, count, out) : -1;
+}
+// one call of mi355_msm_fft_points on the host: window size w, flags bit 1 Projective images, offset an arkworks image or NULL
+int ht_gf_transform(int curve, unsigned k, unsigned kind, const uint8_t* offset, const uint8_t* in, size_t stride, unsigned in_len, int w, unsigned flags,
+                    uint8_t* out, size_t out_stride) {
+  if (k > 12 || kind > 3 || (flags & ~kGfProjective) || !out || (in_len && !in) || in_len > (1u << k) || w < 1 || w > (int)PM_MAX_WINDOW || stride % 4 ||
+      out_stride % 4 || (offset && !(kind & 2)))
+    return -1;
+  DISPATCH_C(curve, t_gf_transform, k, kind, offset, in, stride, in_len, (uint32_t)w, flags, out, out_stride)
+}
+// the refusals of a call from plain values (gf_check_call): returns 0 and an empty message for a call that would run, else -1
+int ht_gf_check(int ctx_curve, int ctx_sharded, int ctx_device, int dom_curve, int dom_device, unsigned k, const void* out, size_t out_stride, const void* in,
+                size_t in_len, size_t stride, unsigned kind, unsigned flags, int has_offset, int offset_is_zero, size_t work_limit, char* msg, size_t msg_len) {
+  if (!msg || msg_len < 1) return -2;
+  GfCall c{ctx_curve, ctx_sharded, ctx_device, dom_curve, dom_device, k, out, out_stride, in, in_len, stride, kind, flags, has_offset, offset_is_zero, work_limit};
+  char buf[256];
+  const char* m = gf_check_call(c, buf, sizeof buf);
+  snprintf(msg, msg_len, "%s", m ? m : "");
+  return m ? -1 : 0;
+}
+}

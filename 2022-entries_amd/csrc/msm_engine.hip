@@ -383,6 +383,12 @@ struct mi355_msm_ctx {
   DevBuf pm_points, pm_scalars, pm_out;         // host-pointer calls: one chunk of staged points / scalars / packed output images
   hipEvent_t pm_ev[2] = {nullptr, nullptr};     // around the device work of a call, on the stream it runs on
   uint64_t last_mul_us = 0, last_mul_device_us = 0;
+  long opt_fft_points_chunk = 0;                // butterflies (table points) per chunk of fft_points (msm_gfft.hpp); 0 = the default
+  DevBuf gf_stage, gf_rec, gf_prefix, gf_inf;   // one chunk of fft_points: table entries in XYZZ (then the chunk's results), their records, scratch, flags
+  DevBuf gf_vec[2];                             // the vector between two stages: packed Affine images
+  DevBuf gf_points, gf_out;                     // host-pointer calls: the staged input / the packed output images
+  hipEvent_t gf_ev[2] = {nullptr, nullptr};
+  uint64_t last_fft_points_us = 0, last_fft_points_device_us = 0;
   long opt_assume_subgroup = 0;   // 1: every base is in the order-r subgroup (r P = O), so a scalar k in (r/2, r) may run as (r - k)(-P)
   long opt_anchor = 1;            // option "anchor_window": 1 = end the signed-digit carry chain at the last full window where that saves additions
   bool anchor_armed = false;      // ... for the run under way: the sum of its bases is at hand (run_device_t)
@@ -570,6 +576,7 @@ void ensure_device(mi355_msm_ctx* ctx) { HIP_OK(hipSetDevice(ctx->device)); }
 // what mul_points runs with (msm_pmul.hpp): the window bits and the points per chunk the options come to
 uint32_t pmul_window(const mi355_msm_ctx* ctx);
 size_t pmul_chunk(const mi355_msm_ctx* ctx);
+size_t gfft_chunk(const mi355_msm_ctx* ctx);   // butterflies per chunk of fft_points (msm_gfft.hpp)
 
 // Every compute entry point starts here: no device, no service (this library has no CPU fallback).  Returns the device count.
 int require_device() {
@@ -2082,9 +2089,12 @@ RustError mi355_msm_destroy(mi355_msm_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->own_stream);
     DevBuf* bufs[] = {&ctx->bases, &ctx->inf, &ctx->scalars, &ctx->te_bases, &ctx->flags, &ctx->stateless_raw[0], &ctx->stateless_raw[1], &ctx->stateless_raw[2],
                       &ctx->codec_in, &ctx->codec_out, &ctx->codec_stat[0], &ctx->codec_stat[1],
-                      &ctx->pm_stage, &ctx->pm_rec, &ctx->pm_prefix, &ctx->pm_inf, &ctx->pm_points, &ctx->pm_scalars, &ctx->pm_out};
+                      &ctx->pm_stage, &ctx->pm_rec, &ctx->pm_prefix, &ctx->pm_inf, &ctx->pm_points, &ctx->pm_scalars, &ctx->pm_out,
+                      &ctx->gf_stage, &ctx->gf_rec, &ctx->gf_prefix, &ctx->gf_inf, &ctx->gf_vec[0], &ctx->gf_vec[1], &ctx->gf_points, &ctx->gf_out};
     for (DevBuf* b : bufs) b->release();
     for (auto& ev : ctx->pm_ev)
+      if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : ctx->gf_ev)
       if (ev) (void)hipEventDestroy(ev);
     release_work_buffers(ctx);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -2359,6 +2369,10 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value) 
       // window bits of pairwise mul_points (0 = the default, 4); results do not depend on it: a test hook
       if (value < 0 || value > 6) bad_arg("mul_window %ld out of range [1, 6] (0 = the default)", value);
       ctx->opt_mul_window = value;
+    } else if (k == "fft_points_chunk") {
+      // butterflies per chunk of fft_points (0 = the default: msm_gfft.hpp); results do not depend on it: a test puts seams at small n
+      if (value < 0 || value >= (1l << 31)) bad_arg("fft_points_chunk %ld out of range [0, 2^31)", value);
+      ctx->opt_fft_points_chunk = value;
     } else if (k == "assume_subgroup") {
       ctx->opt_assume_subgroup = value != 0;
     } else if (k == "carry") {
@@ -2511,6 +2525,15 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
       *value = pmul_chunk(ctx);
     else if (k == "mul_work_bytes")
       *value = ctx->pm_stage.bytes + ctx->pm_rec.bytes + ctx->pm_prefix.bytes + ctx->pm_inf.bytes + ctx->pm_points.bytes + ctx->pm_scalars.bytes + ctx->pm_out.bytes;
+    else if (k == "fft_points_chunk")
+      *value = gfft_chunk(ctx);
+    else if (k == "fft_points_work_bytes")
+      *value = ctx->gf_stage.bytes + ctx->gf_rec.bytes + ctx->gf_prefix.bytes + ctx->gf_inf.bytes + ctx->gf_vec[0].bytes + ctx->gf_vec[1].bytes +
+               ctx->gf_points.bytes + ctx->gf_out.bytes;
+    else if (k == "last_fft_points_us")
+      *value = ctx->last_fft_points_us;
+    else if (k == "last_fft_points_device_us")
+      *value = ctx->last_fft_points_device_us;
     else if (k == "last_mul_us")
       *value = ctx->last_mul_us;
     else if (k == "last_mul_device_us")
@@ -2759,3 +2782,4 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 #include "msm_pmul.hpp"
 #include "msm_ntt.hpp"
 #include "msm_poly.hpp"
+#include "msm_gfft.hpp"

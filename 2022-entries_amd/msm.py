@@ -114,6 +114,8 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_point_to_compressed": [ci, vp, vp],
         "mi355_msm_mul_points": [vp, vp, sz, sz, vp, sz, ctypes.c_uint, vp, sz],
         "mi355_msm_mul_points_device": [vp, vp, sz, sz, vp, sz, ctypes.c_uint, vp, sz, vp],
+        "mi355_msm_fft_points": [vp, vp, vp, sz, vp, sz, sz, ctypes.c_uint, ctypes.c_uint, vp],
+        "mi355_msm_fft_points_device": [vp, vp, vp, sz, vp, sz, sz, ctypes.c_uint, ctypes.c_uint, vp, vp],
         "mi355_msm_last_stateless": [ctypes.POINTER(ctypes.c_double), sz],
         "mi355_msm_stream_create": [ctypes.POINTER(vp), ci, ci, sz, ci],
         "mi355_msm_stream_set_option": [vp, ctypes.c_char_p, ctypes.c_long],
@@ -509,6 +511,77 @@ class MultiScalarMultContext:
     def mul_by_cofactor(self, points, projective: bool = False, stride: Optional[int] = None, out_stride: Optional[int] = None):
         """``out[i] = COFACTOR * points[i]``: arkworks' ``mul_by_cofactor`` (NOT ``clear_cofactor``, which for BLS12-381 is another map)."""
         return self._mul_points(points, None, 0, 8 | (2 if projective else 0), stride, out_stride)
+
+    def fft_points(self, dom, points, kind: Optional[int] = None, inverse: bool = False, coset: bool = False, offset=None,
+                   in_len: Optional[int] = None, projective: bool = False, stride: Optional[int] = None, out_stride: Optional[int] = None,
+                   out=None):
+        """``dom.fft`` / ``ifft`` / ``coset_fft`` / ``coset_ifft`` of a vector of GROUP elements (mi355_msm_fft_points): ``out[i] = sum_j
+        omega^(i j) points[j]`` and its three relatives, the multipliers the canonical integers of the field elements -- what turns a
+        monomial SRS ``[tau^j] G`` into the Lagrange SRS ``[L_i(tau)] G`` (``inverse=True``).  ``dom``: a ``Radix2EvaluationDomain`` of
+        this curve's family on this context's device.  ``points``: Affine images ``stride`` bytes apart (flag byte authoritative,
+        infinities anywhere; subgroup points, nothing is tested); the first ``in_len`` (default: all) are read and the vector is
+        extended to ``dom.size`` with the point at infinity.  ``kind`` 0..3 or ``inverse`` / ``coset``; ``offset``: the coset offset as
+        an integer (default: GENERATOR).  ``dom.size`` Affine images out (``projective``: normalised Projective images),
+        ``out_stride`` bytes apart, in the kind of container that came in; GPU tensors are read in place on the current torch stream
+        and give a GPU tensor, ready for ``set_bases``.  ``out``: a GPU tensor to write into; it may be the input when the strides are
+        equal."""
+        import numpy as np
+
+        if not getattr(dom, "handle", None):
+            raise MsmError(-1, "the domain is closed")
+        if kind is None:
+            kind = (1 if inverse else 0) | (2 if coset else 0)
+        elif inverse or coset:
+            raise ValueError("give kind= or inverse= / coset=, not both")
+        kind = int(kind)
+        if not 0 <= kind <= 3:
+            raise ValueError(f"kind {kind}: 0 forward, 1 inverse, 2 coset forward, 3 coset inverse")
+        if offset is not None and not kind & 2:
+            raise ValueError("an offset goes with the coset kinds")
+        cid = self.curve
+        flags = 2 if projective else 0
+        size = projective_bytes(cid) if projective else affine_stride(cid)
+        stride = affine_stride(cid) if stride is None else int(stride)
+        out_stride = size if out_stride is None else int(out_stride)
+        if stride % 4 or stride < 2 * (projective_bytes(cid) // 3) + 1:
+            raise ValueError(f"stride {stride} must be a multiple of 4 and hold two coordinates and the flag byte")
+        if out_stride % 4 or out_stride < size:
+            raise ValueError(f"out_stride {out_stride} must be a multiple of 4 and at least the {size}-byte image")
+        b = _Buf(points)
+        if b.nbytes % stride:
+            raise ValueError(f"points image of {b.nbytes} bytes is not a multiple of the {stride}-byte stride")
+        have = b.nbytes // stride
+        in_len = have if in_len is None else int(in_len)
+        if in_len < 0 or in_len > have:
+            raise ValueError(f"in_len {in_len} with {have} points given")
+        n = int(dom.size)
+        if in_len > n:
+            raise ValueError(f"{in_len} points exceed the domain size {n}")
+        off = None
+        if offset is not None:
+            off = ((int(offset) % dom.modulus) << 256) % dom.modulus
+            off = off.to_bytes(32, "little")
+        self._check_device(b, "points")
+        if b.is_device:
+            import torch
+
+            if out is None:
+                out = torch.zeros((n, out_stride), dtype=torch.uint8, device=b.keep.device)
+            ob = _Buf(out)
+            if not ob.is_device or ob.nbytes != n * out_stride or ob.keep is not out:
+                raise ValueError(f"out must be a contiguous uint8 GPU tensor of {n * out_stride} bytes")
+            self._check_device(ob, "out")
+            _check(self._lib.mi355_msm_fft_points_device(self.context, dom.handle, ob.ptr, out_stride, b.ptr if in_len else None, in_len, stride, kind,
+                                                         flags, off, b.stream))
+            return out
+        if out is not None:
+            raise ValueError("out= goes with GPU tensors")
+        o = np.zeros(n * out_stride, dtype=np.uint8)
+        _check(self._lib.mi355_msm_fft_points(self.context, dom.handle, o.ctypes.data, out_stride, b.ptr if in_len else None, in_len, stride, kind, flags, off))
+        return _like_input(points, o, (n, out_stride))
+
+    def ifft_points(self, dom, points, **kw):
+        return self.fft_points(dom, points, inverse=True, **kw)
 
     def run(self, scalars, npoints: Optional[int] = None) -> List[bytes]:
         b = _Buf(scalars)

@@ -532,6 +532,60 @@ RustError mi355_msm_domain_divide_by_vanishing_on_coset(mi355_msm_domain* d, voi
 RustError mi355_msm_domain_divide_by_vanishing_on_coset_device(mi355_msm_domain* d, void* d_out, const void* d_in, size_t n, const void* offset,
                                                                unsigned flags, void* stream);
 
+/* ---- transforms of vectors of curve points over a domain (ARK poly/src/domain/mod.rs:99-170 on DomainCoeff = G1Projective / G2Projective) ----
+ * domain.fft / ifft / coset_fft / coset_ifft on GROUP elements: what turns a monomial SRS [tau^j] G into the Lagrange SRS
+ * [L_i(tau)] G (kind 1), and the transform behind FK20, cq and Caulk tables.  With in[j] a point and the products scalar multiples:
+ *   kind     0 forward    out[i] = sum_{j<n} omega^(i j) * in[j]
+ *            1 inverse    out[j] = n^-1 * sum_{i<n} omega^(-i j) * in[i]
+ *            2 coset forward   out[i] = sum_j (g omega^i)^j * in[j]
+ *            3 coset inverse   out[j] = g^-j * n^-1 * sum_i omega^(-i j) * in[i]
+ * Every multiplier is the canonical integer below r of the field element, as arkworks' MulAssign<Fr> uses.  Natural order in and out.
+ *   ctx      a single-device context of the curve whose points these are; domain: a handle of the same curve FAMILY on the same
+ *            device (n = its size, omega, the tables).  The context's base set plays no part.
+ *   in       in_len <= n arkworks Affine images, `stride` bytes apart (a multiple of 4, at least two coordinates and the flag byte),
+ *            read as mi355_msm_mul_points reads them: the flag byte is authoritative, infinities are allowed anywhere, and NOTHING is
+ *            tested.  Points from in_len on are the point at infinity and their bytes are never read; in may be NULL when in_len is 0
+ *            (the call then writes n infinities).  The points must lie in the order-r subgroup for the result to be the sums above;
+ *            for other records the result is unspecified, but the call finishes: every memory access is a function of the lane
+ *            index, n and the twiddle's digits alone.
+ *   offset   g: a HOST pointer (also in the _device call) to one 32-byte arkworks Fr image; NULL = GENERATOR.  Kinds 2 and 3 only;
+ *            zero is refused.
+ *   out      n images, out_stride bytes apart (a multiple of 4, at least the image size; bytes between two images are not written).
+ *            Default: Affine images -- x, y canonical, every flag and pad byte written, infinity all zeros with flag 1.  Flag bit 1:
+ *            normalised Projective images, as mi355_msm_mul_points writes them.  No other flag bit exists.
+ *            out == in with out_stride == stride is allowed; any other overlap of the bytes read with the bytes written is refused.
+ * n = 1 copies (normalises) the point.
+ * The transform is k = log2 n stages of n / 2 butterflies T = w * B, A' = A + T, B' = A - T, decimation in time in Stockham's
+ * self-sorting layout (csrc/group_fft.hpp): every stage reads through an index map and writes two contiguous runs, so no launch
+ * permutes.  One lane per butterfly: the twiddle LO[e mod 2^14] * HI[e >> 14] from the domain's tables becomes a canonical integer in
+ * registers, its signed digits walk B's table (built and normalised per stage, as mul_points builds one), and the two mixed additions
+ * of the affine A onto T and -T follow in the same kernel.  Stage 0 has twiddle 1 everywhere and multiplies nothing: a forward
+ * transform costs (n / 2)(k - 1) multiplications; a coset forward transform one more per point (by g^j, before the stages), an inverse
+ * one more per point (by n^-1 or g^-j n^-1 as one factor, after them).  Between two stages the vector is normalised back to Affine
+ * images by the batched normalisation.
+ * Work memory, kept by the context (query "fft_points_work_bytes"): two vectors of n packed Affine images, the chunk buffers of one
+ * stage -- sized like mul_points': the largest power of two within its 2 GiB bound, 2^19 butterflies for G1 and 2^18 for G2, which
+ * take 1.6 GiB at the default window -- and, for host-pointer calls, the staged input and output.  Options: "fft_points_chunk", butterflies per chunk (0 restores the default; a test hook);
+ * "mul_window" applies as it stands.  Results never depend on either, nor on host versus device pointers.
+ * Queries: "fft_points_chunk", "fft_points_work_bytes", "last_fft_points_us" (host clock around the most recent call),
+ * "last_fft_points_device_us" (the same call between events on the stream it ran on).
+ * mi355_msm_fft_points takes HOST pointers; mi355_msm_fft_points_device DEVICE pointers (4-byte aligned) and the hipStream_t on which
+ * the input becomes ready (NULL = the default stream): the work is enqueued there and the call returns when the output is written.
+ * Errors: -1 with a message for an unknown kind, unknown flag bits, an offset on kinds 0 and 1, a zero offset, null handles, a sharded
+ * context, a domain of the other curve family or on another device, in_len > n, bad strides, null pointers, a partial overlap, a size
+ * whose two work vectors exceed 64 GiB -- decided before any device call; hipErrorNoDevice without a GPU (no handle can be created).
+ * Measured on one MI355X (tools/gfft_bench.py, profiles/gfft.txt: device-resident subgroup points, host clock, beside pairwise
+ * mul_points on the same points; the count gives (k - 1) / 2 multiplications per point forward, one more for the inverse kinds):
+ * BLS12-381 G1 at 2^20 points forward 403 ms, inverse 452 ms, coset inverse 453 ms -- 9.0, 10.1 and 10.1 times mul_points against a
+ * count of 9.5 and 10.5; BLS12-377 G1 387 / 434 / 435 ms.  At 2^16 a stage no longer fills the device and the ratio tends to k - 1:
+ * BLS12-381 G1 89 / 96 / 96 ms (14.3 / 15.4 / 15.4 times), G2 243 / 262 / 262 ms (14.2 / 15.3 / 15.4 times); at 2^12 63 / 69 / 69 ms and
+ * 168 / 185 / 186 ms (11 and 12 times).  Not measured: sizes above 2^20, G2 above 2^16, the coset forward transform, host-pointer calls,
+ * Projective output, and any kernel-level profile. */
+RustError mi355_msm_fft_points(mi355_msm_ctx* ctx, mi355_msm_domain* domain, void* out, size_t out_stride, const void* in, size_t in_len,
+                               size_t stride, unsigned kind, unsigned flags, const void* offset);
+RustError mi355_msm_fft_points_device(mi355_msm_ctx* ctx, mi355_msm_domain* domain, void* d_out, size_t out_stride, const void* d_in, size_t in_len,
+                                      size_t stride, unsigned kind, unsigned flags, const void* offset, void* stream);
+
 /* Sum `count` projective images (any Z) into one normalised image: the multi-GPU combine step
  * ("final 8-point curve add").  Pure host arithmetic on <= a few dozen points; no device needed. */
 RustError mi355_msm_fold(int curve, void* out_projective, const void* projective, size_t count);

@@ -360,4 +360,17 @@ struct Radix2EvaluationDomain {
   }
 };
 
+// domain.fft / ifft / coset_fft / coset_ifft on a vector of G1 points (mi355_msm_fft_points): kind 0 .. 3 as for Fr; `points` may be
+// shorter than the domain (the rest is the point at infinity); offset NULL: GENERATOR.  Affine images out, ready for
+// multi_scalar_mult_init -- kind 1 on a monomial SRS [tau^j] G gives the Lagrange SRS [L_i(tau)] G.
+inline std::vector<G1Affine> fft_points(MultiScalarMultContext& ctx, const Radix2EvaluationDomain& dom, const std::vector<G1Affine>& points, unsigned kind = 0,
+                                        const BigInteger256* offset = nullptr) {
+  std::vector<G1Affine> out(dom.size());
+  check(mi355_msm_fft_points(ctx.context, dom.handle, out.data(), sizeof(G1Affine), points.data(), points.size(), sizeof(G1Affine), kind, 0u, offset));
+  return out;
+}
+inline std::vector<G1Affine> ifft_points(MultiScalarMultContext& ctx, const Radix2EvaluationDomain& dom, const std::vector<G1Affine>& points) {
+  return fft_points(ctx, dom, points, 1);
+}
+
 }  // namespace mi355

@@ -213,6 +213,12 @@ pub mod sys {
                                                              flags: c_uint) -> Error;
         pub fn mi355_msm_domain_divide_by_vanishing_on_coset_device(d: *mut c_void, d_out: *mut c_void, d_in: *const c_void, n: usize,
                                                                     offset: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
+        // the same four transforms on a vector of curve points (ark-poly's domains over DomainCoeff = G1Projective / G2Projective):
+        // Affine images in and out (flags bit 1: Projective images out), offset: one arkworks Fr image on the host or null
+        pub fn mi355_msm_fft_points(ctx: *mut c_void, domain: *mut c_void, out: *mut c_void, out_stride: usize, input: *const c_void, in_len: usize,
+                                    stride: usize, kind: c_uint, flags: c_uint, offset: *const c_void) -> Error;
+        pub fn mi355_msm_fft_points_device(ctx: *mut c_void, domain: *mut c_void, d_out: *mut c_void, out_stride: usize, d_in: *const c_void,
+                                           in_len: usize, stride: usize, kind: c_uint, flags: c_uint, offset: *const c_void, stream: *mut c_void) -> Error;
     }
 }
 
