@@ -1372,6 +1372,119 @@ int ht_poly_coset_factor(int field, unsigned k, unsigned flags, const uint8_t* o
 }
 }
 
+// ---- prefix scans and the permutation product (scan.hpp): a block's loops run in order, and the chains of launches the engine runs --
+#include "scan.hpp"
+
+template <class FR>
+struct HostScanRun {
+  std::vector<Fr> lds, sc, nv;
+  HostScanRun() : lds(POLY_MAX_TILE), sc(POLY_MAX_LANES), nv(POLY_MAX_LANES) {}
+  template <unsigned OP>
+  void up(const ScanUp& p) {
+    const uint32_t T = 1u << p.s.t.tile_log, lanes = poly_lanes(p.s.t.tile_log);
+    for (uint64_t tile = 0; tile < poly_tiles(p.s.t.n, p.s.t.tile_log); tile++) {
+      for (uint32_t i = 0; i < T; i++) scan_load<FR, OP>(lds[i], p.s, (tile << p.s.t.tile_log) + i);
+      for (uint32_t l = 0; l < lanes; l++) scan_up_lane<FR, OP>(lds.data(), l);
+      for (uint32_t s = 0; (2u << s) <= lanes; s++)
+        for (uint32_t j = 0; j < (lanes >> (s + 1)); j++) scan_up_tree<FR, OP>(lds.data(), s, j);
+      scan_store_m<FR, OP>(p.dst + tile, lds[0]);
+    }
+  }
+  template <unsigned OP>
+  void down(const ScanDown& p) {
+    const uint32_t T = 1u << p.s.t.tile_log, lanes = poly_lanes(p.s.t.tile_log);
+    std::vector<ScanLane> st(lanes);
+    for (uint64_t tile = 0; tile < poly_tiles(p.s.t.n, p.s.t.tile_log); tile++) {
+      for (uint32_t i = 0; i < T; i++) scan_load<FR, OP>(lds[i], p.s, (tile << p.s.t.tile_log) + i);
+      for (uint32_t l = 0; l < lanes; l++) scan_down_lane<FR, OP>(st[l], lds.data(), sc.data(), l);
+      for (uint32_t s = 0; (1u << s) < lanes; s++) {
+        for (uint32_t l = 0; l < lanes; l++) scan_down_step<FR, OP>(nv[l], sc.data(), s, l);
+        for (uint32_t l = 0; l < lanes; l++) sc[l] = nv[l];
+      }
+      for (uint32_t l = 0; l < lanes; l++) scan_down_finish<FR, OP>(st[l], lds.data(), sc.data(), p, tile, lanes, l);
+      for (uint32_t i = 0; i < T; i++) scan_down_store<FR, OP>(lds.data(), p, tile, i);
+    }
+  }
+};
+
+// in_place: the chain runs with dst == src, as a call with out == in does
+template <class FR>
+static int t_scan(uint32_t tile_log, unsigned flags, unsigned op, int in_place, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* total32) {
+  const bool normal = (flags & kScanNormal) != 0, inclusive = (flags & kScanInclusive) != 0;
+  Fr id;
+  if (op == kScanProduct) fr_set<FR>(id, FR::ONE); else fr_zero(id);
+  if (n == 0) {
+    if (total32) poly_scalar_out<FR>(total32, id, normal);
+    return 0;
+  }
+  std::vector<Fr> work(scan_work_elems(n, tile_log));
+  std::vector<uint32_t> src(n * 8), other(in_place ? 0 : n * 8);
+  memcpy(src.data(), in, n * 32);
+  uint32_t* dst = in_place ? src.data() : other.data();
+  HostScanRun<FR> run;
+  const Fr* res = op == kScanProduct ? scan_chain<FR, kScanProduct>(run, dst, src.data(), nullptr, n, normal, inclusive, tile_log, work.data())
+                                     : scan_chain<FR, kScanSum>(run, dst, src.data(), nullptr, n, normal, inclusive, tile_log, work.data());
+  if (total32) poly_scalar_out<FR>(total32, *res, normal);
+  memcpy(out, dst, n * 32);
+  return 0;
+}
+
+template <class FR>
+static int t_scan_permutation(uint32_t k, uint32_t tile_log, unsigned flags, uint32_t m, uint64_t stride, const uint8_t* wires, const uint8_t* sigmas,
+                              const uint8_t* ks, const uint8_t* beta, const uint8_t* gamma, uint8_t* out, uint8_t* total32) {
+  const uint64_t n = (uint64_t)1 << k, span = (m - 1) * stride + n;
+  const bool normal = (flags & kScanNormal) != 0;
+  Fr root;
+  ntt_root<FR>(root, k);
+  std::vector<Fr> wlo, whi;
+  t_ntt_two_level<FR>(wlo, whi, root, k);
+  std::vector<uint32_t> w(span * 8), sg(span * 8), num(n * 8), den(n * 8), dst(n * 8);
+  memcpy(w.data(), wires, span * 32);
+  memcpy(sg.data(), sigmas, span * 32);
+  ScanPerm p{};
+  p.wires = w.data();
+  p.sigmas = sg.data();
+  p.num = num.data();
+  p.den = den.data();
+  p.stride = stride;
+  p.k = k;
+  p.m = m;
+  p.normal = normal ? 1u : 0u;
+  p.w = NttTable{wlo.data(), whi.data()};
+  poly_scalar<FR>(p.beta, beta, normal);
+  poly_scalar<FR>(p.gamma, gamma, normal);
+  for (uint32_t i = 0; i < m; i++) poly_scalar<FR>(p.ks[i], ks + 32 * i, normal);
+  for (uint32_t j = 0; j < n; j++) scan_perm_row<FR>(p, j);
+  std::vector<Fr> iwork(poly_work_elems(n, tile_log)), work(scan_work_elems(n, tile_log));
+  Fr one;
+  fr_set<FR>(one, FR::ONE);
+  HostPolyRun<FR> inv;
+  poly_chain_inverse<FR>(inv, den.data(), den.data(), n, normal, tile_log, one, iwork.data());
+  HostScanRun<FR> run;
+  const Fr* res = scan_chain<FR, kScanProduct>(run, dst.data(), num.data(), den.data(), n, normal, false, tile_log, work.data());
+  if (total32) poly_scalar_out<FR>(total32, *res, normal);
+  memcpy(out, dst.data(), n * 32);
+  return 0;
+}
+
+extern "C" {
+// mi355_msm_domain_scan on the host: op 0 product, 1 sum; flags bit 0 normal form, bit 1 inclusive; total32 may be NULL
+int ht_scan_scan(int field, unsigned tile_log, unsigned flags, unsigned op, int in_place, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* total32) {
+  if (tile_log < POLY_TILE_LOG_MIN || tile_log > POLY_TILE_LOG_MAX || (flags & ~(kScanNormal | kScanInclusive)) || op > kScanSum || n > ((uint64_t)1 << 24) ||
+      (n && (!in || !out)))
+    return -1;
+  return POLY_FIELD(t_scan, tile_log, flags, op, in_place, in, n, out, total32);
+}
+// mi355_msm_domain_permutation_product on the host, for the domain of 2^k rows
+int ht_scan_permutation_product(int field, unsigned k, unsigned tile_log, unsigned flags, unsigned m, uint64_t stride, const uint8_t* wires,
+                                const uint8_t* sigmas, const uint8_t* ks, const uint8_t* beta, const uint8_t* gamma, uint8_t* out, uint8_t* total32) {
+  if (tile_log < POLY_TILE_LOG_MIN || tile_log > POLY_TILE_LOG_MAX || (flags & ~kScanNormal) || k > 16 || m < 1 || m > SCAN_MAX_COLUMNS ||
+      stride < ((uint64_t)1 << k) || stride > ((uint64_t)1 << 20) || !wires || !sigmas || !ks || !beta || !gamma || !out)
+    return -1;
+  return POLY_FIELD(t_scan_permutation, k, tile_log, flags, m, stride, wires, sigmas, ks, beta, gamma, out, total32);
+}
+}
+
 // ---- transforms of vectors of points (group_fft.hpp) with the limb-bound checker armed ------------------------------------------
 // The SAME MSM_HD functions the kernels of kernels_gfft.hip wrap: the index maps, the twiddle exponent, the twiddle and the factor as
 // canonical words, the table of a butterfly's B, the walk and the butterfly; records by fb_host_records, the vector between two

@@ -151,6 +151,10 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_domain_vanishing": [vp, vp, vp, ctypes.c_uint],
         "mi355_msm_domain_divide_by_vanishing_on_coset": [vp, vp, vp, sz, vp, ctypes.c_uint],
         "mi355_msm_domain_divide_by_vanishing_on_coset_device": [vp, vp, vp, sz, vp, ctypes.c_uint, vp],
+        "mi355_msm_domain_scan": [vp, vp, vp, vp, sz, ctypes.c_uint, ctypes.c_uint],
+        "mi355_msm_domain_scan_device": [vp, vp, vp, vp, sz, ctypes.c_uint, ctypes.c_uint, vp],
+        "mi355_msm_domain_permutation_product": [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, ctypes.c_uint],
+        "mi355_msm_domain_permutation_product_device": [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, ctypes.c_uint, vp],
         "mi355_msm_trim": [],
         "mi355_msm_pool_stats": [ctypes.POINTER(ctypes.c_uint64), sz],
     }
@@ -1276,12 +1280,84 @@ class Radix2EvaluationDomain:
         off = None if offset is None else self._scalar(offset, montgomery)
         return self._map("mi355_msm_domain_divide_by_vanishing_on_coset", evals, b, n, out, (off, 0 if montgomery else 1))
 
+    # ---- prefix scans and the permutation product (mi355_msm_domain_scan, _permutation_product) -------------------------------------
+
+    PRODUCT, SUM = 0, 1
+
+    def _scan(self, op, v, inclusive, montgomery, out):
+        (b,), n = self._vectors(v)
+        res, ob = self._out(v, b, out, n)
+        tot = ctypes.create_string_buffer(32)
+        flags = (0 if montgomery else 1) | (2 if inclusive else 0)
+        if b.is_device:
+            _check(self._lib.mi355_msm_domain_scan_device(self.handle, ob.ptr, tot, b.ptr, n, op, flags, b.stream))
+        else:
+            _check(self._lib.mi355_msm_domain_scan(self.handle, ob.ptr, tot, b.ptr, n, op, flags))
+            res = _like_input(v, res, (n, 32))
+        return res, self._scalar_out(tot.raw, montgomery)
+
+    def prefix_product(self, v, inclusive: bool = False, montgomery: bool = True, out=None):
+        """(the running product, the product of all of ``v`` as an integer).  Exclusive by default -- ``out[0] = 1``,
+        ``out[i] = v[0] * .. * v[i-1]``, what a grand product wants; ``inclusive=True``: ``out[i] = v[0] * .. * v[i]``.  Zeros are NOT
+        skipped (unlike ``batch_inversion``): after a zero every later product is zero.  ``out`` may be ``v``."""
+        return self._scan(self.PRODUCT, v, inclusive, montgomery, out)
+
+    def prefix_sum(self, v, inclusive: bool = False, montgomery: bool = True, out=None):
+        """(the running sum, the sum of all of ``v`` as an integer): ``out[0] = 0``, ``out[i] = v[0] + .. + v[i-1]``, or with
+        ``inclusive=True`` up to ``v[i]``.  ``out`` may be ``v``."""
+        return self._scan(self.SUM, v, inclusive, montgomery, out)
+
+    def _columns(self, cols, what):
+        """(buffer, m, stride in elements) of the m columns of ``size`` elements: a (m, size, 32) array or tensor, or a list of m vectors"""
+        if isinstance(cols, (list, tuple)):
+            first = cols[0] if len(cols) else None
+            if hasattr(first, "is_cuda") and hasattr(first, "data_ptr"):
+                import torch
+
+                cols = torch.stack([c.reshape(-1, 32) for c in cols])
+            else:
+                import numpy as np
+
+                cols = np.stack([np.frombuffer(_flat_bytes(c), dtype=np.uint8).reshape(-1, 32) for c in cols]) if len(cols) else np.zeros((0, self.size, 32), np.uint8)
+        shape = tuple(getattr(cols, "shape", ()))
+        if len(shape) != 3 or shape[1] != self.size or shape[2] != 32 or not 1 <= shape[0] <= 8:
+            raise ValueError(f"{what}: m columns (1 <= m <= 8) of {self.size} 32-byte elements, shape (m, {self.size}, 32), not {shape}")
+        return _Buf(cols), int(shape[0]), self.size
+
+    def permutation_product(self, wires, sigmas, beta: int, gamma: int, ks, montgomery: bool = True, out=None):
+        """The Plonk permutation grand product over the ``size`` rows of the domain: ``z[0] = 1``,
+        ``z[j+1] = z[j] * prod_i (w_i[j] + beta ks[i] omega^j + gamma) / prod_i (w_i[j] + beta sigma_i[j] + gamma)``.  Returns
+        ``(z, total)``: the ``size`` values of ``z`` (ready for ``ifft``) and ``total = z[size-1] * f[size-1]`` as an integer, which is 1
+        exactly when the copy constraints hold.  ``wires`` and ``sigmas``: a ``(m, size, 32)`` array or tensor, or a list of ``m``
+        vectors; ``ks``: the ``m`` coset representatives as integers.  A zero denominator does not raise: that row's factor is 0 and
+        so are all later values of ``z`` and ``total``.  ``out`` must not overlap the inputs."""
+        if not self.handle:
+            raise MsmError(-1, "the domain is closed")
+        bw, m, stride = self._columns(wires, "wires")
+        bs, ms, _ = self._columns(sigmas, "sigmas")
+        ks = [int(k) for k in ks]
+        if ms != m or len(ks) != m or bw.is_device != bs.is_device:
+            raise ValueError("wires, sigmas and ks must agree in the number of columns, and wires and sigmas in the kind of memory")
+        for b in (bw, bs):
+            if b.is_device and b.device_index != self.device:
+                raise MsmError(-1, f"the input lives on cuda:{b.device_index} but this domain is bound to device {self.device}")
+        res, ob = self._out(wires, bw, out, self.size)
+        tot = ctypes.create_string_buffer(32)
+        kb = b"".join(self._scalar(k, montgomery) for k in ks)
+        bb, gb, flags = self._scalar(beta, montgomery), self._scalar(gamma, montgomery), 0 if montgomery else 1
+        if bw.is_device:
+            _check(self._lib.mi355_msm_domain_permutation_product_device(self.handle, ob.ptr, tot, bw.ptr, bs.ptr, m, stride, kb, bb, gb, flags, bw.stream))
+        else:
+            _check(self._lib.mi355_msm_domain_permutation_product(self.handle, ob.ptr, tot, bw.ptr, bs.ptr, m, stride, kb, bb, gb, flags))
+            res = res.reshape(self.size, 32) if isinstance(wires, (list, tuple)) else _like_input(wires, res, (self.size, 32))
+        return res, self._scalar_out(tot.raw, montgomery)
+
     def set_option(self, key: str, value: int) -> None:
         _check(self._lib.mi355_msm_domain_set_option(self.handle, key.encode(), int(value)))
 
     def query(self, key: str) -> int:
-        """ "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "poly_tile_log", "device", "last_us",
-        "last_device_us" """
+        """ "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "scan_work_bytes", "poly_tile_log",
+        "device", "last_us", "last_device_us" """
         v = ctypes.c_uint64(0)
         _check(self._lib.mi355_msm_domain_query(self.handle, key.encode(), ctypes.byref(v)))
         return int(v.value)

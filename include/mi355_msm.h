@@ -459,7 +459,7 @@ RustError mi355_msm_mul_points_device(mi355_msm_ctx* ctx, const void* d_points, 
  * input becomes ready (NULL = the default stream): the work is enqueued there and the call returns when the output is written.
  * Option "pass_log" 1..10 (0 restores the default, 8): butterfly levels per pass -- a test hook.  Results never depend on it, nor on
  * host versus device pointers, nor on batching.
- * Queries: "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "poly_tile_log", "device", "last_us" (host clock around the most recent
+ * Queries: "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "scan_work_bytes", "poly_tile_log", "device", "last_us" (host clock around the most recent
  * call), "last_device_us" (the same call between events on the stream it ran on).
  * Errors: -1 with a message for null pointers, in_len > n, a partial overlap, unknown or misplaced flag bits, an unknown kind, an offset
  * on a plain transform, a size above the limits -- decided before any device call; hipErrorNoDevice without a GPU. */
@@ -531,6 +531,45 @@ RustError mi355_msm_domain_divide_by_vanishing_on_coset(mi355_msm_domain* d, voi
                                                         unsigned flags);
 RustError mi355_msm_domain_divide_by_vanishing_on_coset_device(mi355_msm_domain* d, void* d_out, const void* d_in, size_t n, const void* offset,
                                                                unsigned flags, void* stream);
+
+/* ---- prefix scans along a vector of Fr and the Plonk permutation grand product -----------------------------------------------------------
+ * What a Plonk prover's second round needs between the wires and ifft + MSM: z[0] = 1,
+ * z[j+1] = z[j] * prod_i (w_i[j] + beta k_i omega^j + gamma) / prod_i (w_i[j] + beta sigma_i[j] + gamma); and, with the sum, the running
+ * sum of logUp / lookup arguments.  The calls live on the domain handle and follow the conventions of the calls above: 32-byte
+ * elements, arkworks Fr images or, with flag bit 0, plain integers; ANY 256-bit input is read as its residue and every output is
+ * canonical; host pointers without _device, device pointers (4-byte aligned) and a stream with it; total32, ks, beta and gamma are HOST
+ * elements in the form of the call, also in the _device calls.
+ *   scan            op 0: the product (identity 1); op 1: the sum (identity 0).  Exclusive by default: out[0] = identity,
+ *                   out[i] = in[0] o .. o in[i-1]; flag bit 1: inclusive, out[i] = in[0] o .. o in[i].  total32 (may be NULL) = the
+ *                   combination of all n inputs; n = 0 writes the identity there and nothing else.  n is any length up to 2^30 and has
+ *                   nothing to do with the domain's size.  out == in is allowed; any other overlap is refused.
+ *                   ZEROS ARE NOT SKIPPED: after an input that is 0 modulo r every later product is 0.  (batch_inverse skips zeros,
+ *                   as arkworks does; a scan has no such habit to follow.)
+ *   permutation_product  n = the size of the handle.  wires and sigmas hold m columns (1 <= m <= 8) of n elements, `stride` >= n
+ *                   elements apart; ks: the m coset representatives.  The identity permutation's value of cell (i, j) is
+ *                   ks[i] * omega^j, taken from the handle's tables: no id vector is passed.  With f[j] = the quotient above,
+ *                   out[0] = 1, out[j] = prod_(t<j) f[t] (n elements) and total32 (may be NULL) = out[n-1] * f[n-1], which is 1 exactly
+ *                   when the copy constraints hold.  out may not overlap the inputs.  Flag bit 0 is the only flag.
+ *                   A ZERO DENOMINATOR IS NOT AN ERROR: the batch inversion leaves it zero, so f[j] = 0 and every later out[] and
+ *                   total32 are 0.
+ * Scheme (csrc/scan.hpp): the tiles of the calls above.  Way up: one total per tile (the lane's run, then a tree); the vector of totals
+ * is scanned the same way (three levels at 2^30); way down: every tile is read again, a Hillis-Steele scan runs over its 256 lane
+ * totals, the carry that enters the tile is folded in and the tile is stored.  The permutation product is one kernel for the m-fold
+ * numerators and denominators, the three launches of the batch inversion on the denominators, and the product scan, whose load
+ * multiplies the two.  Levels are separate launches on one stream: no block waits on another, nothing is atomic.
+ * Work memory is allocated on the first such call and kept by the handle: query "scan_work_bytes" ("work_bytes" and "poly_work_bytes"
+ * keep their meaning and their values).  Results never depend on "poly_tile_log", on host versus device pointers or on `stride`.
+ * Errors: -1 with a message for unknown flag bits, n above 2^30, an unknown op, m outside 1..8, null pointers, a partial overlap, a stride
+ * of 0 and, last, a null handle -- decided before any device call; a stride below n and an output that overlaps the columns are judged
+ * against the handle's size. */
+RustError mi355_msm_domain_scan(mi355_msm_domain* d, void* out, void* total32, const void* in, size_t n, unsigned op, unsigned flags);
+RustError mi355_msm_domain_scan_device(mi355_msm_domain* d, void* d_out, void* total32, const void* d_in, size_t n, unsigned op, unsigned flags,
+                                       void* stream);
+RustError mi355_msm_domain_permutation_product(mi355_msm_domain* d, void* out, void* total32, const void* wires, const void* sigmas, size_t m,
+                                               size_t stride, const void* ks, const void* beta, const void* gamma, unsigned flags);
+RustError mi355_msm_domain_permutation_product_device(mi355_msm_domain* d, void* d_out, void* total32, const void* d_wires, const void* d_sigmas,
+                                                      size_t m, size_t stride, const void* ks, const void* beta, const void* gamma, unsigned flags,
+                                                      void* stream);
 
 /* ---- transforms of vectors of curve points over a domain (ARK poly/src/domain/mod.rs:99-170 on DomainCoeff = G1Projective / G2Projective) ----
  * domain.fft / ifft / coset_fft / coset_ifft on GROUP elements: what turns a monomial SRS [tau^j] G into the Lagrange SRS

@@ -352,6 +352,27 @@ struct Radix2EvaluationDomain {
     check(mi355_msm_domain_divide_by_vanishing_on_coset(handle, out.data(), evals.data(), evals.size(), offset, 0));
     return out;
   }
+  // the running product (op 0) or sum (op 1): exclusive unless `inclusive`; zeros are not skipped; *total = the combination of all of v
+  std::vector<BigInteger256> scan(unsigned op, const std::vector<BigInteger256>& v, bool inclusive = false, BigInteger256* total = nullptr) const {
+    std::vector<BigInteger256> out(v.size());
+    check(mi355_msm_domain_scan(handle, out.data(), total, v.data(), v.size(), op, inclusive ? 2u : 0u));
+    return out;
+  }
+  std::vector<BigInteger256> prefix_product(const std::vector<BigInteger256>& v, bool inclusive = false, BigInteger256* total = nullptr) const {
+    return scan(0, v, inclusive, total);
+  }
+  std::vector<BigInteger256> prefix_sum(const std::vector<BigInteger256>& v, bool inclusive = false, BigInteger256* total = nullptr) const {
+    return scan(1, v, inclusive, total);
+  }
+  // the Plonk permutation grand product z over the size() rows: wires and sigmas hold ks.size() columns `stride` >= size() elements
+  // apart; *total = z[n-1] f[n-1], 1 exactly when the copy constraints hold.  A zero denominator zeroes the rest of z and *total.
+  std::vector<BigInteger256> permutation_product(const std::vector<BigInteger256>& wires, const std::vector<BigInteger256>& sigmas, size_t stride,
+                                                 const std::vector<BigInteger256>& ks, const BigInteger256& beta, const BigInteger256& gamma,
+                                                 BigInteger256* total = nullptr) const {
+    std::vector<BigInteger256> out(size());
+    check(mi355_msm_domain_permutation_product(handle, out.data(), total, wires.data(), sigmas.data(), ks.size(), stride, ks.data(), &beta, &gamma, 0));
+    return out;
+  }
   ~Radix2EvaluationDomain() {
     if (handle) {
       RustError e = mi355_msm_domain_destroy(handle);

@@ -213,6 +213,19 @@ pub mod sys {
                                                              flags: c_uint) -> Error;
         pub fn mi355_msm_domain_divide_by_vanishing_on_coset_device(d: *mut c_void, d_out: *mut c_void, d_in: *const c_void, n: usize,
                                                                     offset: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
+        // prefix scans (op 0 product, 1 sum; flags bit 0 = plain integers, bit 1 = inclusive; zeros are not skipped) and the Plonk
+        // permutation grand product over the rows of the domain (m columns `stride` elements apart; a zero denominator zeroes the rest);
+        // total32, ks, beta and gamma are HOST elements
+        pub fn mi355_msm_domain_scan(d: *mut c_void, out: *mut c_void, total32: *mut c_void, input: *const c_void, n: usize, op: c_uint,
+                                     flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_scan_device(d: *mut c_void, d_out: *mut c_void, total32: *mut c_void, d_in: *const c_void, n: usize, op: c_uint,
+                                            flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_permutation_product(d: *mut c_void, out: *mut c_void, total32: *mut c_void, wires: *const c_void,
+                                                    sigmas: *const c_void, m: usize, stride: usize, ks: *const c_void, beta: *const c_void,
+                                                    gamma: *const c_void, flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_permutation_product_device(d: *mut c_void, d_out: *mut c_void, total32: *mut c_void, d_wires: *const c_void,
+                                                           d_sigmas: *const c_void, m: usize, stride: usize, ks: *const c_void,
+                                                           beta: *const c_void, gamma: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
         // the same four transforms on a vector of curve points (ark-poly's domains over DomainCoeff = G1Projective / G2Projective):
         // Affine images in and out (flags bit 1: Projective images out), offset: one arkworks Fr image on the host or null
         pub fn mi355_msm_fft_points(ctx: *mut c_void, domain: *mut c_void, out: *mut c_void, out_stride: usize, input: *const c_void, in_len: usize,

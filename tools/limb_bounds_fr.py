@@ -18,6 +18,7 @@ All margins must be positive (tests/test_fr_consts.py runs it); the host build c
 
     python tools/limb_bounds_fr.py
     python tools/limb_bounds_fr.py --poly     (the chains of csrc/poly.hpp: analyse_poly below)
+    python tools/limb_bounds_fr.py --scan     (the sum scan and the permutation product of csrc/scan.hpp: analyse_scan below)
 """
 import sys
 
@@ -160,8 +161,79 @@ def analyse_poly(name, r, out):
     return ok
 
 
+def analyse_scan(name, r, out):
+    """The chains of csrc/scan.hpp (python tools/limb_bounds_fr.py --scan).  The product scan multiplies class-M values only.  The sum
+    scan adds limb-wise with one carry pass per step: a lane's run of four class-M elements, then tree or Hillis-Steele steps that
+    each double the bound, with one product by 1 after every odd step; an offset (the carry into the tile plus a scan value) meets a
+    prefix of the lane's run, and the result is converted.  The factors of the permutation product are sums of three, not carried."""
+    import math
+
+    rl = limbs(r)
+    ok = True
+
+    def margin(what, have, limit):
+        nonlocal ok
+        m = limit - have
+        ok &= m > 0
+        out.append("  %-74s %s (limit 2^%.2f, margin %.3e)" % (what, "ok " if m > 0 else "BAD", math.log2(limit), m))
+
+    top_m = (2 * r) >> (B * (N - 1))
+    class_m = [MASK] * (N - 1) + [top_m]
+    w = [MASK] * (N - 1) + [rl[N - 1]]
+
+    def first_operand(what, l, val, second):
+        margin(what + ": value %dr against R" % val, val * r, R)
+        margin(what + ": largest limb against 2^31", max(l), 1 << 31)
+        margin(what + ": largest column against 2^64", max(columns(l, second, rl)), 1 << 64)
+        sec_val = 2 * r if second is class_m else r
+        margin(what + ": product r + a b / R against 2r", r + val * r * sec_val // R + 1, 2 * r)
+
+    def add(what, a, b):
+        sm = [x + y for x, y in zip(a, b)]
+        margin(what + ": limb-wise sum against 2^32", max(sm), 1 << 32)
+        margin(what + ": top limb into the carry pass against 2^31", sm[N - 1] + (sm[N - 2] >> B), 1 << 31)
+        return carry_pass(sm)
+
+    out.append("%s: r = %.3f * 2^252, R / r = %.2f  (the chains of scan.hpp)" % (name, r / 2**252, R / r))
+    margin("second operand: limbs of a class-M value against 2^29 + 8", max(class_m), (1 << B) + 8)
+    first_operand("product scan: class-M by class-M, to any depth", class_m, 2, class_m)
+    # the lane's run: three sums of a running value and a class-M element; prefix[j] is what the way down keeps
+    run_l, run_v = list(class_m), 2
+    for j in range(1, 4):
+        run_l = add("sum scan, lane run element %d" % j, run_l, class_m)
+        run_v += 2
+    # tree (way up) and Hillis-Steele (way down) steps: both operands carry the bound of the step before
+    a_l, a_v = run_l, run_v
+    worst_l, worst_v = a_l, a_v
+    for s in range(POLY_SCAN_LEVELS):
+        a_l = add("sum scan step %d" % s, a_l, a_l)
+        a_v *= 2
+        if s & 1:
+            first_operand("sum scan step %d: the product by 1 of an odd step" % s, a_l, a_v, w)
+            a_l, a_v = list(class_m), 2
+        if a_v > worst_v:
+            worst_l, worst_v = a_l, a_v
+        worst_l = [max(x, y) for x, y in zip(worst_l, a_l)]
+    # what the scan leaves after any number of steps, as the tile total (a product by 1) and as the lane to the left
+    first_operand("sum scan: a total brought to class M", worst_l, worst_v, w)
+    off_l = add("sum scan offset: carry into the tile + scan value", class_m, worst_l)
+    off_v = 2 + worst_v
+    y_l = add("sum scan output: offset + prefix of the run", off_l, run_l)
+    first_operand("sum scan output as the first operand of the conversion", y_l, off_v + run_v, w)
+    # the permutation product: (w + gamma) + beta * id, two class-M values and a canonical one, no carry pass
+    t = [class_m[i] + class_m[i] + w[i] for i in range(N)]
+    margin("permutation product factor: limb-wise sum against 2^32", max(t), 1 << 32)
+    first_operand("permutation product factor w + beta id + gamma times the running product", t, 5, class_m)
+    return ok
+
+
 def main():
     out = []
+    if "--scan" in sys.argv[1:]:
+        ok = all([analyse_scan(name, r, out) for name, r in FIELDS.items()])
+        print("\n".join(out))
+        print("all margins positive" if ok else "A MARGIN IS NOT POSITIVE")
+        return 0 if ok else 1
     if "--poly" in sys.argv[1:]:
         ok = all([analyse_poly(name, r, out) for name, r in FIELDS.items()])
         print("\n".join(out))
