@@ -1485,6 +1485,113 @@ int ht_scan_permutation_product(int field, unsigned k, unsigned tile_log, unsign
 }
 }
 
+// ---- the rows of the Plonk quotient and the linear combination (quotient.hpp): every row in order, and the chain of launches the
+// engine runs ------------------------------------------------------------------------------------------------------------------------
+#include "quotient.hpp"
+
+template <class FR>
+struct HostQuotRun : HostPolyRun<FR> {
+  void xm1(const QuotXm1& p) {
+    for (uint32_t i = 0; (i >> p.k) == 0; i++) quot_xm1_row<FR>(p, i);
+  }
+  void rows(const QuotRows& p) {
+    for (uint32_t i = 0; (i >> p.k) == 0; i++) quot_row<FR>(p, i);
+  }
+};
+
+// -1: refused as the engine refuses it (the offset is zero, or its n-th power is a root of unity of order `ratio`)
+template <class FR>
+static int t_quotient_rows(uint32_t k, uint32_t log_n, uint32_t tile_log, unsigned flags, uint32_t m, uint64_t stride, const uint8_t* wires,
+                           const uint8_t* sigmas, const uint8_t* selectors, const uint8_t* z, const uint8_t* pi, const uint8_t* ks, const uint8_t* alpha,
+                           const uint8_t* beta, const uint8_t* gamma, const uint8_t* offset, uint8_t* out) {
+  const uint64_t M = (uint64_t)1 << k, span = (m - 1) * stride + M, sel_span = (QUOT_SELECTORS - 1) * stride + M;
+  const bool normal = (flags & kQuotNormal) != 0;
+  Fr root, zero, al, a2n;
+  fr_zero(zero);
+  ntt_root<FR>(root, k);
+  std::vector<Fr> wlo, whi;
+  t_ntt_two_level<FR>(wlo, whi, root, k);
+  std::vector<uint32_t> w(span * 8), sg(span * 8), sel(selectors ? sel_span * 8 : 0), zz(M * 8), pp(pi ? M * 8 : 0), dst(M * 8);
+  memcpy(w.data(), wires, span * 32);
+  memcpy(sg.data(), sigmas, span * 32);
+  if (selectors) memcpy(sel.data(), selectors, sel_span * 32);
+  memcpy(zz.data(), z, M * 32);
+  if (pi) memcpy(pp.data(), pi, M * 32);
+  QuotRows p{};
+  p.wires = w.data();
+  p.sigmas = sg.data();
+  p.selectors = selectors ? sel.data() : nullptr;
+  p.z = zz.data();
+  p.pi = pi ? pp.data() : nullptr;
+  p.dst = dst.data();
+  p.stride = stride;
+  p.k = k;
+  p.m = m;
+  p.ratio = 1u << (k - log_n);
+  quot_form<FR>(p.cin, p.cout, normal);
+  p.w = NttTable{wlo.data(), whi.data()};
+  if (offset) poly_scalar<FR>(p.g, offset, normal); else fr_set<FR>(p.g, FR::GENERATOR);
+  if (memcmp(p.g.v, zero.v, sizeof zero.v) == 0) return -1;
+  poly_scalar<FR>(al, alpha, normal);
+  poly_scalar<FR>(p.beta, beta, normal);
+  poly_scalar<FR>(p.gamma, gamma, normal);
+  for (uint32_t j = 0; j < m; j++) poly_scalar<FR>(p.bks[j], ks + 32 * j, normal);
+  if (!quot_constants<FR>(p, a2n, al, log_n)) return -1;
+  std::vector<Fr> work(quot_work_elems(M, tile_log));
+  HostQuotRun<FR> run;
+  quot_chain<FR>(run, p, a2n, tile_log, work.data());
+  memcpy(out, dst.data(), M * 32);
+  return 0;
+}
+
+// in_place: the output is column 0, as a call with out == cols[0] has it
+template <class FR>
+static int t_linear_combination(unsigned flags, uint32_t m, const uint8_t* const* cols, const uint64_t* lens, const uint8_t* coeffs, int in_place,
+                                uint8_t* out) {
+  LinComb p{};
+  std::vector<std::vector<uint32_t>> v(m);
+  uint64_t n = 0;
+  for (uint32_t j = 0; j < m; j++) n = lens[j] > n ? lens[j] : n;
+  if (n == 0) return 0;
+  for (uint32_t j = 0; j < m; j++) {
+    v[j].resize((in_place && j == 0 ? n : lens[j]) * 8 + 8);
+    if (lens[j]) memcpy(v[j].data(), cols[j], lens[j] * 32);
+    p.cols[j] = v[j].data();
+    p.lens[j] = (uint32_t)lens[j];
+    poly_scalar<FR>(p.coeffs[j], coeffs + 32 * j, (flags & kQuotNormal) != 0);
+  }
+  std::vector<uint32_t> dst(n * 8);
+  p.dst = in_place ? v[0].data() : dst.data();
+  p.n = (uint32_t)n;
+  p.m = m;
+  quot_form<FR>(p.cin, p.cout, (flags & kQuotNormal) != 0);
+  for (uint32_t i = 0; i < p.n; i++) lincomb_elem<FR>(p, i);
+  memcpy(out, p.dst, n * 32);
+  return 0;
+}
+
+extern "C" {
+// mi355_msm_domain_plonk_quotient on the host, for the quotient domain of 2^k points over a constraint domain of 2^log_n rows;
+// selectors, pi and offset may be NULL
+int ht_quotient_rows(int field, unsigned k, unsigned log_n, unsigned tile_log, unsigned flags, unsigned m, uint64_t stride, const uint8_t* wires,
+                     const uint8_t* sigmas, const uint8_t* selectors, const uint8_t* z, const uint8_t* pi, const uint8_t* ks, const uint8_t* alpha,
+                     const uint8_t* beta, const uint8_t* gamma, const uint8_t* offset, uint8_t* out) {
+  if (tile_log < POLY_TILE_LOG_MIN || tile_log > POLY_TILE_LOG_MAX || (flags & ~kQuotNormal) || k > 16 || log_n >= k || k - log_n > 4 || log_n == 0 ||
+      (selectors ? m != QUOT_GATE_WIRES : (m < 1 || m > QUOT_MAX_COLUMNS)) || stride < ((uint64_t)1 << k) || stride > ((uint64_t)1 << 20) || !wires ||
+      !sigmas || !z || !ks || !alpha || !beta || !gamma || !out)
+    return -1;
+  return POLY_FIELD(t_quotient_rows, k, log_n, tile_log, flags, m, stride, wires, sigmas, selectors, z, pi, ks, alpha, beta, gamma, offset, out);
+}
+// mi355_msm_domain_linear_combination on the host
+int ht_quotient_linear_combination(int field, unsigned flags, unsigned m, const uint8_t* const* cols, const uint64_t* lens, const uint8_t* coeffs,
+                                   int in_place, uint8_t* out) {
+  if ((flags & ~kQuotNormal) || m < 1 || m > LINCOMB_MAX_COLUMNS || !cols || !lens || !coeffs || !out) return -1;
+  for (unsigned j = 0; j < m; j++)
+    if (lens[j] > ((uint64_t)1 << 24) || (lens[j] && !cols[j])) return -1;
+  return POLY_FIELD(t_linear_combination, flags, m, cols, lens, coeffs, in_place, out);
+}
+}
+
 // ---- transforms of vectors of points (group_fft.hpp) with the limb-bound checker armed ------------------------------------------
 // The SAME MSM_HD functions the kernels of kernels_gfft.hip wrap: the index maps, the twiddle exponent, the twiddle and the factor as
 // canonical words, the table of a butterfly's B, the walk and the butterfly; records by fb_host_records, the vector between two

@@ -2783,4 +2783,5 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 #include "msm_ntt.hpp"
 #include "msm_poly.hpp"
 #include "msm_scan.hpp"
+#include "msm_quot.hpp"
 #include "msm_gfft.hpp"

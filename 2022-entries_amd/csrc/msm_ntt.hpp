@@ -21,6 +21,7 @@ struct mi355_msm_domain {
   DevBuf poly, pstage;    // msm_poly.hpp: the partial vectors of the scans; the staged vectors of its host-pointer calls
   uint32_t poly_tile_log = POLY_DEFAULT_TILE_LOG;
   DevBuf scan, sstage;    // msm_scan.hpp: the levels of the scans and the rows of the permutation product; the staged vectors of its host-pointer calls
+  DevBuf quot, qstage;    // msm_quot.hpp: x - 1 per row, its inverses and their tile products; the staged vectors of its host-pointer calls
   Fr size_inv{};
   Fr g_have{};            // the (inverted, for the inverse kinds) offset the offset tables hold
   bool g_valid = false;
@@ -61,7 +62,7 @@ void with_fr(int curve, Fn&& fn) {
 }
 
 void domain_release(mi355_msm_domain* d) {
-  for (DevBuf* b : {&d->tables, &d->work, &d->stage, &d->poly, &d->pstage, &d->scan, &d->sstage}) b->release();
+  for (DevBuf* b : {&d->tables, &d->work, &d->stage, &d->poly, &d->pstage, &d->scan, &d->sstage, &d->quot, &d->qstage}) b->release();
   for (hipEvent_t& e : d->ev)
     if (e) { (void)hipEventDestroy(e); e = nullptr; }
   if (d->own_stream) { (void)hipStreamDestroy(d->own_stream); d->own_stream = nullptr; }
@@ -375,6 +376,7 @@ RustError mi355_msm_domain_query(mi355_msm_domain* d, const char* key, uint64_t*
     else if (k == "work_bytes") *value = d->work.bytes + d->stage.bytes;
     else if (k == "poly_work_bytes") *value = d->poly.bytes + d->pstage.bytes;
     else if (k == "scan_work_bytes") *value = d->scan.bytes + d->sstage.bytes;
+    else if (k == "quotient_work_bytes") *value = d->quot.bytes + d->qstage.bytes;
     else if (k == "poly_tile_log") *value = d->poly_tile_log;
     else if (k == "device") *value = (uint64_t)d->device;
     else if (k == "last_us") *value = d->last_us;

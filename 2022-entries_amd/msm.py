@@ -155,6 +155,10 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_domain_scan_device": [vp, vp, vp, vp, sz, ctypes.c_uint, ctypes.c_uint, vp],
         "mi355_msm_domain_permutation_product": [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, ctypes.c_uint],
         "mi355_msm_domain_permutation_product_device": [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, ctypes.c_uint, vp],
+        "mi355_msm_domain_plonk_quotient": [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, ctypes.c_uint],
+        "mi355_msm_domain_plonk_quotient_device": [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, ctypes.c_uint, vp],
+        "mi355_msm_domain_linear_combination": [vp, vp, vp, vp, vp, sz, ctypes.c_uint],
+        "mi355_msm_domain_linear_combination_device": [vp, vp, vp, vp, vp, sz, ctypes.c_uint, vp],
         "mi355_msm_trim": [],
         "mi355_msm_pool_stats": [ctypes.POINTER(ctypes.c_uint64), sz],
     }
@@ -1307,8 +1311,9 @@ class Radix2EvaluationDomain:
         ``inclusive=True`` up to ``v[i]``.  ``out`` may be ``v``."""
         return self._scan(self.SUM, v, inclusive, montgomery, out)
 
-    def _columns(self, cols, what):
-        """(buffer, m, stride in elements) of the m columns of ``size`` elements: a (m, size, 32) array or tensor, or a list of m vectors"""
+    def _columns(self, cols, what, most: int = 8, strided: bool = False):
+        """(buffer, m, stride in elements) of the m columns of ``size`` elements: a (m, size, 32) array or tensor, or a list of m
+        vectors; ``strided``: an array or tensor may hold its columns further apart, (m, stride, 32) with ``stride >= size``"""
         if isinstance(cols, (list, tuple)):
             first = cols[0] if len(cols) else None
             if hasattr(first, "is_cuda") and hasattr(first, "data_ptr"):
@@ -1320,9 +1325,9 @@ class Radix2EvaluationDomain:
 
                 cols = np.stack([np.frombuffer(_flat_bytes(c), dtype=np.uint8).reshape(-1, 32) for c in cols]) if len(cols) else np.zeros((0, self.size, 32), np.uint8)
         shape = tuple(getattr(cols, "shape", ()))
-        if len(shape) != 3 or shape[1] != self.size or shape[2] != 32 or not 1 <= shape[0] <= 8:
-            raise ValueError(f"{what}: m columns (1 <= m <= 8) of {self.size} 32-byte elements, shape (m, {self.size}, 32), not {shape}")
-        return _Buf(cols), int(shape[0]), self.size
+        if len(shape) != 3 or shape[2] != 32 or not 1 <= shape[0] <= most or (shape[1] < self.size if strided else shape[1] != self.size):
+            raise ValueError(f"{what}: m columns (1 <= m <= {most}) of {self.size} 32-byte elements, shape (m, {self.size}, 32), not {shape}")
+        return _Buf(cols), int(shape[0]), int(shape[1])
 
     def permutation_product(self, wires, sigmas, beta: int, gamma: int, ks, montgomery: bool = True, out=None):
         """The Plonk permutation grand product over the ``size`` rows of the domain: ``z[0] = 1``,
@@ -1352,11 +1357,98 @@ class Radix2EvaluationDomain:
             res = res.reshape(self.size, 32) if isinstance(wires, (list, tuple)) else _like_input(wires, res, (self.size, 32))
         return res, self._scalar_out(tot.raw, montgomery)
 
+    # ---- the rows of the Plonk quotient and linear combinations (mi355_msm_domain_plonk_quotient, _linear_combination) -------------
+
+    def plonk_quotient(self, wires, sigmas, z, alpha: int, beta: int, gamma: int, ks, n: int, selectors=None, pi=None, offset=None,
+                       montgomery: bool = True, out=None):
+        """The row loop of a TurboPlonk prover's third round on THIS domain as the quotient domain (``size = M``): all vectors hold the
+        ``M`` evaluations on ``offset * H_M`` that ``coset_fft`` writes, ``n`` is the size of the constraint domain (``M / n`` in 2, 4,
+        8, 16).  With ``x = offset * omega^i``::
+
+            gate    = q_c + pi + sum_j q_lc[j] w_j + q_mul[0] w0 w1 + q_mul[1] w2 w3 + q_ecc w0 w1 w2 w3 w4 + sum_j q_hash[j] w_j^5 - q_o w4
+            out[i]  = (gate + alpha (z[i] prod_j (w_j + beta ks[j] x + gamma) - z[i + M/n] prod_j (w_j + beta sigma_j + gamma))) / (x^n - 1)
+                      + alpha^2 (z[i] - 1) / (n (x - 1))
+
+        ``wires`` and ``sigmas``: ``(m, stride, 32)`` arrays or tensors with ``stride >= M``, or lists of ``m`` vectors; ``selectors``:
+        the same with the 13 columns ``q_lc[0..3], q_mul[0..1], q_hash[0..3], q_o, q_c, q_ecc`` (then ``m == 5``), or None: the gate
+        is ``pi`` alone (``1 <= m <= 8``), for a prover that brings its own gate evaluations.  ``pi`` None: 0.  ``offset`` None: the
+        field's GENERATOR; one whose ``n``-th power is a ``M/n``-th root of unity is refused.  ``out`` must not overlap any input.
+        Returns the ``M`` values, ready for ``coset_ifft``."""
+        if not self.handle:
+            raise MsmError(-1, "the domain is closed")
+        bw, m, stride = self._columns(wires, "wires", strided=True)
+        bs, ms, sstride = self._columns(sigmas, "sigmas", strided=True)
+        ks = [int(k) for k in ks]
+        if ms != m or len(ks) != m or sstride != stride:
+            raise ValueError("wires, sigmas and ks must agree in the number of columns, and wires and sigmas in the stride")
+        bufs = [bw, bs]
+        bq = None
+        if selectors is not None:
+            bq, mq, qstride = self._columns(selectors, "selectors", most=13, strided=True)
+            if mq != 13 or m != 5 or qstride != stride:
+                raise ValueError("selectors: 13 columns with the stride of the wires, beside 5 columns of wires")
+            bufs.append(bq)
+        (bz,), nz = self._vectors(z)
+        bp = None
+        if pi is not None:
+            (bp,), npi = self._vectors(pi)
+            if npi != nz:
+                raise ValueError("z and pi must hold the same number of 32-byte elements")
+            bufs.append(bp)
+        if nz != self.size:
+            raise ValueError(f"z: {self.size} 32-byte elements, not {nz}")
+        for b in bufs:
+            if b.is_device != bz.is_device:
+                raise ValueError("all vectors must live in the same kind of memory")
+            if b.is_device and b.device_index != self.device:
+                raise MsmError(-1, f"the input lives on cuda:{b.device_index} but this domain is bound to device {self.device}")
+        res, ob = self._out(z, bz, out, self.size)
+        kb = b"".join(self._scalar(k, montgomery) for k in ks)
+        ab, bb, gb = (self._scalar(v, montgomery) for v in (alpha, beta, gamma))
+        off, flags = self._offset(offset, montgomery), 0 if montgomery else 1
+        ptrs = (ob.ptr, bw.ptr, bs.ptr, bq.ptr if bq else None, bz.ptr, bp.ptr if bp else None)
+        if bz.is_device:
+            _check(self._lib.mi355_msm_domain_plonk_quotient_device(self.handle, *ptrs, m, stride, int(n), kb, ab, bb, gb, off, flags, bz.stream))
+            return res
+        _check(self._lib.mi355_msm_domain_plonk_quotient(self.handle, *ptrs, m, stride, int(n), kb, ab, bb, gb, off, flags))
+        return _like_input(z, res, (self.size, 32))
+
+    def linear_combination(self, cols, coeffs, montgomery: bool = True, out=None):
+        """``out[i] = sum_j coeffs[j] * cols[j][i]`` for ``i < max(len(cols[j]))``: a list of 1 .. 32 vectors of any lengths (a vector
+        contributes 0 past its end) and as many integers -- a linearisation or a batched opening polynomial in one pass.  ``out`` may
+        be one of the vectors (the longest).  The length has nothing to do with the domain's size."""
+        if not self.handle:
+            raise MsmError(-1, "the domain is closed")
+        cols, coeffs = list(cols), [int(c) for c in coeffs]
+        if not 1 <= len(cols) <= 32 or len(coeffs) != len(cols):
+            raise ValueError("cols: 1 .. 32 columns, and as many coefficients")
+        bufs = [_Buf(c) for c in cols]
+        for b in bufs:
+            if b.nbytes % 32 or b.is_device != bufs[0].is_device:
+                raise ValueError("the vectors must hold 32-byte elements, in the same kind of memory")
+            if b.is_device and b.device_index != self.device:
+                raise MsmError(-1, f"the input lives on cuda:{b.device_index} but this domain is bound to device {self.device}")
+        m = len(bufs)
+        lens = [b.nbytes // 32 for b in bufs]
+        n = max(lens)
+        first = bufs[lens.index(n)]
+        res, ob = self._out(cols[lens.index(n)], first, out, n)
+        ptrs = (ctypes.c_void_p * m)(*[b.ptr if ln else None for b, ln in zip(bufs, lens)])
+        lv = (ctypes.c_size_t * m)(*lens)
+        cb = b"".join(self._scalar(c, montgomery) for c in coeffs)
+        flags = 0 if montgomery else 1
+        if first.is_device:
+            _check(self._lib.mi355_msm_domain_linear_combination_device(self.handle, ob.ptr if n else None, ptrs, lv, cb, m, flags, first.stream))
+            return res
+        _check(self._lib.mi355_msm_domain_linear_combination(self.handle, ob.ptr if n else None, ptrs, lv, cb, m, flags))
+        return _like_input(cols[lens.index(n)], res, (n, 32))
+
     def set_option(self, key: str, value: int) -> None:
         _check(self._lib.mi355_msm_domain_set_option(self.handle, key.encode(), int(value)))
 
     def query(self, key: str) -> int:
-        """ "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "scan_work_bytes", "poly_tile_log",
+        """ "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "scan_work_bytes", "quotient_work_bytes",
+        "poly_tile_log",
         "device", "last_us", "last_device_us" """
         v = ctypes.c_uint64(0)
         _check(self._lib.mi355_msm_domain_query(self.handle, key.encode(), ctypes.byref(v)))

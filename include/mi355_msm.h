@@ -459,7 +459,7 @@ RustError mi355_msm_mul_points_device(mi355_msm_ctx* ctx, const void* d_points, 
  * input becomes ready (NULL = the default stream): the work is enqueued there and the call returns when the output is written.
  * Option "pass_log" 1..10 (0 restores the default, 8): butterfly levels per pass -- a test hook.  Results never depend on it, nor on
  * host versus device pointers, nor on batching.
- * Queries: "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "scan_work_bytes", "poly_tile_log", "device", "last_us" (host clock around the most recent
+ * Queries: "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "scan_work_bytes", "quotient_work_bytes", "poly_tile_log", "device", "last_us" (host clock around the most recent
  * call), "last_device_us" (the same call between events on the stream it ran on).
  * Errors: -1 with a message for null pointers, in_len > n, a partial overlap, unknown or misplaced flag bits, an unknown kind, an offset
  * on a plain transform, a size above the limits -- decided before any device call; hipErrorNoDevice without a GPU. */
@@ -570,6 +570,57 @@ RustError mi355_msm_domain_permutation_product(mi355_msm_domain* d, void* out, v
 RustError mi355_msm_domain_permutation_product_device(mi355_msm_domain* d, void* d_out, void* total32, const void* d_wires, const void* d_sigmas,
                                                       size_t m, size_t stride, const void* ks, const void* beta, const void* gamma, unsigned flags,
                                                       void* stream);
+
+/* ---- the rows of the Plonk quotient and linear combinations of Fr vectors ---------------------------------------------------------------
+ * What a TurboPlonk prover's third round needs between its 25 coset_ffts and the coset_ifft (Jellyfish's compute_quotient_polynomial),
+ * and the sum sum_j c_j p_j(X) with host scalars of its fourth and fifth (the linearisation and the batched opening polynomial).  The
+ * calls live on the domain handle and follow the conventions of the calls above: 32-byte elements, arkworks Fr images or, with flag
+ * bit 0 (the only flag), plain integers; ANY 256-bit input is read as its residue and every output is canonical; host pointers without
+ * _device, device pointers (4-byte aligned) and a stream with it; ks, alpha, beta, gamma, offset and coeffs are HOST elements in the form
+ * of the call, also in the _device calls.
+ *   plonk_quotient  the handle is the QUOTIENT domain, of M = 2^K points; n, a power of two, is the size of the constraint domain and
+ *                   ratio = M / n is 2, 4, 8 or 16.  Every vector holds M evaluations on offset * H_M in natural order, what the coset
+ *                   transform of kind 2 writes (offset NULL: GENERATOR).  wires and sigmas hold m columns `stride` >= M elements
+ *                   apart; selectors is NULL or holds 13 columns with the same stride in the order q_lc[0..3], q_mul[0..1],
+ *                   q_hash[0..3], q_o, q_c, q_ecc, and then m == 5; with selectors == NULL, 1 <= m <= 8 and the gate term is pi[i]
+ *                   alone, for a prover that brings the evaluations of a gate of its own.  z: the permutation polynomial; pi may be
+ *                   NULL, meaning 0; ks: m elements.  For row i, with x = offset * omega_M^i:
+ *                     t_circ  = q_c + pi + sum_(j<4) q_lc[j] w_j + q_mul[0] w0 w1 + q_mul[1] w2 w3 + q_ecc w0 w1 w2 w3 w4
+ *                               + sum_(j<4) q_hash[j] w_j^5 - q_o w4
+ *                     t_perm1 = alpha (z[i] prod_j (w_j + beta ks[j] x + gamma) - z[(i + ratio) mod M] prod_j (w_j + beta sigma_j + gamma))
+ *                     t_perm2 = alpha^2 (z[i] - 1) / (n (x - 1))
+ *                     out[i]  = (t_circ + t_perm1) / ((offset omega_M^(i mod ratio))^n - 1) + t_perm2
+ *                   out may not overlap any input: z is read `ratio` rows ahead.  An offset that is 0, or with
+ *                   (offset omega_M^i)^n = 1 for some i < ratio, is an error, judged in host arithmetic as
+ *                   divide_by_vanishing_on_coset judges its own.  AFTER THAT CHECK x - 1 IS NEVER 0 (an offset inside H_M fails it), so
+ *                   the zero convention of the batch inversion underneath cannot be reached.  Sums over several proving instances
+ *                   (the reference's alpha_base) stay with vec_op.
+ *   linear_combination  cols: a HOST array of m pointers (1 <= m <= 32) to vectors of lens[j] <= 2^30 elements; coeffs: m elements.
+ *                   out[i] = sum_j coeffs[j] * cols[j][i] for i < max(lens); a column contributes 0 past its length; max(lens) == 0
+ *                   writes nothing.  out may be exactly one of the columns; any other overlap is refused.  The length has nothing
+ *                   to do with the domain's size.
+ * Scheme (csrc/quotient.hpp): one kernel writes x_i - 1 into work memory, the three launches of the batch inversion turn it into
+ * alpha^2 / (n (x_i - 1)) in place, and one kernel with one lane per row and one rolled loop over the columns does the rest; the `ratio`
+ * inverses of Z_H, alpha, alpha^2 / n, beta ks[j] and gamma are prepared on the host.  The linear combination is one launch and one
+ * pass.  Separate launches on one stream: no block waits on another, nothing is atomic.
+ * Work memory is allocated on the first such call and kept by the handle: query "quotient_work_bytes" ("work_bytes", "poly_work_bytes"
+ * and "scan_work_bytes" keep their meaning and their values).  Results never depend on "poly_tile_log", on host versus device pointers
+ * or on `stride`.  There is no CPU fallback.
+ * Errors: -1 with a message for unknown flag bits, m outside its range (5 with selectors, 1..8 without, 1..32 columns of a combination),
+ * n not a power of two or too large for any ratio, a stride of 0, a length above 2^30, null pointers, an output that is an input, an
+ * offset of 0 and, last, a null handle -- decided before any device call; the ratio, a stride below M, the overlap of whole columns and
+ * the offset's residue are judged against the handle. */
+RustError mi355_msm_domain_plonk_quotient(mi355_msm_domain* d, void* out, const void* wires, const void* sigmas, const void* selectors, const void* z,
+                                          const void* pi, size_t m, size_t stride, size_t n, const void* ks, const void* alpha, const void* beta,
+                                          const void* gamma, const void* offset, unsigned flags);
+RustError mi355_msm_domain_plonk_quotient_device(mi355_msm_domain* d, void* d_out, const void* d_wires, const void* d_sigmas, const void* d_selectors,
+                                                 const void* d_z, const void* d_pi, size_t m, size_t stride, size_t n, const void* ks,
+                                                 const void* alpha, const void* beta, const void* gamma, const void* offset, unsigned flags,
+                                                 void* stream);
+RustError mi355_msm_domain_linear_combination(mi355_msm_domain* d, void* out, const void* const* cols, const size_t* lens, const void* coeffs,
+                                              size_t m, unsigned flags);
+RustError mi355_msm_domain_linear_combination_device(mi355_msm_domain* d, void* d_out, const void* const* d_cols, const size_t* lens,
+                                                     const void* coeffs, size_t m, unsigned flags, void* stream);
 
 /* ---- transforms of vectors of curve points over a domain (ARK poly/src/domain/mod.rs:99-170 on DomainCoeff = G1Projective / G2Projective) ----
  * domain.fft / ifft / coset_fft / coset_ifft on GROUP elements: what turns a monomial SRS [tau^j] G into the Lagrange SRS

@@ -373,6 +373,33 @@ struct Radix2EvaluationDomain {
     check(mi355_msm_domain_permutation_product(handle, out.data(), total, wires.data(), sigmas.data(), ks.size(), stride, ks.data(), &beta, &gamma, 0));
     return out;
   }
+  // the rows of a TurboPlonk quotient on THIS domain as the quotient domain (size() = M, n = the constraint domain's size, M / n in
+  // 2, 4, 8, 16): wires and sigmas hold ks.size() columns of coset evaluations `stride` >= size() elements apart, selectors is empty
+  // (the gate is pi alone) or holds the 13 columns q_lc, q_mul, q_hash, q_o, q_c, q_ecc beside 5 wires; pi may be empty (0)
+  std::vector<BigInteger256> plonk_quotient(const std::vector<BigInteger256>& wires, const std::vector<BigInteger256>& sigmas,
+                                            const std::vector<BigInteger256>& selectors, const std::vector<BigInteger256>& z,
+                                            const std::vector<BigInteger256>& pi, size_t stride, size_t n, const std::vector<BigInteger256>& ks,
+                                            const BigInteger256& alpha, const BigInteger256& beta, const BigInteger256& gamma,
+                                            const BigInteger256* offset = nullptr) const {
+    std::vector<BigInteger256> out(size());
+    check(mi355_msm_domain_plonk_quotient(handle, out.data(), wires.data(), sigmas.data(), selectors.empty() ? nullptr : selectors.data(), z.data(),
+                                          pi.empty() ? nullptr : pi.data(), ks.size(), stride, n, ks.data(), &alpha, &beta, &gamma, offset, 0));
+    return out;
+  }
+  // sum_j coeffs[j] * cols[j][i], as long as the longest column; a column contributes 0 past its end
+  std::vector<BigInteger256> linear_combination(const std::vector<std::vector<BigInteger256>>& cols, const std::vector<BigInteger256>& coeffs) const {
+    std::vector<const void*> ptrs;
+    std::vector<size_t> lens;
+    size_t n = 0;
+    for (const auto& c : cols) {
+      ptrs.push_back(c.data());
+      lens.push_back(c.size());
+      n = c.size() > n ? c.size() : n;
+    }
+    std::vector<BigInteger256> out(n);
+    check(mi355_msm_domain_linear_combination(handle, out.data(), ptrs.data(), lens.data(), coeffs.data(), cols.size(), 0));
+    return out;
+  }
   ~Radix2EvaluationDomain() {
     if (handle) {
       RustError e = mi355_msm_domain_destroy(handle);

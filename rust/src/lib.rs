@@ -226,6 +226,21 @@ pub mod sys {
         pub fn mi355_msm_domain_permutation_product_device(d: *mut c_void, d_out: *mut c_void, total32: *mut c_void, d_wires: *const c_void,
                                                            d_sigmas: *const c_void, m: usize, stride: usize, ks: *const c_void,
                                                            beta: *const c_void, gamma: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
+        // the rows of a TurboPlonk quotient on the quotient domain (m columns of coset evaluations `stride` elements apart, selectors
+        // null or 13 columns beside 5 wires, pi and offset may be null, n = the constraint domain's size) and the linear combination
+        // sum_j coeffs[j] * cols[j][i] of m <= 32 vectors; ks, alpha, beta, gamma, offset and coeffs are HOST elements
+        pub fn mi355_msm_domain_plonk_quotient(d: *mut c_void, out: *mut c_void, wires: *const c_void, sigmas: *const c_void,
+                                               selectors: *const c_void, z: *const c_void, pi: *const c_void, m: usize, stride: usize, n: usize,
+                                               ks: *const c_void, alpha: *const c_void, beta: *const c_void, gamma: *const c_void,
+                                               offset: *const c_void, flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_plonk_quotient_device(d: *mut c_void, d_out: *mut c_void, d_wires: *const c_void, d_sigmas: *const c_void,
+                                                      d_selectors: *const c_void, d_z: *const c_void, d_pi: *const c_void, m: usize,
+                                                      stride: usize, n: usize, ks: *const c_void, alpha: *const c_void, beta: *const c_void,
+                                                      gamma: *const c_void, offset: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_linear_combination(d: *mut c_void, out: *mut c_void, cols: *const *const c_void, lens: *const usize,
+                                                   coeffs: *const c_void, m: usize, flags: c_uint) -> Error;
+        pub fn mi355_msm_domain_linear_combination_device(d: *mut c_void, d_out: *mut c_void, d_cols: *const *const c_void, lens: *const usize,
+                                                          coeffs: *const c_void, m: usize, flags: c_uint, stream: *mut c_void) -> Error;
         // the same four transforms on a vector of curve points (ark-poly's domains over DomainCoeff = G1Projective / G2Projective):
         // Affine images in and out (flags bit 1: Projective images out), offset: one arkworks Fr image on the host or null
         pub fn mi355_msm_fft_points(ctx: *mut c_void, domain: *mut c_void, out: *mut c_void, out_stride: usize, input: *const c_void, in_len: usize,

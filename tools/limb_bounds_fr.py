@@ -19,6 +19,7 @@ All margins must be positive (tests/test_fr_consts.py runs it); the host build c
     python tools/limb_bounds_fr.py
     python tools/limb_bounds_fr.py --poly     (the chains of csrc/poly.hpp: analyse_poly below)
     python tools/limb_bounds_fr.py --scan     (the sum scan and the permutation product of csrc/scan.hpp: analyse_scan below)
+    python tools/limb_bounds_fr.py --quotient (the rows of the Plonk quotient and the linear combination of csrc/quotient.hpp: analyse_quotient below)
 """
 import sys
 
@@ -227,8 +228,97 @@ def analyse_scan(name, r, out):
     return ok
 
 
+LINCOMB_COLUMNS = 32    # LINCOMB_MAX_COLUMNS of csrc/quotient.hpp
+
+
+def analyse_quotient(name, r, out):
+    """The chains of csrc/quotient.hpp (python tools/limb_bounds_fr.py --quotient), carried exactly as quot_row performs them.  The gate
+    accumulator starts as q_c + pi; every iteration of the column loop adds two class-M products (q_lc w, q_hash w^5) and at odd columns a
+    third (q_mul w w'), then one carry pass; the fifth column adds q_ecc w0..w4, carries, subtracts q_o w4 (+ 4r) and carries; t_perm1,
+    one class-M product, is added and the sum is the first operand of the product by 1 / Z_H.  The linear combination adds one class-M
+    product per column with a carry pass after each.  The largest column of every product must stay below 2^64."""
+    import math
+
+    rl = limbs(r)
+    ok = True
+    worst_col = 0
+
+    def margin(what, have, limit):
+        nonlocal ok
+        m = limit - have
+        ok &= m > 0
+        out.append("  %-78s %s (limit 2^%.2f, margin %.3e)" % (what, "ok " if m > 0 else "BAD", math.log2(limit), m))
+
+    top_m = (2 * r) >> (B * (N - 1))
+    class_m = [MASK] * (N - 1) + [top_m]
+    w = [MASK] * (N - 1) + [rl[N - 1]]
+    bias = bias4(r)
+
+    def first_operand(what, l, val, second):
+        nonlocal worst_col
+        col = max(columns(l, second, rl))
+        worst_col = max(worst_col, col)
+        margin(what + ": value %dr against R" % val, val * r, R)
+        margin(what + ": largest limb against 2^31", max(l), 1 << 31)
+        margin(what + ": largest column against 2^64", col, 1 << 64)
+        sec_val = 2 * r if second is class_m else r
+        margin(what + ": product r + a b / R against 2r", r + val * r * sec_val // R + 1, 2 * r)
+
+    def add(what, a, b, carry=True):
+        sm = [x + y for x, y in zip(a, b)]
+        margin(what + ": limb-wise sum against 2^32", max(sm), 1 << 32)
+        if not carry:
+            return sm
+        margin(what + ": top limb into the carry pass against 2^31", sm[N - 1] + (sm[N - 2] >> B), 1 << 31)
+        return carry_pass(sm)
+
+    out.append("%s: r = %.3f * 2^252, R / r = %.2f  (the chains of quotient.hpp)" % (name, r / 2**252, R / r))
+    margin("second operand: limbs of a class-M value against 2^29 + 8", max(class_m), (1 << B) + 8)
+    first_operand("products of loaded values, wires and their powers: class-M by class-M", class_m, 2, class_m)
+    for i in range(N):
+        margin("BIAS4 limb %d covers the limb of a class-M value" % i, class_m[i], bias[i] + 1)
+    # x - 1 (the first kernel) and z[i] - 1: a class-M value + BIAS4 - a class-M value, one carry pass, then a product
+    diff = add("difference x - 1, z - 1, num - den", class_m, bias)
+    first_operand("difference as a first operand (conversion, alpha^2 / (n (x - 1)), alpha)", diff, 6, class_m)
+    # the permutation factors, as in scan.hpp
+    t = [class_m[i] + class_m[i] + w[i] for i in range(N)]
+    margin("permutation factor: limb-wise sum against 2^32", max(t), 1 << 32)
+    first_operand("permutation factor w + beta k x + gamma times the running product", t, 5, class_m)
+    # the gate
+    acc, val = add("gate: q_c + pi", class_m, class_m, carry=False), 4
+    for j in range(4):
+        acc = add("gate column %d: + q_lc w" % j, acc, class_m, carry=False)
+        acc = add("gate column %d: + q_hash w^5" % j, acc, class_m, carry=j % 2 == 0)
+        val += 4
+        if j % 2:
+            acc = add("gate column %d: + q_mul w w'" % j, acc, class_m)
+            val += 2
+    acc = add("gate column 4: + q_ecc w0 w1 w2 w3 w4", acc, class_m)
+    val += 2
+    acc = add("gate column 4: - q_o w4 (+ 4r)", acc, bias)
+    val += 4
+    acc = add("gate + t_perm1", acc, class_m, carry=False)
+    val += 2
+    first_operand("gate + t_perm1 times 1 / Z_H", acc, val, w)
+    fin = add("(..) / Z_H + t_perm2", class_m, class_m, carry=False)
+    first_operand("the row as the first operand of the conversion", fin, 4, w)
+    # the linear combination
+    acc, val = [0] * N, 0
+    for j in range(LINCOMB_COLUMNS):
+        acc = add("linear combination, column %2d" % j, acc, class_m)
+        val += 2
+    first_operand("linear combination of %d columns as the first operand of the conversion" % LINCOMB_COLUMNS, acc, val, w)
+    margin("the chain's largest column against 2^64", worst_col, 1 << 64)
+    return ok
+
+
 def main():
     out = []
+    if "--quotient" in sys.argv[1:]:
+        ok = all([analyse_quotient(name, r, out) for name, r in FIELDS.items()])
+        print("\n".join(out))
+        print("all margins positive" if ok else "A MARGIN IS NOT POSITIVE")
+        return 0 if ok else 1
     if "--scan" in sys.argv[1:]:
         ok = all([analyse_scan(name, r, out) for name, r in FIELDS.items()])
         print("\n".join(out))
