@@ -12,6 +12,7 @@ import pytest
 
 import fixed_base_cases as fc
 import pymodel as pm
+import stream_cases as st
 
 pytestmark = pytest.mark.gpu
 
@@ -51,21 +52,24 @@ def rows(out, size):
     return [bytes(r[:size]) for r in out]
 
 
-def device_scalars(torch, raw, stream):
-    """the scalars as a GPU tensor PRODUCED on `stream` by a kernel (two xors of a masked copy), so that a call that ignored the
-    stream would read the mask instead"""
-    host = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
-    with torch.cuda.stream(stream):
-        d = host.to("cuda", non_blocking=False)
-        mask = torch.full_like(d, 0x5A)
-        d = torch.bitwise_xor(torch.bitwise_xor(d, mask), mask)
-    return d
+def device_scalars(torch, raw, stream, delay):
+    """the scalars as a GPU tensor PRODUCED LATE on `stream` (tests/stream_cases.py: poison until tens of milliseconds of device work
+    have passed there), so that a call that ignored the stream would read the poison instead"""
+    return st.late(torch, raw, stream, delay)
+
+
+@pytest.fixture(scope="module")
+def delay():
+    """the calibrated delay of tests/stream_cases.py, once for the module"""
+    import torch
+
+    return st.Delay(torch, torch.cuda.Stream())
 
 
 # ---- 1. bytes, small ---------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("name", fc.CURVE_NAMES)
-def test_bytes_small(ea, oracle, name):
+def test_bytes_small(ea, oracle, delay, name):
     import torch
 
     curve = pm.CURVES[name]
@@ -92,10 +96,13 @@ def test_bytes_small(ea, oracle, name):
             bad = [i for i, (g, e) in enumerate(zip(rows(got_p, curve.projective_bytes), want_p)) if g != e]
             assert not bad, (name, label, "projective", bad[:8])
             # device pointers, a non-default stream, the scalars produced on it by a preceding kernel
-            d = device_scalars(torch, raw, stream)
+            d = device_scalars(torch, raw, stream, delay)
+            assert st.window_open(d.produced)
             with torch.cuda.stream(stream):
                 dev_a = table.msm(d)
                 dev_p = table.msm(d, projective=True)
+            stream.synchronize()
+            assert st.closed(d)
             assert dev_a.is_cuda and tuple(dev_a.shape) == (len(ks), curve.affine_stride)
             assert dev_a.cpu().numpy().tobytes() == got_a
             assert dev_p.cpu().numpy().tobytes() == got_p

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import ntt_cases as nc
+import stream_cases as st
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -147,7 +148,7 @@ def test_short_inputs_and_batches(domains, torch_, field):
 
 
 @pytest.mark.parametrize("field", FIELDS)
-def test_host_and_device_pointers_and_streams(domains, torch_, field):
+def test_host_and_device_pointers_and_streams(domains, torch_, delay, field):
     torch = torch_
     k = 10
     dom = domains(field, k)
@@ -156,14 +157,19 @@ def test_host_and_device_pointers_and_streams(domains, torch_, field):
         raw, want = nc.encode(field, x, False), nc.encode(field, y, False)
         assert dom_bytes(call(dom, kind, raw)) == want
         s = torch.cuda.Stream()
-        host = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
+        d = st.late(torch, raw, s, delay, shape=(-1, 32))                             # produced LATE on s: poison until then
+        assert st.window_open(d.produced)
         with torch.cuda.stream(s):
-            d = host.to("cuda")
-            mask = torch.full_like(d, 0x5A)
-            d = torch.bitwise_xor(torch.bitwise_xor(d, mask), mask).reshape(-1, 32)   # produced on s by kernels
             got = call(dom, kind, d)
         s.synchronize()
+        assert st.closed(d)
         assert raw_of(got) == want
+
+
+@pytest.fixture(scope="module")
+def delay(torch_):
+    """the calibrated delay of tests/stream_cases.py, once for the module"""
+    return st.Delay(torch_, torch_.cuda.Stream())
 
 
 def dom_bytes(out):

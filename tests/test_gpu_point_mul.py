@@ -13,6 +13,7 @@ import pytest
 
 import point_mul_cases as pc
 import pymodel as pm
+import stream_cases as st
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -30,15 +31,18 @@ def rows(out, size):
     return [bytes(r[:size]) for r in out]
 
 
-def produced_on(torch, raw, stream):
-    """`raw` as a GPU tensor PRODUCED on `stream` by a kernel (two xors of a masked copy), so that a call that ignored the stream would
-    read the mask instead (the device_scalars trick of tests/test_gpu_fixed_base.py)"""
-    host = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
-    with torch.cuda.stream(stream):
-        d = host.to("cuda", non_blocking=False)
-        mask = torch.full_like(d, 0x5A)
-        d = torch.bitwise_xor(torch.bitwise_xor(d, mask), mask)
-    return d
+def produced_on(torch, raw, stream, delay):
+    """`raw` as a GPU tensor PRODUCED LATE on `stream` (tests/stream_cases.py: poison until tens of milliseconds of device work have
+    passed there), so that a call that ignored the stream would read the poison instead"""
+    return st.late(torch, raw, stream, delay)
+
+
+@pytest.fixture(scope="module")
+def delay():
+    """the calibrated delay of tests/stream_cases.py, once for the module"""
+    import torch
+
+    return st.Delay(torch, torch.cuda.Stream())
 
 
 def mismatches(got, want):
@@ -76,7 +80,7 @@ def pairwise_cases(name):
 # ---- 1. bytes, small ---------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("name", pc.CURVE_NAMES)
-def test_pairwise_bytes_small(ea, ctxs, name):
+def test_pairwise_bytes_small(ea, ctxs, delay, name):
     import torch
 
     curve = pm.CURVES[name]
@@ -96,10 +100,13 @@ def test_pairwise_bytes_small(ea, ctxs, name):
     assert not bad, (name, "projective", bad[:8])
     # device pointers, a non-default stream, points and scalars produced on it by preceding kernels
     stream = torch.cuda.Stream()
-    d_pts, d_s = produced_on(torch, pts, stream), produced_on(torch, raw, stream)
+    d_pts, d_s = st.late_many(torch, [pts, raw], stream, delay)             # (one producer in front of both)
+    assert st.window_open(d_pts.produced) and st.window_open(d_s.produced)
     with torch.cuda.stream(stream):
         dev_a = ctx.mul_points(d_pts, d_s)
         dev_p = ctx.mul_points(d_pts, d_s, projective=True)
+    stream.synchronize()
+    assert st.closed(d_pts, d_s)
     assert dev_a.is_cuda and tuple(dev_a.shape) == (m, curve.affine_stride)
     assert dev_a.cpu().numpy().tobytes() == got_a
     assert dev_p.cpu().numpy().tobytes() == got_p
@@ -142,7 +149,7 @@ def test_pairwise_wave_trim(ea, ctxs, name):
 
 
 @pytest.mark.parametrize("name", pc.CURVE_NAMES)
-def test_uniform_bytes_small(ea, ctxs, name):
+def test_uniform_bytes_small(ea, ctxs, delay, name):
     import torch
 
     curve = pm.CURVES[name]
@@ -162,9 +169,12 @@ def test_uniform_bytes_small(ea, ctxs, name):
                 assert ctx.mul_points_by(pts, k) == got                 # an int is packed into the fewest words
                 got_p = ctx.mul_points_by(pts, kb, projective=True)
                 assert rows(got_p, curve.projective_bytes) == [curve.encode_projective_normalized(v) for v in want]
-                d_pts = produced_on(torch, pts, stream)
+                d_pts = produced_on(torch, pts, stream, delay)
+                assert st.window_open(d_pts.produced)
                 with torch.cuda.stream(stream):
                     dev = ctx.mul_points_by(d_pts, kb)
+                stream.synchronize()
+                assert st.closed(d_pts)
                 assert dev.is_cuda and dev.cpu().numpy().tobytes() == got
             if k == 1:
                 # the canonical input images, byte for byte (a flagged infinity with junk coordinates comes back as the canonical one)
