@@ -2,5 +2,5 @@
 #include "launch_impl.hpp"
 
 namespace msm {
-template struct Launch<Bls12_381_G1::E>;
+MSM_INSTANTIATE_SW_LAUNCHERS(Bls12_381_G1::E)
 }

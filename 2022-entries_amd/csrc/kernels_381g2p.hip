@@ -1,7 +1,7 @@
 // kernels_381g2p.hip -- the throughput kernels of Bls12_381_G2 with two lanes per point (fp2pair.hpp); its own translation unit so
 // that it compiles beside kernels_381g2.hip.
-#include "launch_pair_impl.hpp"
+#include "launch_impl.hpp"
 
 namespace msm {
-template struct LaunchPair<Bls12_381_G2::E>;
+template struct WalkLaunch<PairedForm<SwLaw<Bls12_381_G2::E>>::L>;   // (no sum_bases and no quad form: launch_impl.hpp)
 }

@@ -1105,46 +1105,51 @@ hipEvent_t* carry_events(mi355_msm_ctx* ctx, uint32_t index) {
   return ctx->carry_ev.data() + 7 * (size_t)index;
 }
 
-// One chunk of one batch: device scalars [0, n) against bases [base0, base0 + n).  Leaves the folded chunk sum in `out`.
-// TE = true runs the twisted-Edwards kernels (BLS12-377 G1 contexts whose bases all have an image) and returns false when
-// an addition reported a vanishing denominator: the caller then repeats the chunk -- or, when `carry` is set, the whole batch -- with TE = false.
-template <class C, bool TE>
-bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0, size_t n, hipStream_t st,
-                    typename HostTail<typename C::E>::Pt& out, const std::function<void()>* while_gpu_busy, const BucketCarry* carry = nullptr) {
-  using E = typename C::E;
-  using El = typename E::T;
-  using XyzzDev = XyzzDevT<El>;
-  using AffineDev = AffineDevT<El>;
-  using SegOut = SegOutT<El>;
-  using Xyzz = XyzzT<El>;
-  const bool use_tables = ctx->pre_c && (TE || !ctx->sw_level0_only);
-  const Plan p = ctx->plan(n, use_tables, carry ? carry->c : 0);
-  if (p.entries >= (1ull << 32)) bad_arg("chunk of %zu pairs needs %llu sort entries (>= 2^32)", n, (unsigned long long)p.entries);
-  hipEvent_t* const ev = carry ? carry_events(ctx, carry->index) : ctx->ev;
-  const size_t NE = p.entries;
-  if (ctx->inject_alloc_failures != 0) {
-    // N > 0: the next N reservations fail; -K: the K-th reservation from now fails (a chunk in the middle of a carried batch)
-    const bool fail = ctx->inject_alloc_failures > 0 ? (ctx->inject_alloc_failures--, true) : (++ctx->inject_alloc_failures == 0);
-    if (fail) throw HipFailure((int)hipErrorOutOfMemory, "work-buffer reservation failed: out of memory (injected by the inject_alloc_failures test hook)");
-  }
-  reserve_work(ctx, chunk_work_bytes(p, n, use_tables, sizeof(XyzzDev), carry != nullptr));
-  const uint32_t table_stride = use_tables ? (uint32_t)ctx->nbases : 0u;
-  const PartPlan gp = part_plan((uint32_t)n, p.c, p.windows, use_tables ? p.levels : 1, (uint32_t)base0, table_stride, ctx->opt_assume_subgroup != 0, p.anchor);
-  ctx->last_anchor = gp.anchor;
-  const size_t nbuckets = (size_t)p.bucket_windows * p.half;
-  if (ctx->pinned_bytes < p.windows * sizeof(XyzzDev)) {
-    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-    ctx->pinned_bytes = 64 * sizeof(XyzzDev) > p.windows * sizeof(XyzzDev) ? 64 * sizeof(XyzzDev) : p.windows * sizeof(XyzzDev);
-    HIP_OK(hipHostMalloc(&ctx->pinned, ctx->pinned_bytes, hipHostMallocDefault));
-  }
+// ---- one chunk of one batch, stage by stage ----------------------------------------------------------------------------------------------
+// A chunk runs under one law G (launch.hpp): SwLaw<C::E>, or TeLaw<TeFq> on a BLS12-377 G1 context whose bases all have an image.
+template <class G>
+inline constexpr bool kEdwards = false;
+template <class F>
+inline constexpr bool kEdwards<TeLaw<F>> = true;
 
-  const AffineDev* bases = ctx->bases.as<AffineDev>();
-  const uint8_t* inf = ctx->inf.as<uint8_t>();
-  uint32_t* flags = ctx->flags.as<uint32_t>();
+// the base records law G gathers, and the device flag words of a law that can fail
+template <class G>
+const typename LawMem<G>::BaseDev* law_bases(const mi355_msm_ctx* ctx) {
+  if constexpr (kEdwards<G>)
+    return ctx->te_bases.as<TeAffineDev>();
+  else
+    return ctx->bases.as<typename LawMem<G>::BaseDev>();
+}
+template <class G>
+uint32_t* law_flags(const mi355_msm_ctx* ctx) {
+  return kEdwards<G> ? ctx->flags.as<uint32_t>() : nullptr;
+}
 
-  // digits + bucket grouping: (value, key) entries sorted by key in entries[sorted]; the count of real entries stays on the device
-  HIP_OK(hipEventRecord(ev[0], st));
-  PartBuffers gb{};
+// The form of a walking launch under law G: launch.template operator()<L>() with L = G, or with the two-lanes-per-point law of a G2
+// curve when bit `bit` of the option "g2_paired" asks for it (1 accumulate, 2 bucket_reduce at every level, 4 fragment merge, 8 scan
+// steps, 16 bucket_merge; 0 = this launch is never paired).  A `small` launch (at most quad_limit additions) stays with G whatever the
+// mask: WalkLaunch<G> runs it on the quad kernel, which the paired law does not have.  Over Fp there is one form: the mask is ignored.
+template <class G, class Fn>
+hipError_t walk_form(const mi355_msm_ctx* ctx, long bit, bool small, Fn&& launch) {
+  using P = typename PairedForm<G>::L;
+  if constexpr (!std::is_same_v<P, G>) {
+    if ((ctx->opt_g2_paired & bit) != 0 && !small) return launch.template operator()<P>();
+  }
+  return launch.template operator()<G>();
+}
+
+// room for `rows` window sums in pinned host memory
+void reserve_pinned(mi355_msm_ctx* ctx, size_t rows, size_t row_bytes) {
+  const size_t need = std::max<size_t>(64, rows) * row_bytes;
+  if (ctx->pinned_bytes >= need) return;
+  if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+  ctx->pinned_bytes = need;
+  HIP_OK(hipHostMalloc(&ctx->pinned, ctx->pinned_bytes, hipHostMallocDefault));
+}
+
+// Digits + bucket grouping: (value, key) entries sorted by key in the returned buffer; the count of real entries stays on the device
+// (gb.totals).  `mid` is recorded between the two.
+const uint2* group_chunk(mi355_msm_ctx* ctx, const uint32_t* d_scalars, const PartPlan& gp, PartBuffers& gb, hipStream_t st, hipEvent_t mid) {
   gb.entries[0] = ctx->entries[0].as<uint2>();
   gb.entries[1] = ctx->entries[1].as<uint2>();
   gb.matrix = ctx->part_matrix.as<uint32_t>();
@@ -1156,23 +1161,47 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
   gb.totals = ctx->part_totals.as<uint32_t>();
   hipError_t gerr = hipSuccess;
   const int scalar_mode = ctx->opt_scalars_montgomery ? SCALARS_FROM_MONT : ctx->opt_scalars_to_montgomery ? SCALARS_TO_MONT : SCALARS_PLAIN;
-  const int sorted = PartLaunch::run((ctx->curve == MI355_BLS12_381_G1 || ctx->curve == MI355_BLS12_381_G2) ? 1 : 0, scalar_mode, d_scalars, inf, gp, gb, st,
-                                     ev[1], gerr);
+  const int sorted = PartLaunch::run(is_381(ctx->curve) ? 1 : 0, scalar_mode, d_scalars, ctx->inf.as<uint8_t>(), gp, gb, st, mid, gerr);
   HIP_OK(gerr);
-  const uint2* entries = gb.entries[sorted];
-  const uint32_t* n_real = gb.totals;
+  return gb.entries[sorted];
+}
+
+// Merge the run fragments that crossed lane boundaries: levels of fan-in K over the two slots each of `nlanes` lanes left, down to one lane.
+template <class G>
+void merge_fragments(mi355_msm_ctx* ctx, uint32_t nlanes, uint32_t K, long paired_bit, hipStream_t st) {
+  using XyzzDev = XyzzDevT<typename LawMem<G>::MemT>;
+  uint32_t n_in = 2 * nlanes;
+  for (int cur = 0;; cur ^= 1) {
+    const uint32_t nl = ceil_div(n_in, K);
+    if (nl > 1 && 2 * (uint64_t)nl >= n_in) bad_arg("fragment merge would not shrink (%u slots, fan-in %u)", n_in, K);
+    SegOutT<typename LawMem<G>::MemT> o{ctx->buckets.as<XyzzDev>(), ctx->slots[cur ^ 1].as<XyzzDev>(), ctx->slot_keys[cur ^ 1].as<uint32_t>()};
+    HIP_OK(walk_form<G>(ctx, paired_bit, nl <= ctx->quad_limit, [&]<class L>() {
+      return WalkLaunch<L>::segreduce(ctx->slots[cur].as<XyzzDev>(), ctx->slot_keys[cur].as<uint32_t>(), n_in, K, o, nl, ctx->quad_limit, law_flags<G>(ctx), st);
+    }));
+    if (nl == 1) break;
+    n_in = 2 * nl;
+  }
+}
+
+// Sorted entries -> buckets: accumulate (between ev[2] and ev[3]), fragment merge, and the chunk's place among the carried buckets.
+// Returns the bucket array that holds the sums so far.
+template <class G>
+XyzzDevT<typename LawMem<G>::MemT>* accumulate_chunk(mi355_msm_ctx* ctx, const Plan& p, const PartPlan& gp, const PartBuffers& gb, const uint2* entries,
+                                                     const BucketCarry* carry, hipStream_t st, hipEvent_t* ev) {
+  using El = typename LawMem<G>::MemT;
+  using XyzzDev = XyzzDevT<El>;
+  const size_t nbuckets = (size_t)p.bucket_windows * p.half;
   // Carried batches: the twisted-Edwards kernels accumulate a later chunk straight onto the buckets the earlier chunks left
   // (SegOutT::carry_in); the XYZZ kernels fill a fresh array that k_bucket_merge adds to the batch's (see carry_begin_run for why).
-  const bool carry_in = TE && carry && !carry->first;
+  const bool carry_in = kEdwards<G> && carry && !carry->first;
   if (!carry_in) HIP_OK(hipMemsetAsync(ctx->buckets.p, 0, nbuckets * sizeof(XyzzDev), st));
   HIP_OK(hipEventRecord(ev[2], st));
 
-  SegOut so{ctx->buckets.as<XyzzDev>(), ctx->slots[0].as<XyzzDev>(), ctx->slot_keys[0].as<uint32_t>()};
+  SegOutT<El> so{ctx->buckets.as<XyzzDev>(), ctx->slots[0].as<XyzzDev>(), ctx->slot_keys[0].as<uint32_t>()};
   so.carry_in = carry_in ? 1u : 0u;
-  if constexpr (TE)
-    HIP_OK(LaunchTe::accumulate(entries, n_real, p.K, ctx->te_bases.as<TeAffineDev>(), so, p.nlanes, flags, st));
-  else
-    HIP_OK(Launch<E>::accumulate(entries, n_real, p.K, bases, so, p.nlanes, st, (ctx->opt_g2_paired & 1) != 0));
+  HIP_OK(walk_form<G>(ctx, 1, false, [&]<class L>() {
+    return WalkLaunch<L>::accumulate(entries, gb.totals, p.K, law_bases<G>(ctx), so, p.nlanes, law_flags<G>(ctx), st);
+  }));
   HIP_OK(hipEventRecord(ev[3], st));
 #ifdef MSM_DEBUG
   {
@@ -1182,66 +1211,36 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
     if (what[0]) throw HipFailure(-2, what);
   }
 #endif
-
-  // merge the run fragments that crossed lane boundaries
-  uint32_t n_in = 2 * p.nlanes;
-  int cur = 0;
-  if (p.nlanes > 1) {
-    for (;;) {
-      uint32_t nl = ceil_div(n_in, p.segK);
-      if (nl > 1 && 2 * (uint64_t)nl >= n_in) bad_arg("fragment merge would not shrink (%u slots, fan-in %u)", n_in, p.segK);
-      SegOut o{ctx->buckets.as<XyzzDev>(), ctx->slots[cur ^ 1].as<XyzzDev>(), ctx->slot_keys[cur ^ 1].as<uint32_t>()};
-      if constexpr (TE)
-        HIP_OK(LaunchTe::segreduce(ctx->slots[cur].as<XyzzDev>(), ctx->slot_keys[cur].as<uint32_t>(), n_in, p.segK, o, nl, ctx->quad_limit, flags, st));
-      else
-        HIP_OK(Launch<E>::segreduce(ctx->slots[cur].as<XyzzDev>(), ctx->slot_keys[cur].as<uint32_t>(), n_in, p.segK, o, nl, ctx->quad_limit, st,
-                                    (ctx->opt_g2_paired & 4) != 0));
-      if (nl == 1) break;
-      n_in = 2 * nl;
-      cur ^= 1;
-    }
-  }
-  // carried buckets
-  XyzzDev* bucket_src = ctx->buckets.as<XyzzDev>();
-  if constexpr (!TE) {
+  if (p.nlanes > 1) merge_fragments<G>(ctx, p.nlanes, p.segK, 4, st);
+  if constexpr (!kEdwards<G>) {
     // XYZZ: the first chunk's array becomes the batch's, later chunks are added to it
     if (carry) {
       if (carry->first) {
         std::swap(ctx->buckets, ctx->carry_buckets);
       } else {
-        HIP_OK(Launch<E>::bucket_merge(ctx->carry_buckets.as<XyzzDev>(), ctx->buckets.as<XyzzDev>(), (uint32_t)nbuckets, st, (ctx->opt_g2_paired & 16) != 0));
+        HIP_OK(walk_form<G>(ctx, 16, false, [&]<class L>() {
+          return WalkLaunch<L>::bucket_merge(ctx->carry_buckets.as<XyzzDev>(), ctx->buckets.as<XyzzDev>(), (uint32_t)nbuckets, law_flags<G>(ctx), st);
+        }));
       }
-      bucket_src = ctx->carry_buckets.as<XyzzDev>();
+      return ctx->carry_buckets.as<XyzzDev>();
     }
   }
-  HIP_OK(hipEventRecord(ev[4], st));
-  ctx->last_info[0] = p.c;
-  ctx->last_info[1] = p.windows;
-  ctx->last_info[6] = ctx->pre_c ? 1 : 0;
-  ctx->last_info[2] = NE;
-  ctx->last_info[3] = p.K;
-  ctx->last_info[4] += 1;
-  ctx->last_info[5] = p.nlanes;
-  ctx->last_info[7] = TE ? 1 : 0;
-  ctx->last_bucket_windows = p.bucket_windows;
-  ctx->last_l1_bits = gp.hb;
-  ctx->last_l1_bins = gp.nbins;
-  {
-    uint32_t rb_[4];
-    ctx->last_passes = (uint32_t)part_pass_bits(gp.lb, rb_);
-  }
-  if (carry && !carry->last) {
-    // nothing to reduce yet, nothing to wait for: the next chunk's kernels queue up behind these
-    HIP_OK(hipEventRecord(ev[5], st));
-    HIP_OK(hipEventRecord(ev[6], st));
-    if (while_gpu_busy) (*while_gpu_busy)();
-    HostTail<E>::set_inf(out);
-    return true;
-  }
+  return ctx->buckets.as<XyzzDev>();
+}
 
-  // buckets -> one point per window
-  const XyzzDev* sums_src = nullptr;   // where the W window sums end up: element 0 of rows that are sums_stride elements apart
-  uint32_t sums_stride = 1;
+// Buckets -> one point per window.  The W window sums end up in element 0 of rows of the returned array that are `sums_stride` elements apart.
+template <class G>
+const XyzzDevT<typename LawMem<G>::MemT>* reduce_buckets(mi355_msm_ctx* ctx, const Plan& p, XyzzDevT<typename LawMem<G>::MemT>* bucket_src, hipStream_t st,
+                                                         uint32_t& sums_stride) {
+  using XyzzDev = XyzzDevT<typename LawMem<G>::MemT>;
+  uint32_t* const flags = law_flags<G>(ctx);
+  // one chunked level: windows x chunks walkers, each over L elements of its window's n_per_win
+  auto bucket_reduce = [&](bool first, const XyzzDev* in_a, const XyzzDev* in_x, uint32_t n_per_win, uint32_t L, uint32_t chunks, uint32_t out_stride, int to) {
+    HIP_OK(walk_form<G>(ctx, 2, false, [&]<class W>() {
+      return WalkLaunch<W>::bucket_reduce(first, in_a, in_x, n_per_win, L, chunks, p.bucket_windows, out_stride, ctx->red_a[to].as<XyzzDev>(),
+                                          ctx->red_x[to].as<XyzzDev>(), flags, st);
+    }));
+  };
   if (p.reduce_scan) {
     // parallel scan, one addition per thread and step.  Direct: on the buckets, ping-pong with a second bucket-sized array.
     // Otherwise: one chunked level first (A_t, X_t per chunk), scan on the X_t, join with the A_t, tree.
@@ -1254,12 +1253,7 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
         HIP_OK(hipMemsetAsync(ctx->red_a[0].p, 0, (size_t)p.bucket_windows * p.scan_nb * sizeof(XyzzDev), st));
         HIP_OK(hipMemsetAsync(ctx->red_x[0].p, 0, (size_t)p.bucket_windows * p.scan_nb * sizeof(XyzzDev), st));
       }
-      if constexpr (TE)
-        HIP_OK(LaunchTe::bucket_reduce(true, nullptr, bucket_src, p.half, p.L0, p.T0, p.bucket_windows, p.scan_nb,
-                                       ctx->red_a[0].as<XyzzDev>(), ctx->red_x[0].as<XyzzDev>(), flags, st));
-      else
-        HIP_OK(Launch<E>::bucket_reduce(true, nullptr, bucket_src, p.half, p.L0, p.T0, p.bucket_windows, p.scan_nb,
-                                        ctx->red_a[0].as<XyzzDev>(), ctx->red_x[0].as<XyzzDev>(), st, (ctx->opt_g2_paired & 2) != 0));
+      bucket_reduce(true, nullptr, bucket_src, p.half, p.L0, p.T0, p.scan_nb, 0);
       nb = p.scan_nb;
       a_sums = ctx->red_a[0].as<XyzzDev>();
       bufs[0] = ctx->red_x[0].as<XyzzDev>();
@@ -1267,10 +1261,10 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
     }
     int cur = 0;
     auto step = [&](uint32_t d, uint32_t mode) {
-      if constexpr (TE)
-        HIP_OK(LaunchTe::reduce_scan_step(bufs[cur], a_sums, bufs[cur ^ 1], nb, p.bucket_windows, d, mode, ctx->quad_limit, flags, st));
-      else
-        HIP_OK(Launch<E>::reduce_scan_step(bufs[cur], a_sums, bufs[cur ^ 1], nb, p.bucket_windows, d, mode, ctx->quad_limit, st, (ctx->opt_g2_paired & 8) != 0));
+      const bool small = (uint64_t)p.bucket_windows * (mode == 1 ? d : nb) <= ctx->quad_limit;
+      HIP_OK(walk_form<G>(ctx, 8, small, [&]<class W>() {
+        return WalkLaunch<W>::reduce_scan_step(bufs[cur], a_sums, bufs[cur ^ 1], nb, p.bucket_windows, d, mode, ctx->quad_limit, flags, st);
+      }));
       cur ^= 1;
     };
     for (uint32_t d = 1; d < nb; d <<= 1) step(d, 0);
@@ -1278,42 +1272,52 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
     if (nb & (nb - 1)) bad_arg("scan reduction needs a power-of-two element count per window (%u)", nb);
     for (uint32_t h = nb >> 1; h >= 1; h >>= 1) step(h, 1);   // out_j = in_j + in_(j+h) for j < h
     if (nb == 1 && !a_sums) step(1, 0);   // a single bucket per window: one pass that normalises an empty bucket to the identity
-    HIP_OK(hipEventRecord(ev[5], st));
     // the window sums sit at the head of each window's row
-    sums_src = bufs[cur];
     sums_stride = nb;
+    return bufs[cur];
+  }
+  uint32_t n_per_win = p.half, logL = p.logL0, chunks = p.T0;
+  int rb = 0;
+  bucket_reduce(true, nullptr, bucket_src, n_per_win, 1u << logL, chunks, chunks, 0);
+  while (chunks > 1) {
+    n_per_win = chunks;
+    logL = p.logL;
+    chunks = ceil_div(n_per_win, 1u << logL);
+    bucket_reduce(false, ctx->red_a[rb].as<XyzzDev>(), ctx->red_x[rb].as<XyzzDev>(), n_per_win, 1u << logL, chunks, chunks, rb ^ 1);
+    rb ^= 1;
+  }
+  sums_stride = 1;
+  return ctx->red_a[rb].as<XyzzDev>();
+}
+
+// `rows` window sums -> ctx->pinned, with the flag words of a law that can fail -> ctx->h_flags
+template <class G>
+void collect_sums(mi355_msm_ctx* ctx, const XyzzDevT<typename LawMem<G>::MemT>* src, uint32_t stride, uint32_t rows, hipStream_t st) {
+  using XyzzDev = XyzzDevT<typename LawMem<G>::MemT>;
+  static_assert(sizeof(XyzzDev) % 16 == 0, "window sums are collected in 16-byte pieces");
+  const uint32_t row_u4 = sizeof(XyzzDev) / 16, total = rows * row_u4;
+  hipLaunchKernelGGL(k_collect_sums, dim3((total + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4*>(src), stride * row_u4, row_u4, rows,
+                     reinterpret_cast<uint4*>(ctx->pinned), law_flags<G>(ctx), kEdwards<G> ? ctx->h_flags : nullptr);
+  HIP_OK(hipGetLastError());
+}
+
+// the host tail over collected sums; false when the law reported an addition it could not compute (h_flags) or the fold meets one
+template <class C, class G>
+bool fold_sums(mi355_msm_ctx* ctx, typename HostTail<typename C::E>::Pt& out, const XyzzT<typename C::E::T>* sums, int windows, int c) {
+  if constexpr (kEdwards<G>) {
+    return ctx->h_flags[1] == 0 && HostTail<typename C::E>::fold_te(out, sums, windows, c);
   } else {
-    uint32_t n_per_win = p.half, logL = p.logL0, chunks = p.T0;
-    int rb = 0;
-    if constexpr (TE)
-      HIP_OK(LaunchTe::bucket_reduce(true, nullptr, bucket_src, n_per_win, 1u << logL, chunks, p.bucket_windows, chunks,
-                                     ctx->red_a[0].as<XyzzDev>(), ctx->red_x[0].as<XyzzDev>(), flags, st));
-    else
-      HIP_OK(Launch<E>::bucket_reduce(true, nullptr, bucket_src, n_per_win, 1u << logL, chunks, p.bucket_windows, chunks,
-                                      ctx->red_a[0].as<XyzzDev>(), ctx->red_x[0].as<XyzzDev>(), st, (ctx->opt_g2_paired & 2) != 0));
-    while (chunks > 1) {
-      n_per_win = chunks;
-      logL = p.logL;
-      chunks = ceil_div(n_per_win, 1u << logL);
-      if constexpr (TE)
-        HIP_OK(LaunchTe::bucket_reduce(false, ctx->red_a[rb].as<XyzzDev>(), ctx->red_x[rb].as<XyzzDev>(), n_per_win, 1u << logL, chunks,
-                                       p.bucket_windows, chunks, ctx->red_a[rb ^ 1].as<XyzzDev>(), ctx->red_x[rb ^ 1].as<XyzzDev>(), flags, st));
-      else
-        HIP_OK(Launch<E>::bucket_reduce(false, ctx->red_a[rb].as<XyzzDev>(), ctx->red_x[rb].as<XyzzDev>(), n_per_win, 1u << logL, chunks,
-                                        p.bucket_windows, chunks, ctx->red_a[rb ^ 1].as<XyzzDev>(), ctx->red_x[rb ^ 1].as<XyzzDev>(), st, (ctx->opt_g2_paired & 2) != 0));
-      rb ^= 1;
-    }
-    HIP_OK(hipEventRecord(ev[5], st));
-    sums_src = ctx->red_a[rb].as<XyzzDev>();
-    sums_stride = 1;
+    HostTail<typename C::E>::fold(out, sums, windows, c);
+    return true;
   }
-  {
-    static_assert(sizeof(XyzzDev) % 16 == 0, "window sums are collected in 16-byte pieces");
-    const uint32_t row_u4 = sizeof(XyzzDev) / 16, total = p.bucket_windows * row_u4;
-    hipLaunchKernelGGL(k_collect_sums, dim3((total + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4*>(sums_src), sums_stride * row_u4, row_u4,
-                       p.bucket_windows, reinterpret_cast<uint4*>(ctx->pinned), TE ? flags : nullptr, TE ? ctx->h_flags : nullptr);
-    HIP_OK(hipGetLastError());
-  }
+}
+
+// Window sums -> the folded chunk sum in `out`: collect (ev[6] behind it), wait, fold, stage times.
+template <class C, class G>
+bool finish_chunk(mi355_msm_ctx* ctx, const Plan& p, const XyzzDevT<typename C::E::T>* sums_src, uint32_t sums_stride, hipStream_t st, hipEvent_t* ev,
+                  const BucketCarry* carry, const std::function<void()>* while_gpu_busy, typename HostTail<typename C::E>::Pt& out) {
+  using XyzzDev = XyzzDevT<typename C::E::T>;
+  collect_sums<G>(ctx, sums_src, sums_stride, p.bucket_windows, st);
   HIP_OK(hipEventRecord(ev[6], st));
   // everything for this chunk is enqueued: host work that should hide behind it (the next batch's H2D copy) goes here
   if (while_gpu_busy) (*while_gpu_busy)();
@@ -1329,16 +1333,11 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
   }
   HIP_OK(hipStreamSynchronize(st));
 
-  typename E::Md md;
-  std::vector<Xyzz> sums(p.bucket_windows);
+  std::vector<XyzzT<typename C::E::T>> sums(p.bucket_windows);
   const XyzzDev* hs = reinterpret_cast<const XyzzDev*>(ctx->pinned);
   for (uint32_t w = 0; w < p.bucket_windows; w++) sums[w] = hs[w].p;
-  bool ok = true;
   const auto t_fold = std::chrono::steady_clock::now();
-  if constexpr (TE)
-    ok = ctx->h_flags[1] == 0 && HostTail<E>::fold_te(out, sums.data(), (int)p.bucket_windows, (int)p.c);
-  else
-    HostTail<E>::fold(out, sums.data(), (int)p.bucket_windows, (int)p.c);
+  const bool ok = fold_sums<C, G>(ctx, out, sums.data(), (int)p.bucket_windows, (int)p.c);
   ctx->last_ms[MI355_T_HOST_FOLD] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_fold).count();
 
   // stage times: of this chunk, or of every chunk of the carried batch (their events have all completed by now)
@@ -1353,6 +1352,63 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
     ctx->last_ms[MI355_T_TOTAL] += ms;
   }
   return ok;
+}
+
+// One chunk of one batch: device scalars [0, n) against bases [base0, base0 + n).  Leaves the folded chunk sum in `out`.
+// Under TeLaw (BLS12-377 G1 contexts whose bases all have an image) it returns false when an addition reported a vanishing
+// denominator: the caller then repeats the chunk -- or, when `carry` is set, the whole batch -- under SwLaw.
+template <class C, class G>
+bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0, size_t n, hipStream_t st,
+                    typename HostTail<typename C::E>::Pt& out, const std::function<void()>* while_gpu_busy, const BucketCarry* carry = nullptr) {
+  using XyzzDev = XyzzDevT<typename C::E::T>;
+  static_assert(std::is_same_v<typename LawMem<G>::MemT, typename C::E::T>, "a law of this curve's coordinates");
+  const bool use_tables = ctx->pre_c && (kEdwards<G> || !ctx->sw_level0_only);
+  const Plan p = ctx->plan(n, use_tables, carry ? carry->c : 0);
+  if (p.entries >= (1ull << 32)) bad_arg("chunk of %zu pairs needs %llu sort entries (>= 2^32)", n, (unsigned long long)p.entries);
+  hipEvent_t* const ev = carry ? carry_events(ctx, carry->index) : ctx->ev;
+  if (ctx->inject_alloc_failures != 0) {
+    // N > 0: the next N reservations fail; -K: the K-th reservation from now fails (a chunk in the middle of a carried batch)
+    const bool fail = ctx->inject_alloc_failures > 0 ? (ctx->inject_alloc_failures--, true) : (++ctx->inject_alloc_failures == 0);
+    if (fail) throw HipFailure((int)hipErrorOutOfMemory, "work-buffer reservation failed: out of memory (injected by the inject_alloc_failures test hook)");
+  }
+  reserve_work(ctx, chunk_work_bytes(p, n, use_tables, sizeof(XyzzDev), carry != nullptr));
+  const uint32_t table_stride = use_tables ? (uint32_t)ctx->nbases : 0u;
+  const PartPlan gp = part_plan((uint32_t)n, p.c, p.windows, use_tables ? p.levels : 1, (uint32_t)base0, table_stride, ctx->opt_assume_subgroup != 0, p.anchor);
+  ctx->last_anchor = gp.anchor;
+  reserve_pinned(ctx, p.windows, sizeof(XyzzDev));
+
+  HIP_OK(hipEventRecord(ev[0], st));
+  PartBuffers gb{};
+  const uint2* entries = group_chunk(ctx, d_scalars, gp, gb, st, ev[1]);
+  XyzzDev* const bucket_src = accumulate_chunk<G>(ctx, p, gp, gb, entries, carry, st, ev);
+  HIP_OK(hipEventRecord(ev[4], st));
+  ctx->last_info[0] = p.c;
+  ctx->last_info[1] = p.windows;
+  ctx->last_info[6] = ctx->pre_c ? 1 : 0;
+  ctx->last_info[2] = p.entries;
+  ctx->last_info[3] = p.K;
+  ctx->last_info[4] += 1;
+  ctx->last_info[5] = p.nlanes;
+  ctx->last_info[7] = kEdwards<G> ? 1 : 0;
+  ctx->last_bucket_windows = p.bucket_windows;
+  ctx->last_l1_bits = gp.hb;
+  ctx->last_l1_bins = gp.nbins;
+  {
+    uint32_t rb_[4];
+    ctx->last_passes = (uint32_t)part_pass_bits(gp.lb, rb_);
+  }
+  if (carry && !carry->last) {
+    // nothing to reduce yet, nothing to wait for: the next chunk's kernels queue up behind these
+    HIP_OK(hipEventRecord(ev[5], st));
+    HIP_OK(hipEventRecord(ev[6], st));
+    if (while_gpu_busy) (*while_gpu_busy)();
+    HostTail<typename C::E>::set_inf(out);
+    return true;
+  }
+  uint32_t sums_stride = 1;
+  const XyzzDev* sums_src = reduce_buckets<G>(ctx, p, bucket_src, st, sums_stride);
+  HIP_OK(hipEventRecord(ev[5], st));
+  return finish_chunk<C, G>(ctx, p, sums_src, sums_stride, st, ev, carry, while_gpu_busy, out);
 }
 
 // A base set that trips the incomplete law twice in a row (points outside the prime-order subgroup) would pay for both paths
@@ -1373,33 +1429,31 @@ bool run_chunk(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0, size
                const BucketCarry* carry = nullptr, bool allow_te = true) {
   if constexpr (std::is_same_v<C, Bls12_377_G1>) {
     if (ctx->te_active && allow_te) {
-      if (run_chunk_impl<C, true>(ctx, d_scalars, base0, n, st, out, while_gpu_busy, carry)) {
+      if (run_chunk_impl<C, TeLaw<TeFq>>(ctx, d_scalars, base0, n, st, out, while_gpu_busy, carry)) {
         if (!carry || carry->last) ctx->te_fallback_streak = 0;
         return true;
       }
       ctx->te_fallbacks++;
       if (carry) return false;
       // (the hook -- the next batch's H2D copy -- has run already)
-      run_chunk_impl<C, false>(ctx, d_scalars, base0, n, st, out, nullptr);
+      run_chunk_impl<C, SwLaw<typename C::E>>(ctx, d_scalars, base0, n, st, out, nullptr);
       te_fell_back(ctx);
       return true;
     }
   }
-  run_chunk_impl<C, false>(ctx, d_scalars, base0, n, st, out, while_gpu_busy, carry);
+  run_chunk_impl<C, SwLaw<typename C::E>>(ctx, d_scalars, base0, n, st, out, while_gpu_busy, carry);
   return true;
 }
 
 // ---- anchored window: the sum of the bases of a run, and its multiples (see choose_window_bits) ------------------------------------
 // S = the sum of bases [0, n) (the ones not flagged infinite): k_sum_bases leaves one fragment per lane of 32..512 bases, the fragment merge
 // of the pipeline adds them up into bucket 0, k_collect_sums brings it (and the Edwards failure flag) to the host, the host tail turns it
-// into a point.  ~n mixed additions: 7 ms at 2^26.  TE = true returns false when an addition hit a vanishing denominator (bases outside
-// the prime-order subgroup): the caller repeats on the XYZZ records.
-template <class C, bool TE>
+// into a point.  ~n mixed additions: 7 ms at 2^26.  Under TeLaw it returns false when an addition hit a vanishing denominator (bases outside
+// the prime-order subgroup): the caller repeats on the XYZZ records.  Never paired: there is no such k_sum_bases, and the merge follows it.
+template <class C, class G>
 bool sum_bases_impl(mi355_msm_ctx* ctx, size_t n, hipStream_t st, typename HostTail<typename C::E>::Pt& S) {
-  using E = typename C::E;
-  using El = typename E::T;
+  using El = typename C::E::T;
   using XyzzDev = XyzzDevT<El>;
-  using SegOut = SegOutT<El>;
   constexpr uint32_t kSegK = 8;
   const uint32_t kPerLane = (uint32_t)std::min<size_t>(512, std::max<size_t>(32, n >> 17));   // ~2^17 lanes: a chip's worth, whatever n
   const uint32_t nlanes = ceil_div(n, kPerLane);
@@ -1408,47 +1462,22 @@ bool sum_bases_impl(mi355_msm_ctx* ctx, size_t n, hipStream_t st, typename HostT
     ctx->slots[k].reserve(2 * (size_t)nlanes * sizeof(XyzzDev));
     ctx->slot_keys[k].reserve(2 * (size_t)nlanes * sizeof(uint32_t));
   }
-  if (ctx->pinned_bytes < 64 * sizeof(XyzzDev)) {
-    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-    ctx->pinned_bytes = 64 * sizeof(XyzzDev);
-    HIP_OK(hipHostMalloc(&ctx->pinned, ctx->pinned_bytes, hipHostMallocDefault));
-  }
-  uint32_t* flags = ctx->flags.as<uint32_t>();
+  reserve_pinned(ctx, 1, sizeof(XyzzDev));
   HIP_OK(hipMemsetAsync(ctx->buckets.p, 0, sizeof(XyzzDev), st));   // the empty-bucket marker: no base at all
-  SegOut so{ctx->buckets.as<XyzzDev>(), ctx->slots[0].as<XyzzDev>(), ctx->slot_keys[0].as<uint32_t>()};
-  if constexpr (TE)
-    HIP_OK(LaunchTe::sum_bases(ctx->te_bases.as<TeAffineDev>(), ctx->inf.as<uint8_t>(), 0, (uint32_t)n, kPerLane, so, nlanes, flags, st));
-  else
-    HIP_OK(Launch<E>::sum_bases(ctx->bases.as<AffineDevT<El>>(), ctx->inf.as<uint8_t>(), 0, (uint32_t)n, kPerLane, so, nlanes, st));
-  uint32_t n_in = 2 * nlanes;
-  for (int cur = 0;; cur ^= 1) {
-    const uint32_t nl = ceil_div(n_in, kSegK);
-    SegOut o{ctx->buckets.as<XyzzDev>(), ctx->slots[cur ^ 1].as<XyzzDev>(), ctx->slot_keys[cur ^ 1].as<uint32_t>()};
-    if constexpr (TE)
-      HIP_OK(LaunchTe::segreduce(ctx->slots[cur].as<XyzzDev>(), ctx->slot_keys[cur].as<uint32_t>(), n_in, kSegK, o, nl, ctx->quad_limit, flags, st));
-    else
-      HIP_OK(Launch<E>::segreduce(ctx->slots[cur].as<XyzzDev>(), ctx->slot_keys[cur].as<uint32_t>(), n_in, kSegK, o, nl, ctx->quad_limit, st, false));
-    if (nl == 1) break;
-    n_in = 2 * nl;
-  }
-  const uint32_t row_u4 = sizeof(XyzzDev) / 16;
-  hipLaunchKernelGGL(k_collect_sums, dim3((row_u4 + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4*>(ctx->buckets.p), row_u4, row_u4, 1u,
-                     reinterpret_cast<uint4*>(ctx->pinned), TE ? flags : nullptr, TE ? ctx->h_flags : nullptr);
-  HIP_OK(hipGetLastError());
+  SegOutT<El> so{ctx->buckets.as<XyzzDev>(), ctx->slots[0].as<XyzzDev>(), ctx->slot_keys[0].as<uint32_t>()};
+  HIP_OK(WalkLaunch<G>::sum_bases(law_bases<G>(ctx), ctx->inf.as<uint8_t>(), 0, (uint32_t)n, kPerLane, so, nlanes, law_flags<G>(ctx), st));
+  merge_fragments<G>(ctx, nlanes, kSegK, 0, st);   // (at least one level, which leaves the sum in bucket 0)
+  collect_sums<G>(ctx, ctx->buckets.as<XyzzDev>(), 1, 1, st);
   HIP_OK(hipStreamSynchronize(st));
   const XyzzDev* hs = reinterpret_cast<const XyzzDev*>(ctx->pinned);
   bool empty = true;
   for (size_t k = 0; k < sizeof(XyzzDev); k++) empty = empty && reinterpret_cast<const uint8_t*>(hs)[k] == 0;
   if (empty) {
-    HostTail<E>::set_inf(S);
-    return !TE || ctx->h_flags[1] == 0;
+    HostTail<typename C::E>::set_inf(S);
+    return !kEdwards<G> || ctx->h_flags[1] == 0;
   }
   const XyzzT<El> sum = hs[0].p;
-  if constexpr (TE)
-    return ctx->h_flags[1] == 0 && HostTail<E>::fold_te(S, &sum, 1, 1);
-  else
-    HostTail<E>::fold(S, &sum, 1, 1);
-  return true;
+  return fold_sums<C, G>(ctx, S, &sum, 1, 1);
 }
 
 // Kept per context and n until the bases change.
@@ -1465,9 +1494,9 @@ void anchor_sum_of_bases(mi355_msm_ctx* ctx, size_t n, hipStream_t st, typename 
   const auto t0 = std::chrono::steady_clock::now();
   bool done = false;
   if constexpr (std::is_same_v<C, Bls12_377_G1>) {
-    if (ctx->te_active) done = sum_bases_impl<C, true>(ctx, n, st, S);   // (a failure here is not counted as a fallback of a run)
+    if (ctx->te_active) done = sum_bases_impl<C, TeLaw<TeFq>>(ctx, n, st, S);   // (a failure here is not counted as a fallback of a run)
   }
-  if (!done) sum_bases_impl<C, false>(ctx, n, st, S);
+  if (!done) sum_bases_impl<C, SwLaw<typename C::E>>(ctx, n, st, S);
   if (ctx->anchor_sums.size() >= 12) ctx->anchor_sums.erase(ctx->anchor_sums.begin(), ctx->anchor_sums.begin() + 4);
   mi355_msm_ctx::AnchorSum a{n, -1, std::vector<uint8_t>(sizeof S)};
   memcpy(a.pt.data(), &S, sizeof S);

@@ -64,7 +64,10 @@ def test_paired_special_cases(ea, oracle, torch_cuda, cid, c, rid):
     exp = _oracle_g2(oracle, bases, sc, n, cid)
     assert ctx.run(sc)[0] == exp
     ctx.set_option("max_chunk", n // 3 + 1)
-    assert ctx.run(sc)[0] == exp
+    for mask in (ALL, 16, 15):                # k_bucket_merge in either form beside kernels of the other
+        ctx.set_option("g2_paired", mask)
+        assert ctx.run(sc)[0] == exp, mask
+    ctx.set_option("g2_paired", ALL)
     ctx.set_option("max_chunk", 0)
     ctx.set_option("window_bits", 4)          # 8 buckets per window: P and -P meet, runs of hundreds
     assert ctx.run(sc)[0] == exp
