@@ -35,6 +35,7 @@ from .msm import (  # noqa: F401
     mul_points_by,
     mul_by_cofactor,
     Radix2EvaluationDomain,
+    SparseMatrix,
 )
 from .dist import all_gather_partials, shard_bounds, sharded_msm  # noqa: F401,E402
 from . import formats  # noqa: F401,E402

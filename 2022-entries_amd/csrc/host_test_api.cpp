@@ -1592,6 +1592,67 @@ int ht_quotient_linear_combination(int field, unsigned flags, unsigned m, const 
 }
 }
 
+// ---- sparse matrices and y = M z (sparse.hpp): the plan create derives, the coefficients slot by slot, and the chain of launches the
+// engine runs, every lane in order --------------------------------------------------------------------------------------------------
+#include "sparse.hpp"
+
+template <class FR>
+struct HostSparseRun {
+  uint32_t tile_log;
+  void z(const SparseZ& p) {
+    for (uint32_t i = 0; i < p.cols; i++) sparse_z_elem<FR>(p, i);
+  }
+  void totals(const SparseRun& p) {
+    for (uint32_t t = 0; t < p.m.nlanes; t++) sparse_total<FR>(p, t);
+  }
+  void rows(const SparseRun& p) {
+    for (uint32_t t = 0; t < p.m.nlanes; t++) sparse_rows_lane<FR>(p, t);
+  }
+  void cross(const SparseRun& p) {
+    for (uint32_t r = 0; r < p.m.rows; r++) sparse_cross_row<FR>(p, r);
+  }
+  void scan(uint32_t* v, uint64_t n) {
+    std::vector<Fr> work(scan_work_elems(n, tile_log));
+    HostScanRun<FR> run;
+    scan_chain<FR, kScanSum>(run, v, v, nullptr, n, false, false, tile_log, work.data());
+  }
+};
+
+template <class FR>
+static int t_sparse_apply(uint32_t tile_log, unsigned create_flags, unsigned flags, uint64_t rows, uint64_t cols, const uint64_t* row_ptr,
+                          const uint32_t* col_idx, const uint8_t* values, const uint8_t* z, uint8_t* out) {
+  char why[256];
+  if (!sparse_validate(rows, cols, row_ptr, col_idx, why, sizeof why)) return -1;
+  SparsePlan pl;
+  sparse_plan(pl, rows, row_ptr, col_idx);
+  std::vector<uint32_t> raw((size_t)pl.nnz * 8 + 8), vals((size_t)pl.slots * 8 + 8), zz(cols * 8 + 8), dst(rows * 8 + 8, 0xa5a5a5a5u);
+  if (pl.nnz) memcpy(raw.data(), values, (size_t)pl.nnz * 32);
+  if (cols) memcpy(zz.data(), z, cols * 32);
+  const SparseVals vp{raw.data(), vals.data(), pl.nnz, pl.slots, (create_flags & kSparseNormal) ? 1u : 0u};
+  for (uint32_t s = 0; s < pl.slots; s++) sparse_val_slot<FR>(vp, s);
+  const SparseMat m{vals.data(),  pl.col.data(), pl.ne_end.data(), pl.ne_row.data(), pl.lane_row.data(), pl.row_ptr.data(),
+                    (uint32_t)rows, (uint32_t)cols, pl.nnz,        pl.nne,           pl.nlanes,          pl.slots};
+  std::vector<uint64_t> work(sparse_work_bytes(cols, pl.nlanes) / 8 + 4);
+  void* w32 = (void*)(((uintptr_t)work.data() + 31) & ~(uintptr_t)31);
+  HostSparseRun<FR> run{tile_log};
+  sparse_chain<FR>(run, m, dst.data(), zz.data(), (flags & kSparseNormal) != 0, w32);
+  if (rows) memcpy(out, dst.data(), rows * 32);
+  return 0;
+}
+
+extern "C" {
+// mi355_msm_sparse_create + _apply on the host: create_flags bit 0, the values are plain integers; flags bit 0, z and out are plain integers
+unsigned ht_sparse_entries_per_lane(void) { return SPARSE_E; }
+unsigned ht_sparse_block_lanes(void) { return SPARSE_LANES; }
+int ht_sparse_apply(int field, unsigned tile_log, unsigned create_flags, unsigned flags, uint64_t rows, uint64_t cols, const uint64_t* row_ptr,
+                    const uint32_t* col_idx, const uint8_t* values, const uint8_t* z, uint8_t* out) {
+  if (tile_log < POLY_TILE_LOG_MIN || tile_log > POLY_TILE_LOG_MAX || (create_flags & ~kSparseNormal) || (flags & ~kSparseNormal) || rows > ((uint64_t)1 << 20) ||
+      cols > ((uint64_t)1 << 20) || !row_ptr || row_ptr[rows] > ((uint64_t)1 << 22) || (row_ptr[rows] && (!col_idx || !values)) || (cols && !z) || (rows && !out))
+    return -1;
+  return POLY_FIELD(t_sparse_apply, tile_log, create_flags, flags, rows, cols, row_ptr, col_idx, values, z, out);
+}
+}
+
 // ---- transforms of vectors of points (group_fft.hpp) with the limb-bound checker armed ------------------------------------------
 // The SAME MSM_HD functions the kernels of kernels_gfft.hip wrap: the index maps, the twiddle exponent, the twiddle and the factor as
 // canonical words, the table of a butterfly's B, the walk and the butterfly; records by fb_host_records, the vector between two

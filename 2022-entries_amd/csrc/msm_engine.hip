@@ -2813,4 +2813,5 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 #include "msm_poly.hpp"
 #include "msm_scan.hpp"
 #include "msm_quot.hpp"
+#include "msm_sparse.hpp"
 #include "msm_gfft.hpp"

@@ -159,6 +159,10 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_domain_plonk_quotient_device": [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, ctypes.c_uint, vp],
         "mi355_msm_domain_linear_combination": [vp, vp, vp, vp, vp, sz, ctypes.c_uint],
         "mi355_msm_domain_linear_combination_device": [vp, vp, vp, vp, vp, sz, ctypes.c_uint, vp],
+        "mi355_msm_sparse_create": [ctypes.POINTER(vp), vp, sz, sz, vp, vp, vp, ctypes.c_uint],
+        "mi355_msm_sparse_apply": [vp, vp, vp, ctypes.c_uint, vp],
+        "mi355_msm_sparse_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_sparse_destroy": [vp],
         "mi355_msm_trim": [],
         "mi355_msm_pool_stats": [ctypes.POINTER(ctypes.c_uint64), sz],
     }
@@ -1443,6 +1447,58 @@ class Radix2EvaluationDomain:
         _check(self._lib.mi355_msm_domain_linear_combination(self.handle, ob.ptr if n else None, ptrs, lv, cb, m, flags))
         return _like_input(cols[lens.index(n)], res, (n, 32))
 
+    # ---- resident sparse matrices and Groth16's witness map (mi355_msm_sparse_*) -----------------------------------------------------
+
+    def sparse_matrix(self, rows, cols, row_ptr, col_idx, values, montgomery: bool = True) -> "SparseMatrix":
+        """A CSR matrix over this domain's field, uploaded once and kept on this domain's device: ``row_ptr`` (``rows + 1`` offsets) and
+        ``col_idx`` (``nnz`` indices) as integer arrays (NumPy, torch CPU, or bytes of little-endian uint64 / uint32), ``values`` as
+        ``nnz`` 32-byte elements (bytes, NumPy or torch CPU).  Duplicate columns in a row are summed.  The domain must outlive the
+        matrix; the matrix keeps a reference to it."""
+        return SparseMatrix(self, rows, cols, row_ptr, col_idx, values, montgomery=montgomery)
+
+    def groth16_witness_map(self, A, B, z, num_inputs, montgomery: bool = True):
+        """ark-groth16's ``LibsnarkReduction::witness_map`` from the full assignment ``z`` to the ``size`` coefficients of ``h``, with the
+        R1CS matrices ``A`` and ``B`` as ``SparseMatrix`` on this domain: ``a = A z`` with ``z[0 .. num_inputs)`` appended at rows
+        ``n .. n + num_inputs`` (``n = A.rows`` constraints), ``b = B z``, ``c = a * b`` element by element, all zero-padded to ``size``;
+        ``h = coset_ifft((coset_fft(ifft(a)) * coset_fft(ifft(b)) - coset_fft(ifft(c))) / Z(g))``.  With a GPU tensor in, every step
+        runs on the tensor's current stream and the result is a GPU tensor that ``MultiScalarMultContext.run`` takes as it is; nothing
+        but ``z`` comes from the host and nothing goes back."""
+        if not self.handle:
+            raise MsmError(-1, "the domain is closed")
+        n, ni = int(A.rows), int(num_inputs)
+        if B.rows != n or A.cols != B.cols:
+            raise ValueError(f"A is {A.rows} x {A.cols} and B is {B.rows} x {B.cols}: the two matrices must agree in shape")
+        if ni < 0 or ni > A.cols or n + ni > self.size:
+            raise ValueError(f"{n} constraints and {ni} inputs do not fit a domain of {self.size} points (or exceed the {A.cols} variables)")
+        if not (hasattr(z, "data_ptr") and hasattr(z, "is_cuda") and z.is_cuda):
+            import numpy as np
+
+            z = np.frombuffer(_flat_bytes(z), dtype=np.uint8)
+            if z.size != A.cols * 32:
+                raise ValueError(f"z: {A.cols} 32-byte elements, shape ({A.cols}, 32)")
+            z = z.reshape(A.cols, 32)
+            a = np.zeros((self.size, 32), dtype=np.uint8)
+            b = np.zeros((self.size, 32), dtype=np.uint8)
+            a[:n] = A.apply(z, montgomery=montgomery)
+            b[:n] = B.apply(z, montgomery=montgomery)
+        else:
+            import torch
+
+            if tuple(z.shape) != (A.cols, 32):
+                raise ValueError(f"z: {A.cols} 32-byte elements, shape ({A.cols}, 32), not {tuple(z.shape)}")
+            z = z.contiguous()
+            a = torch.zeros((self.size, 32), dtype=torch.uint8, device=z.device)
+            b = torch.zeros((self.size, 32), dtype=torch.uint8, device=z.device)
+            A.apply(z, montgomery=montgomery, out=a[:n])
+            B.apply(z, montgomery=montgomery, out=b[:n])
+        a[n:n + ni] = z[:ni]
+        kw = dict(montgomery=montgomery)
+        c = self.mul(a, b, **kw)
+        ea, eb, ec = (self.coset_fft(self.ifft(v, **kw), **kw) for v in (a, b, c))
+        h = self.mul_sub(ea, eb, ec, **kw)
+        h = self.divide_by_vanishing_poly_on_coset(h, **kw)
+        return self.coset_ifft(h, **kw)
+
     def set_option(self, key: str, value: int) -> None:
         _check(self._lib.mi355_msm_domain_set_option(self.handle, key.encode(), int(value)))
 
@@ -1457,6 +1513,121 @@ class Radix2EvaluationDomain:
     def close(self) -> None:
         if self.handle:
             _check(self._lib.mi355_msm_domain_destroy(self.handle))
+            self.handle = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _index_array(obj, dtype, what):
+    """a contiguous NumPy array of `dtype` from an integer array (NumPy, torch CPU, a list) or little-endian bytes of that type"""
+    import numpy as np
+
+    if hasattr(obj, "data_ptr") and hasattr(obj, "is_cuda"):
+        if obj.is_cuda:
+            raise ValueError(f"{what}: the structure of a matrix is read from host memory")
+        obj = obj.numpy()
+    if isinstance(obj, (bytes, bytearray, memoryview)):
+        if len(obj) % np.dtype(dtype).itemsize:
+            raise ValueError(f"{what}: not a whole number of {np.dtype(dtype).itemsize}-byte integers")
+        return np.frombuffer(bytes(obj), dtype=dtype)
+    return np.ascontiguousarray(np.asarray(obj).reshape(-1), dtype=dtype)
+
+
+class SparseMatrix:
+    """A sparse matrix over ``Fr`` resident on one GPU (mi355_msm_sparse_*): the R1CS matrices of a proving key, uploaded once like the
+    bases of an MSM.  ``apply(z)`` is ``y = M z``.  Made by ``Radix2EvaluationDomain.sparse_matrix`` or ``SparseMatrix.from_rows``."""
+
+    def __init__(self, dom, rows, cols, row_ptr, col_idx, values, montgomery: bool = True):
+        import numpy as np
+
+        self.handle = ctypes.c_void_p()
+        self.dom = dom
+        if not dom.handle:
+            raise MsmError(-1, "the domain is closed")
+        self._lib = dom._lib
+        rows, cols = int(rows), int(cols)
+        if rows < 0 or cols < 0:
+            raise ValueError("rows and cols must not be negative")
+        rp = _index_array(row_ptr, np.uint64, "row_ptr")
+        ci = _index_array(col_idx, np.uint32, "col_idx")
+        if rp.size != rows + 1:
+            raise ValueError(f"row_ptr: {rows + 1} offsets for {rows} rows, not {rp.size}")
+        vb = _Buf(values)
+        if vb.is_device:
+            raise ValueError("values: the coefficients of a matrix are read from host memory")
+        if vb.nbytes != ci.size * 32:
+            raise ValueError(f"values: {ci.size} 32-byte elements beside {ci.size} column indices, not {vb.nbytes} bytes")
+        _check(self._lib.mi355_msm_sparse_create(ctypes.byref(self.handle), dom.handle, rows, cols, rp.ctypes.data, ci.ctypes.data if ci.size else None,
+                                                 vb.ptr if ci.size else None, 0 if montgomery else 1))
+        self.rows, self.cols, self.nnz = self.query("rows"), self.query("cols"), self.query("nnz")
+
+    @classmethod
+    def from_rows(cls, dom, rows_list, cols) -> "SparseMatrix":
+        """arkworks' ``Matrix<F> = Vec<Vec<(F, usize)>>``: a list of rows, each a list of ``(coefficient as an integer, column)``"""
+        import numpy as np
+
+        row_ptr, col_idx, vals = [0], [], []
+        for row in rows_list:
+            for coeff, col in row:
+                col_idx.append(int(col))
+                vals.append((int(coeff) % dom.modulus).to_bytes(32, "little"))
+            row_ptr.append(len(col_idx))
+        if any(c < 0 or c >= 1 << 32 for c in col_idx):
+            raise ValueError("a column index is out of range")
+        return cls(dom, len(row_ptr) - 1, cols, np.array(row_ptr, dtype=np.uint64), np.array(col_idx, dtype=np.uint32), b"".join(vals), montgomery=False)
+
+    def apply(self, z, montgomery: bool = True, out=None):
+        """``y = M z``: ``z`` holds ``cols`` 32-byte elements.  Bytes or NumPy in gives a NumPy array ``(rows, 32)``; a torch GPU tensor of
+        shape ``(cols, 32)`` is read in place on its current stream and gives a GPU tensor (``out=``: one of shape ``(rows, 32)`` to write
+        into, which must not overlap ``z``).  ``montgomery`` is the form of ``z`` and of the result, whatever the form given at creation."""
+        if not self.handle:
+            raise MsmError(-1, "the matrix is closed")
+        shape = getattr(z, "shape", None)
+        b = _Buf(z)
+        if b.nbytes != self.cols * 32 or (shape is not None and tuple(shape) != (self.cols, 32)):
+            raise ValueError(f"z: {self.cols} 32-byte elements, shape ({self.cols}, 32), not {tuple(shape) if shape is not None else b.nbytes}")
+        flags = 0 if montgomery else 1
+        if b.is_device:
+            import torch
+
+            if b.device_index != self.dom.device:
+                raise MsmError(-1, f"the input lives on cuda:{b.device_index} but this matrix is bound to device {self.dom.device}")
+            if out is None:
+                out = torch.empty((self.rows, 32), dtype=torch.uint8, device=b.keep.device)
+            if tuple(getattr(out, "shape", ())) != (self.rows, 32):
+                raise ValueError(f"out: a contiguous uint8 GPU tensor of shape ({self.rows}, 32)")
+            ob = _Buf(out)
+            if not ob.is_device or ob.keep is not out:
+                raise ValueError(f"out: a contiguous uint8 GPU tensor of shape ({self.rows}, 32)")
+            _check(self._lib.mi355_msm_sparse_apply(self.handle, ob.ptr if self.rows else None, b.ptr if self.cols else None, flags | 2, b.stream))
+            return out
+        if out is not None:
+            raise ValueError("out= goes with GPU tensors")
+        import numpy as np
+
+        res = np.zeros((self.rows, 32), dtype=np.uint8)
+        _check(self._lib.mi355_msm_sparse_apply(self.handle, res.ctypes.data if self.rows else None, b.ptr if self.cols else None, flags, None))
+        return res
+
+    def query(self, key: str) -> int:
+        """ "rows", "cols", "nnz", "entries_per_lane", "block_lanes", "work_bytes" """
+        v = ctypes.c_uint64(0)
+        _check(self._lib.mi355_msm_sparse_query(self.handle, key.encode(), ctypes.byref(v)))
+        return int(v.value)
+
+    def close(self) -> None:
+        if self.handle:
+            _check(self._lib.mi355_msm_sparse_destroy(self.handle))
             self.handle = ctypes.c_void_p()
 
     def __enter__(self):

@@ -622,6 +622,48 @@ RustError mi355_msm_domain_linear_combination(mi355_msm_domain* d, void* out, co
 RustError mi355_msm_domain_linear_combination_device(mi355_msm_domain* d, void* d_out, const void* const* d_cols, const size_t* lens,
                                                      const void* coeffs, size_t m, unsigned flags, void* stream);
 
+/* ---- resident sparse matrices over Fr and y = M z (Groth16's witness map) ------------------------------------------------------------
+ * The vectors a[i] = <A_i, z> and b[i] = <B_i, z> that open a Groth16 or Marlin prover: the rows of the R1CS matrices times the full
+ * assignment (ark-groth16's evaluate_constraint loop over arkworks' Matrix<F>).  The matrices belong to the proving key, so like the
+ * bases of an MSM they are uploaded once and kept; what changes per proof is z.
+ *   create  CSR in HOST memory: row_ptr holds rows + 1 offsets (8-byte aligned), nnz = row_ptr[rows]; col_idx (4-byte aligned) and
+ *           values hold nnz entries, a value being one 32-byte element: an arkworks Fr image or, with flag bit 0 (the only flag), a
+ *           plain integer.  ANY 256-bit value is read as its residue.  Duplicate columns within a row are allowed and summed; zero
+ *           coefficients, empty rows, rows == 0 and nnz == 0 are allowed.  rows, cols <= 2^30, nnz <= 2^31.  The field, the device, the
+ *           stream of host-pointer calls and the work memory of the sum scan are those of the domain d, WHICH MUST OUTLIVE THE MATRIX;
+ *           the vector lengths have nothing to do with the domain's size.  The structure is validated on the host before any device
+ *           call: row_ptr[0] == 0, row_ptr non-decreasing, every col_idx < cols; a violation is -1 with a message that names the first
+ *           offending row.  The call uploads once, converts the coefficients, synchronises and returns a handle that any number of
+ *           apply calls reuse.
+ *   apply   out[i] = sum_k values[k] * z[col_idx[k]] over the entries of row i: reads cols elements of z, writes rows canonical
+ *           elements of out (an empty row gives 0; rows == 0 writes nothing).  Flag bit 0: z and out are plain integers -- the form of
+ *           the call is independent of the form given at create.  Flag bit 1 (value 2): out and z are DEVICE pointers (4-byte
+ *           aligned) and `stream` is the hipStream_t on which z becomes ready (NULL = the default stream): the work is enqueued there
+ *           and the call returns when out is written, as the device-pointer calls of the domain do.  Without bit 1 both are host
+ *           pointers, staged through buffers the matrix keeps, and a non-null stream is an error.  Any overlap of out and z is refused.
+ *   query   "rows", "cols", "nnz"; "entries_per_lane" and "block_lanes", the constants E and L of the kernels (answered without a
+ *           handle too); "work_bytes", everything the matrix holds on the device.
+ * One apply with a flag bit, and no twin whose name ends in _device: every such name in this header stands in the table of
+ * tests/stream_cases.py with the test that pins its stream order, and tests/test_stream_coverage.py keeps the two equal.  The
+ * stream-ordering promise of flag bit 1 is the same one and is pinned by a late-producer test of its own in tests/test_gpu_sparse.py,
+ * written with the helpers of stream_cases.
+ * Scheme (csrc/sparse.hpp).  R1CS rows are badly skewed, so no kernel is per row: every lane handles E consecutive entries of the CSR
+ * arrays, whatever rows they belong to.  create stores the coefficients as canonical Montgomery values of 32 bytes in a lane-interleaved
+ * order, and per lane the row that is open at its first entry.  apply is five launches on one stream: z to class M, once per column;
+ * the sum of every lane's E products; the exclusive prefix sum of the lane totals (the sum scan above); the lanes again, which write
+ * every row that begins and ends inside a lane and leave the running sum where a row crosses a lane boundary; one lane per row for
+ * those rows and the empty ones.  No block waits on another, nothing is atomic.  Sums in Fr are exact: results are canonical and never
+ * depend on "poly_tile_log", on host versus device pointers or on the form of the call.  There is no CPU fallback.
+ * Errors: -1 with a message, decided before any device call, in this order: unknown flag bits, sizes above their limits, null
+ * pointers, alignment, a stream without flag bit 1, an output that overlaps z, the structure (create), and last the null handle
+ * (create: the domain); the extent of an overlap is judged against the handle. */
+typedef struct mi355_msm_sparse mi355_msm_sparse;
+RustError mi355_msm_sparse_create(mi355_msm_sparse** out, mi355_msm_domain* d, size_t rows, size_t cols, const uint64_t* row_ptr,
+                                  const uint32_t* col_idx, const void* values, unsigned flags);
+RustError mi355_msm_sparse_apply(mi355_msm_sparse* m, void* out, const void* z, unsigned flags, void* stream);
+RustError mi355_msm_sparse_query(mi355_msm_sparse* m, const char* key, uint64_t* value);
+RustError mi355_msm_sparse_destroy(mi355_msm_sparse* m);
+
 /* ---- transforms of vectors of curve points over a domain (ARK poly/src/domain/mod.rs:99-170 on DomainCoeff = G1Projective / G2Projective) ----
  * domain.fft / ifft / coset_fft / coset_ifft on GROUP elements: what turns a monomial SRS [tau^j] G into the Lagrange SRS
  * [L_i(tau)] G (kind 1), and the transform behind FK20, cq and Caulk tables.  With in[j] a point and the products scalar multiples:

@@ -408,6 +408,53 @@ struct Radix2EvaluationDomain {
   }
 };
 
+// arkworks' Matrix<F> = Vec<Vec<(F, usize)>> resident on the GPU (mi355_msm_sparse_*): the R1CS matrices of a proving key, uploaded once
+// on a domain that outlives them; apply is y = M z, the evaluate_constraint loop of ark-groth16's witness map.  CSR: row_ptr holds
+// rows + 1 offsets, col_idx and values one entry per coefficient (Fr values in Montgomery form).
+struct SparseMatrix {
+  mi355_msm_sparse* handle = nullptr;
+  SparseMatrix(const Radix2EvaluationDomain& dom, size_t rows, size_t cols, const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx,
+               const std::vector<BigInteger256>& values) {
+    check(mi355_msm_sparse_create(&handle, dom.handle, rows, cols, row_ptr.data(), col_idx.data(), values.data(), 0));
+  }
+  SparseMatrix(const SparseMatrix&) = delete;
+  SparseMatrix& operator=(const SparseMatrix&) = delete;
+  SparseMatrix(SparseMatrix&& o) noexcept : handle(o.handle) { o.handle = nullptr; }
+  uint64_t query(const char* key) const {
+    uint64_t v = 0;
+    check(mi355_msm_sparse_query(handle, key, &v));
+    return v;
+  }
+  size_t rows() const { return (size_t)query("rows"); }
+  size_t cols() const { return (size_t)query("cols"); }
+  // y[i] = sum_k values[k] * z[col_idx[k]] over the entries of row i; z holds cols() elements
+  std::vector<BigInteger256> apply(const std::vector<BigInteger256>& z) const {
+    std::vector<BigInteger256> out(rows());
+    check(mi355_msm_sparse_apply(handle, out.data(), z.data(), 0, nullptr));
+    return out;
+  }
+  ~SparseMatrix() {
+    if (handle) {
+      RustError e = mi355_msm_sparse_destroy(handle);
+      if (e.message) std::free(e.message);
+    }
+  }
+};
+
+// ark-groth16's LibsnarkReduction::witness_map on host vectors, from the full assignment z to the size() coefficients of h: a = A z with
+// z[0 .. num_inputs) appended behind the constraints, b = B z, c = a * b element by element, all zero-padded to the domain;
+// h = coset_ifft((coset_fft(ifft(a)) * coset_fft(ifft(b)) - coset_fft(ifft(c))) / Z(g)).  (The Python layer keeps every step in device memory.)
+inline std::vector<BigInteger256> groth16_witness_map(const Radix2EvaluationDomain& dom, const SparseMatrix& A, const SparseMatrix& B,
+                                                      const std::vector<BigInteger256>& z, size_t num_inputs) {
+  std::vector<BigInteger256> a = A.apply(z), b = B.apply(z);
+  a.insert(a.end(), z.begin(), z.begin() + num_inputs);
+  a.resize(dom.size());
+  b.resize(dom.size());
+  const std::vector<BigInteger256> c = dom.mul(a, b);
+  const std::vector<BigInteger256> h = dom.mul_sub(dom.coset_fft(dom.ifft(a)), dom.coset_fft(dom.ifft(b)), dom.coset_fft(dom.ifft(c)));
+  return dom.coset_ifft(dom.divide_by_vanishing_poly_on_coset(h));
+}
+
 // domain.fft / ifft / coset_fft / coset_ifft on a vector of G1 points (mi355_msm_fft_points): kind 0 .. 3 as for Fr; `points` may be
 // shorter than the domain (the rest is the point at infinity); offset NULL: GENERATOR.  Affine images out, ready for
 // multi_scalar_mult_init -- kind 1 on a monomial SRS [tau^j] G gives the Lagrange SRS [L_i(tau)] G.

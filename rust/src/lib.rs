@@ -241,6 +241,14 @@ pub mod sys {
                                                    coeffs: *const c_void, m: usize, flags: c_uint) -> Error;
         pub fn mi355_msm_domain_linear_combination_device(d: *mut c_void, d_out: *mut c_void, d_cols: *const *const c_void, lens: *const usize,
                                                           coeffs: *const c_void, m: usize, flags: c_uint, stream: *mut c_void) -> Error;
+        // resident sparse matrices over Fr (the R1CS matrices of a proving key) on a domain handle, which must outlive them: CSR in host
+        // memory at create (flags bit 0: the values are plain integers); apply flags bit 0: z and out are plain integers, bit 1 (value
+        // 2): out and z are device pointers and `stream` is where z becomes ready, else host pointers and a null stream
+        pub fn mi355_msm_sparse_create(out: *mut *mut c_void, d: *mut c_void, rows: usize, cols: usize, row_ptr: *const u64, col_idx: *const u32,
+                                       values: *const c_void, flags: c_uint) -> Error;
+        pub fn mi355_msm_sparse_apply(m: *mut c_void, out: *mut c_void, z: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_sparse_query(m: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
+        pub fn mi355_msm_sparse_destroy(m: *mut c_void) -> Error;
         // the same four transforms on a vector of curve points (ark-poly's domains over DomainCoeff = G1Projective / G2Projective):
         // Affine images in and out (flags bit 1: Projective images out), offset: one arkworks Fr image on the host or null
         pub fn mi355_msm_fft_points(ctx: *mut c_void, domain: *mut c_void, out: *mut c_void, out_stride: usize, input: *const c_void, in_len: usize,
@@ -628,6 +636,67 @@ pub mod fixed_base {
             check(unsafe {
                 sys::mi355_msm_fixed_mul(table.0, out.as_mut_ptr() as *mut c_void, std::mem::size_of::<G1Affine>(), v.as_ptr() as *const c_void,
                                          v.len(), SCALARS_MONTGOMERY)
+            });
+            out
+        }
+    }
+}
+
+/// arkworks' `Matrix<F> = Vec<Vec<(F, usize)>>` resident on the GPU (`mi355_msm_sparse_*`): the R1CS matrices of a proving key are
+/// uploaded once, like the bases of an MSM, and `apply` is `y = M z` -- the `evaluate_constraint` loop of ark-groth16's witness map.
+pub mod sparse {
+    use super::sys;
+    use super::Fr;
+    use ark_std::Zero;
+    use std::os::raw::c_void;
+
+    fn check(err: super::Error) {
+        if err.code != 0 {
+            panic!("{}", String::from(err));
+        }
+    }
+
+    /// Lives on a domain handle of `sys::mi355_msm_domain_create`, which the caller keeps alive for as long as the matrix.
+    pub struct SparseMatrix {
+        handle: *mut c_void,
+        pub rows: usize,
+        pub cols: usize,
+    }
+
+    impl Drop for SparseMatrix {
+        fn drop(&mut self) {
+            if !self.handle.is_null() {
+                let _ = unsafe { sys::mi355_msm_sparse_destroy(self.handle) };
+            }
+        }
+    }
+
+    impl SparseMatrix {
+        /// # Safety
+        /// `domain` is a live handle of `sys::mi355_msm_domain_create` over the field of `Fr` and outlives the matrix.
+        pub unsafe fn new(domain: *mut c_void, matrix: &[Vec<(Fr, usize)>], cols: usize) -> Self {
+            let mut row_ptr: Vec<u64> = vec![0];
+            let mut col_idx: Vec<u32> = Vec::new();
+            let mut values: Vec<Fr> = Vec::new();
+            for row in matrix {
+                for (coeff, col) in row {
+                    values.push(*coeff);
+                    col_idx.push(*col as u32);
+                }
+                row_ptr.push(values.len() as u64);
+            }
+            let mut handle: *mut c_void = std::ptr::null_mut();
+            check(sys::mi355_msm_sparse_create(&mut handle, domain, matrix.len(), cols, row_ptr.as_ptr(), col_idx.as_ptr(),
+                                               values.as_ptr() as *const c_void, 0));
+            SparseMatrix { handle, rows: matrix.len(), cols }
+        }
+
+        /// `y[i] = sum_k coeff_k * z[col_k]` over the entries of row `i`; `z` holds `cols` elements
+        pub fn apply(&self, z: &[Fr]) -> Vec<Fr> {
+            assert_eq!(z.len(), self.cols, "z holds one element per column");
+            let mut out = vec![Fr::zero(); self.rows];
+            check(unsafe {
+                sys::mi355_msm_sparse_apply(self.handle, out.as_mut_ptr() as *mut c_void, z.as_ptr() as *const c_void, 0, std::ptr::null_mut())
             });
             out
         }

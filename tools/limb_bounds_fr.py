@@ -20,6 +20,7 @@ All margins must be positive (tests/test_fr_consts.py runs it); the host build c
     python tools/limb_bounds_fr.py --poly     (the chains of csrc/poly.hpp: analyse_poly below)
     python tools/limb_bounds_fr.py --scan     (the sum scan and the permutation product of csrc/scan.hpp: analyse_scan below)
     python tools/limb_bounds_fr.py --quotient (the rows of the Plonk quotient and the linear combination of csrc/quotient.hpp: analyse_quotient below)
+    python tools/limb_bounds_fr.py --sparse   (the lane sums of the sparse matrix-vector product of csrc/sparse.hpp: analyse_sparse below)
 """
 import sys
 
@@ -312,8 +313,78 @@ def analyse_quotient(name, r, out):
     return ok
 
 
+SPARSE_ENTRIES = 16     # SPARSE_E of csrc/sparse.hpp: the entries a lane sums before it reduces
+
+
+def analyse_sparse(name, r, out):
+    """The chains of csrc/sparse.hpp (python tools/limb_bounds_fr.py --sparse), carried exactly as sparse_total and sparse_rows_lane
+    perform them.  z is converted once (any 256-bit input times a canonical constant) and every entry is one product of that class-M
+    value by a canonical coefficient.  A lane adds SPARSE_ENTRIES such products, with one carry pass after each: `loc` from zero, `run`
+    from the class-M value of a canonical prefix.  Either sum is then the first operand of a product by a canonical constant (the
+    conversion on the way out, the product by 1 into bstart / bend).  A row that crosses lanes is bend + BIAS4 - bstart, carried and
+    converted.  The largest column of every product must stay below 2^64."""
+    import math
+
+    rl = limbs(r)
+    ok = True
+    worst_col = 0
+
+    def margin(what, have, limit):
+        nonlocal ok
+        m = limit - have
+        ok &= m > 0
+        out.append("  %-78s %s (limit 2^%.2f, margin %.3e)" % (what, "ok " if m > 0 else "BAD", math.log2(limit), m))
+
+    top_m = (2 * r) >> (B * (N - 1))
+    class_m = [MASK] * (N - 1) + [top_m]
+    w = [MASK] * (N - 1) + [rl[N - 1]]
+    any256 = [MASK] * (N - 1) + [(1 << (256 - B * (N - 1))) - 1]
+    bias = bias4(r)
+
+    def first_operand(what, l, val, second):
+        nonlocal worst_col
+        col = max(columns(l, second, rl))
+        worst_col = max(worst_col, col)
+        margin(what + ": value %dr against R" % val, val * r, R)
+        margin(what + ": largest limb against 2^31", max(l), 1 << 31)
+        margin(what + ": largest column against 2^64", col, 1 << 64)
+        sec_val = 2 * r if second is class_m else r
+        margin(what + ": product r + a b / R against 2r", r + val * r * sec_val // R + 1, 2 * r)
+
+    def add(what, a, b):
+        sm = [x + y for x, y in zip(a, b)]
+        margin(what + ": limb-wise sum against 2^32", max(sm), 1 << 32)
+        margin(what + ": top limb into the carry pass against 2^31", sm[N - 1] + (sm[N - 2] >> B), 1 << 31)
+        return carry_pass(sm)
+
+    out.append("%s: r = %.3f * 2^252, R / r = %.2f  (the chains of sparse.hpp, %d entries a lane)" % (name, r / 2**252, R / r, SPARSE_ENTRIES))
+    margin("2r against a packed element (2^256)", 2 * r, 1 << 256)
+    first_operand("z or a coefficient on the way in: any 256-bit value times a canonical constant", any256, -(-(1 << 256) // r), w)
+    first_operand("an entry: z in class M times a canonical coefficient", class_m, 2, w)
+    loc, run, lv, rv = [0] * N, list(class_m), 0, 2
+    for e in range(SPARSE_ENTRIES):
+        loc = add("loc, entry %2d" % e, loc, class_m)
+        run = add("run, entry %2d (from a canonical prefix in class M)" % e, run, class_m)
+        lv += 2
+        rv += 2
+    first_operand("a lane total or a row inside a lane as the first operand of the conversion", loc, lv, w)
+    first_operand("the running sum as the first operand of the product by 1 (bstart, bend)", run, rv, w)
+    for i in range(N):
+        margin("BIAS4 limb %d covers the limb of bstart" % i, class_m[i], bias[i] + 1)
+    diff = add("a crossing row: bend + 4r - bstart", class_m, bias)
+    first_operand("a crossing row as the first operand of the conversion", diff, 6, w)
+    margin("the chain's largest column against 2^64", worst_col, 1 << 64)
+    out.append("  largest column: %d = 2^%.3f" % (worst_col, math.log2(worst_col)))
+    return ok
+
+
 def main():
     out = []
+    if "--sparse" in sys.argv[1:]:
+        ok = all([analyse_sparse(name, r, out) for name, r in FIELDS.items()])
+        print("\n".join(out))
+        print("all margins positive" if ok else "A MARGIN IS NOT POSITIVE")
+        return 0 if ok else 1
     if "--quotient" in sys.argv[1:]:
         ok = all([analyse_quotient(name, r, out) for name, r in FIELDS.items()])
         print("\n".join(out))
