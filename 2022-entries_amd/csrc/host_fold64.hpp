@@ -421,14 +421,23 @@ inline void xyzz64_from_device(const FC& f, XyzzG64<typename FC::El>& r, const X
 }
 
 // result = sum_w 2^(c w) sums[w]   (Horner, high to low)
+// `wide_a` >= 0 (a wide anchored window, partition_plan.hpp part_plan; wide_a + 2 == windows): rows wide_a and wide_a + 1 are the two bucket
+// sets of ONE digit window and share its weight 2^(c wide_a); the buckets of the upper set weigh 2^(c-1) more than their reduction gave
+// them, and sums[windows] is their plain sum R: result = sum_(w < a) 2^(c w) sums[w] + 2^(c a) (sums[a] + sums[a+1] + 2^(c-1) R).
 template <class F, class FC, class DevEl>
-inline void fold_windows64(const FC& f, XyzzG64<typename FC::El>& acc, const XyzzT<DevEl>* sums, int windows, int c) {
+inline void fold_windows64(const FC& f, XyzzG64<typename FC::El>& acc, const XyzzT<DevEl>* sums, int windows, int c, int wide_a = -1) {
   sw64_set_inf(acc);
   for (int w = windows - 1; w >= 0; w--) {
-    for (int i = 0; i < c; i++) sw64_dbl(f, acc);
+    if (w != wide_a)
+      for (int i = 0; i < c; i++) sw64_dbl(f, acc);
     XyzzG64<typename FC::El> s;
     xyzz64_from_device<F>(f, s, sums[w]);
     sw64_add(f, acc, s);
+    if (wide_a >= 0 && w == wide_a + 1) {
+      xyzz64_from_device<F>(f, s, sums[windows]);
+      for (int i = 0; i < c - 1; i++) sw64_dbl(f, s);
+      sw64_add(f, acc, s);
+    }
   }
 }
 
@@ -481,18 +490,26 @@ inline bool te64_dbl(const Fp64& f, Xyzz64& a) {
 // false: a vanishing denominator was hit (possible only off the odd-order subgroup) -- the caller repeats on XYZZ.
 // FD = the field constants whose limb shape the device sums are in (Bls12_377_Fq29 when the Edwards kernels run on 13 x 29 limbs).
 template <class F, class FD = F>
-inline bool fold_windows_te64(const Fp64& f, Xyzz64& out, const Xyzz* sums, int windows, int c) {
+// `wide_a`: as fold_windows64.
+inline bool fold_windows_te64(const Fp64& f, Xyzz64& out, const Xyzz* sums, int windows, int c, int wide_a = -1) {
   Xyzz64 acc{};
   acc.y = f.one;
   acc.zz = f.one;   // identity (0, 1, 1, 0)
   for (int w = windows - 1; w >= 0; w--) {
-    if (w != windows - 1)
+    if (w != windows - 1 && w != wide_a)
       for (int i = 0; i < c; i++)
         if (!te64_dbl(f, acc)) return false;
     Xyzz64 s;
     xyzz64_from_device<FD>(f, s, sums[w]);
     if (f.is_zero(s.zz)) return false;
     if (!te64_add(f, acc, s)) return false;
+    if (wide_a >= 0 && w == wide_a + 1) {
+      xyzz64_from_device<FD>(f, s, sums[windows]);
+      if (f.is_zero(s.zz)) return false;
+      for (int i = 0; i < c - 1; i++)
+        if (!te64_dbl(f, s)) return false;
+      if (!te64_add(f, acc, s)) return false;
+    }
   }
   // (0, 1) -> infinity, (0, -1) -> the 2-torsion point (-1, 0); otherwise u = (Z + Y)/(Z - Y), v = FSC u Z / X
   if (f.is_zero(acc.x)) {

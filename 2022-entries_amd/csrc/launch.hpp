@@ -70,7 +70,8 @@ struct WalkLaunch {
   static hipError_t segreduce(const XyzzDevT<El>* in_slots, const uint32_t* in_keys, uint32_t n_in, uint32_t K, SegOutT<El> out, uint32_t nlanes,
                               uint32_t quad_limit, uint32_t* flags, hipStream_t st);
   static hipError_t bucket_reduce(bool first, const XyzzDevT<El>* in_a, const XyzzDevT<El>* in_x, uint32_t n_per_win, uint32_t L, uint32_t chunks,
-                                  uint32_t windows, uint32_t out_stride, XyzzDevT<El>* out_a, XyzzDevT<El>* out_x, uint32_t* flags, hipStream_t st);
+                                  uint32_t windows, uint32_t out_stride, XyzzDevT<El>* out_a, XyzzDevT<El>* out_x, uint32_t* flags, hipStream_t st,
+                                  uint32_t run_win = 0xffffffffu);   // (first level: this window's plain chunk sums become the A of row `windows`)
   // small windows: one step of the scan-based reduction (k_reduce_scan_step)
   static hipError_t reduce_scan_step(const XyzzDevT<El>* in, const XyzzDevT<El>* in2, XyzzDevT<El>* out, uint32_t nb, uint32_t windows, uint32_t d,
                                      uint32_t mode, uint32_t quad_limit, uint32_t* flags, hipStream_t st);

@@ -102,12 +102,13 @@ hipError_t WalkLaunch<G>::segreduce(const XyzzDevT<El>* in_slots, const uint32_t
 
 template <class G>
 hipError_t WalkLaunch<G>::bucket_reduce(bool first, const XyzzDevT<El>* in_a, const XyzzDevT<El>* in_x, uint32_t n_per_win, uint32_t L, uint32_t chunks,
-                                        uint32_t windows, uint32_t out_stride, XyzzDevT<El>* out_a, XyzzDevT<El>* out_x, uint32_t* flags, hipStream_t st) {
+                                        uint32_t windows, uint32_t out_stride, XyzzDevT<El>* out_a, XyzzDevT<El>* out_x, uint32_t* flags, hipStream_t st,
+                                        uint32_t run_win) {
   dim3 grid(walk_blocks<G>((uint64_t)windows * chunks));
   if (first)
-    hipLaunchKernelGGL((k_bucket_reduce<G, true>), grid, dim3(256), 0, st, in_a, in_x, n_per_win, L, chunks, windows, out_stride, out_a, out_x, flags);
+    hipLaunchKernelGGL((k_bucket_reduce<G, true>), grid, dim3(256), 0, st, in_a, in_x, n_per_win, L, chunks, windows, out_stride, out_a, out_x, flags, run_win);
   else
-    hipLaunchKernelGGL((k_bucket_reduce<G, false>), grid, dim3(256), 0, st, in_a, in_x, n_per_win, L, chunks, windows, out_stride, out_a, out_x, flags);
+    hipLaunchKernelGGL((k_bucket_reduce<G, false>), grid, dim3(256), 0, st, in_a, in_x, n_per_win, L, chunks, windows, out_stride, out_a, out_x, flags, run_win);
   return hipGetLastError();
 }
 
@@ -149,7 +150,7 @@ hipError_t WalkLaunch<G>::bucket_merge(XyzzDevT<El>* total, const XyzzDevT<El>* 
   template hipError_t W_::segreduce(const X_*, const uint32_t*, uint32_t, uint32_t, S_, uint32_t, uint32_t, uint32_t*, hipStream_t);             \
   template hipError_t Launch<E>::pre_double(const A_*, const uint8_t*, uint32_t, uint32_t, X_*, hipStream_t);                                    \
   template hipError_t Launch<E>::pre_normalize(const X_*, uint32_t, uint32_t, E::T*, A_*, uint8_t*, hipStream_t);                                \
-  template hipError_t W_::bucket_reduce(bool, const X_*, const X_*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, X_*, X_*, uint32_t*, hipStream_t); \
+  template hipError_t W_::bucket_reduce(bool, const X_*, const X_*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, X_*, X_*, uint32_t*, hipStream_t, uint32_t); \
   template hipError_t W_::reduce_scan_step(const X_*, const X_*, X_*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, hipStream_t); \
   template hipError_t W_::bucket_merge(X_*, const X_*, uint32_t, uint32_t*, hipStream_t);                                                        \
   template hipError_t W_::sum_bases(const A_*, const uint8_t*, uint32_t, uint32_t, uint32_t, S_, uint32_t, uint32_t*, hipStream_t);

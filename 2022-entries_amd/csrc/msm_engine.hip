@@ -257,6 +257,17 @@ uint32_t anchor_window(int c, int scalar_bits, bool always = false) {
   return (always || (plain - anchored) >= 0.01 * plain) ? (uint32_t)(full - 1) : kNoAnchor;
 }
 
+// The wide anchored window (round 7; partition_plan.hpp, part_plan): the anchored window a also carries the scalar's top bit where exactly ONE
+// bit of r lies above it -- bits(r) - (a + 1) c == 1: BLS12-377's Fr where c divides 252 (6, 7, 9, 12, 14, 18, 21); never BLS12-381's (255 = 15 x 17) -- and that bit's
+// window is the last one (so that its bucket set can take the large magnitudes).  A function of c and the curve alone: every chunk of a
+// carried batch decides alike.
+bool anchor_wide_fits(uint32_t anchor, int c, int scalar_bits) {
+  if (anchor == kNoAnchor) return false;
+  return scalar_bits - (int)(anchor + 1) * c == 1 && (257 + c - 1) / c == (int)anchor + 2;
+}
+// additions per scalar with it: a + 1 digit windows, each zero once in 2^c (the wide one once in 2^(c+1))
+double wide_eff_windows(uint32_t anchor, int c) { return (double)(anchor + 1) * (1.0 - std::ldexp(1.0, -c)); }
+
 // Window size.  Cost model in field-multiply units: one mixed add (10) per non-zero digit, ~50 per bucket for the
 // bucket->window reduction (measured: 0.79 ns/bucket vs 0.15 ns/add).  Canonical scalars have `scalar_bits` bits, so the
 // top window is only partly populated: with `rem` significant bits left it behaves like a full window, with none it
@@ -265,7 +276,8 @@ uint32_t anchor_window(int c, int scalar_bits, bool always = false) {
 // `levels` = precomputed table levels k (0: none; >= windows: one bucket set for all): windows g, g + G, ... share bucket set g,
 // G = ceil(windows / k) sets exist.
 // `anchor_min_c` (0: plain digits): window sizes from this one on are priced with their anchored window, where they have one.
-int choose_window_bits(size_t n, int scalar_bits, bool shared_buckets, bool fold = false, int levels = 0, int anchor_min_c = 0) {
+// `anchor_wide`: ... and with the wide anchored window where that fits.
+int choose_window_bits(size_t n, int scalar_bits, bool shared_buckets, bool fold = false, int levels = 0, int anchor_min_c = 0, bool anchor_wide = false) {
   // Between 2^12 and 2^19 pairs an MSM is latency, not throughput: what a window size costs is the launches it implies
   // (two scan steps of the bucket reduction per bit, a grouping pass more from 12 bits on, per-window steps of the level-1
   // tiles) and the model below does not see them.  Measured on all three curves (tools/small_c_sweep.py,
@@ -299,6 +311,7 @@ int choose_window_bits(size_t n, int scalar_bits, bool shared_buckets, bool fold
     if (anchor_min_c > 0 && !fold && c >= anchor_min_c && anchor_window(c, scalar_bits) != kNoAnchor) {
       double plain;
       eff_windows(scalar_bits, c, plain, eff);
+      if (anchor_wide && !shared_buckets && anchor_wide_fits(anchor_window(c, scalar_bits), c, scalar_bits)) eff = wide_eff_windows(anchor_window(c, scalar_bits), c);
     }
     const int wins = (257 + c - 1) / c;
     const double alloc = shared_buckets ? (double)(levels > 0 ? (wins + std::min(levels, wins) - 1) / std::min(levels, wins) : 1) : (double)wins;
@@ -331,6 +344,7 @@ struct Plan {
   uint32_t bucket_windows;  // windows that own buckets: `windows`; with precomputed tables the bucket sets G = ceil(windows / levels)
   uint32_t levels;          // table levels in use (1 = none)
   uint32_t anchor;          // the anchored window (kNoAnchor: plain signed digits)
+  bool wide;                // ... which also carries the scalar's top bit (anchor_wide_fits): bucket set anchor + 1 holds its large magnitudes
   uint64_t entries;     // windows * n
   uint32_t K, nlanes;   // accumulate geometry
   uint32_t segK;        // fragment-merge fan-in
@@ -401,6 +415,15 @@ struct mi355_msm_ctx {
   uint64_t anchor_sums_computed = 0;
   float anchor_sum_ms = 0;        // host wall time the most recent run spent computing such a sum (0: it was at hand)
   uint32_t last_anchor = kNoAnchor;   // the anchored window of the most recent chunk
+  long opt_anchor_wide = 1;       // option "anchor_wide": 1 = the anchored window carries the scalar's top bit where anchor_wide_fits; 0 = round 6's recoding
+  bool wide_suppress = false;     // ... not in the repeat of a chunk or batch whose scalars had bits above bits(r)
+  bool wide_overflowed = false;   // the chunk just run met such a scalar: its result is void (run_chunk)
+  bool wide_off = false;          // two repeats in a row: this context stops using it
+  uint32_t wide_streak = 0;
+  uint64_t wide_fallbacks = 0, wide_demotions = 0;
+  bool last_wide = false;         // the most recent chunk ran with it
+  DevBuf wide_flag, wide_r;       // the device flag word of k_l1_hist; direct scan: the plain sum of bucket set anchor + 1
+  uint32_t* h_wide_flag = nullptr;   // pinned copy (k_collect_sums)
   long opt_reduce_log_chunk = 0, opt_reduce_log_chunk0 = 0;
   long opt_reduce_scan = -1;      // 0: recursive chunked running sums only; otherwise the scan tail (default)
   long opt_reduce_fill = 0;       // waves per SIMD the first chunked level of the bucket reduction is cut for (0 = the default, 1)
@@ -452,6 +475,7 @@ struct mi355_msm_ctx {
   bool anchor_wanted(size_t n_batch) const {
     return opt_anchor != 0 && opt_carry != 0 && opt_assume_subgroup == 0 && n_batch >= (opt_anchor == 2 ? (size_t)1 : (size_t)1 << 20);
   }
+  bool wide_wanted() const { return opt_anchor_wide != 0 && !wide_off && !wide_suppress; }
 
   // use_tables = false plans the run WITHOUT the precomputed tables of this context (the XYZZ fallback of a
   // twisted-Edwards context, whose short-Weierstrass tables were dropped)
@@ -465,8 +489,9 @@ struct mi355_msm_ctx {
       p.c = force_c;
     else
       p.c = (opt_window_bits && !pre_c) ? (uint32_t)opt_window_bits
-                                        : (uint32_t)choose_window_bits(n, scalar_bits(), false, opt_assume_subgroup != 0, 0, anchor_wanted(n) ? anchor_min_c() : 0);
+                                        : (uint32_t)choose_window_bits(n, scalar_bits(), false, opt_assume_subgroup != 0, 0, anchor_wanted(n) ? anchor_min_c() : 0, wide_wanted());
     p.anchor = anchor_armed ? anchor_window((int)p.c, scalar_bits(), opt_anchor == 2) : kNoAnchor;
+    p.wide = wide_wanted() && !tables && anchor_wide_fits(p.anchor, (int)p.c, scalar_bits());
     p.windows = (257 + p.c - 1) / p.c;
     p.levels = tables ? std::min<uint32_t>(pre_windows, p.windows) : 1;
     p.bucket_windows = ceil_div(p.windows, p.levels);
@@ -496,7 +521,11 @@ struct mi355_msm_ctx {
       eff_windows(scalar_bits(), (int)p.c, plain, anchored);
       // (a plan made outside a run -- mi355_msm_plan, the chunk fit -- expects the anchored window wherever a run would use it)
       const bool anchor_expected = (anchor_armed || anchor_wanted(n)) && anchor_window((int)p.c, scalar_bits(), opt_anchor == 2) != kNoAnchor;
-      const double adds = (anchor_expected ? anchored : plain) * (double)n;
+      // (a wide anchored window has fewer entries still: 12 (1 - 2^-21) n at c = 21 are 24.00 groups of K = 512 where 12.143 n took K = 520 for 23.91 --
+      //  the same 24 generations, each 8 entries shorter: 85.0 -> 83.9 ms same-box, profiles/ab_anchor_wide.txt)
+      const uint32_t a_expected = anchor_expected ? anchor_window((int)p.c, scalar_bits(), opt_anchor == 2) : kNoAnchor;
+      const bool wide_expected = wide_wanted() && !tables && anchor_wide_fits(a_expected, (int)p.c, scalar_bits());
+      const double adds = (wide_expected ? wide_eff_windows(a_expected, (int)p.c) : anchor_expected ? anchored : plain) * (double)n;
       const double per_group = ((curve == MI355_BLS12_377_G2 || curve == MI355_BLS12_381_G2) && (opt_g2_paired & 1) ? 128.0 : 256.0) * 256.0;
       auto fill = [&](long k) {
         const double g = adds / ((double)k * per_group);
@@ -611,7 +640,7 @@ uint64_t work_bytes(const Plan& p, uint64_t el, bool carry = false) {
   const PartPlan pp = part_plan((uint32_t)(p.entries / p.windows), p.c, p.windows, p.levels, 0, 0);
   const PartScratchSizes ps = part_scratch_sizes(pp);
   return p.entries * 16 + ps.matrix + ps.partial + ps.segs_a + ps.segs_b + ps.subjob_first + ps.counts + ps.totals +
-         (uint64_t)p.bucket_windows * p.half * 224 * el * (carry ? 2 : 1) + 2 * (2ull * p.nlanes) * (224 * el + 4) + (p.scan_direct ? (uint64_t)p.bucket_windows * p.half : 4ull * p.bucket_windows * p.scan_nb) * 224 * el;
+         (uint64_t)p.bucket_windows * p.half * 224 * el * (carry ? 2 : 1) + 2 * (2ull * p.nlanes) * (224 * el + 4) + (p.scan_direct ? (uint64_t)p.bucket_windows * p.half : 4ull * (p.bucket_windows + (p.wide ? 1 : 0)) * p.scan_nb) * 224 * el;
 }
 
 DevBuf* const* work_buffers(mi355_msm_ctx* ctx, size_t& count) {
@@ -639,7 +668,8 @@ WorkBytes chunk_work_bytes(const Plan& p, size_t n, bool use_tables, size_t xyzz
   const PartPlan gp = part_plan((uint32_t)n, p.c, p.windows, use_tables ? p.levels : 1, 0, 0);
   const PartScratchSizes gs = part_scratch_sizes(gp);
   const size_t nbuckets = (size_t)p.bucket_windows * p.half, nslots0 = 2 * (size_t)p.nlanes;
-  const size_t red0 = p.scan_direct ? nbuckets : (size_t)p.bucket_windows * p.scan_nb;   // direct scan: a second bucket-sized array to ping-pong with
+  // direct scan: a second bucket-sized array to ping-pong with; a wide anchored window: one more row, the plain sums of its upper bucket set
+  const size_t red0 = p.scan_direct ? nbuckets : (size_t)(p.bucket_windows + (p.wide ? 1 : 0)) * p.scan_nb;
   w.b[0] = w.b[1] = p.entries * 8 + 64;
   w.b[2] = gs.matrix;
   w.b[3] = gs.partial;
@@ -871,6 +901,7 @@ int precompute_auto_levels(mi355_msm_ctx* ctx, size_t n) {
     tmp.opt_window_bits = ctx->opt_window_bits;
     tmp.opt_assume_subgroup = ctx->opt_assume_subgroup;
     tmp.opt_anchor = ctx->opt_anchor;
+    tmp.opt_anchor_wide = ctx->opt_anchor_wide;
     tmp.opt_carry = ctx->opt_carry;
     tmp.opt_lane_entries = ctx->opt_lane_entries;
     tmp.opt_seg_entries = ctx->opt_seg_entries;
@@ -1049,7 +1080,7 @@ struct HostTail<Fp2El<F, NB>> {   // G2: the same code over Fp2
   static void set_inf(Pt& a) { sw64_set_inf(a); }
   static void add(Pt& a, const Pt& b) { sw64_add(fp2_64_of<F, NB>(), a, b); }
   static void dbl(Pt& a) { sw64_dbl(fp2_64_of<F, NB>(), a); }
-  static void fold(Pt& out, const XyzzT<Fe2>* sums, int windows, int c) { fold_windows64<F>(fp2_64_of<F, NB>(), out, sums, windows, c); }
+  static void fold(Pt& out, const XyzzT<Fe2>* sums, int windows, int c, int wide_a = -1) { fold_windows64<F>(fp2_64_of<F, NB>(), out, sums, windows, c, wide_a); }
   static void to_abi(uint8_t* out, const Pt& a) { sw64_to_abi(fp2_64_of<F, NB>(), out, a); }
 };
 template <class F>
@@ -1058,13 +1089,13 @@ struct HostTail<FpEl<F>> {
   static void set_inf(Pt& a) { sw64_set_inf(a); }
   static void add(Pt& a, const Pt& b) { sw64_add(fp64_of<F>(), a, b); }
   static void dbl(Pt& a) { sw64_dbl(fp64_of<F>(), a); }
-  static void fold(Pt& out, const Xyzz* sums, int windows, int c) { fold_windows64<F>(fp64_of<F>(), out, sums, windows, c); }
+  static void fold(Pt& out, const Xyzz* sums, int windows, int c, int wide_a = -1) { fold_windows64<F>(fp64_of<F>(), out, sums, windows, c, wide_a); }
   // (the Edwards kernels hold their points in the limb shape of TeFq: te.hpp)
-  static bool fold_te(Pt& out, const Xyzz* sums, int windows, int c) {
+  static bool fold_te(Pt& out, const Xyzz* sums, int windows, int c, int wide_a = -1) {
     if constexpr (std::is_same_v<F, Bls12_377_Fq>)
-      return fold_windows_te64<F, TeFq>(fp64_of<F>(), out, sums, windows, c);
+      return fold_windows_te64<F, TeFq>(fp64_of<F>(), out, sums, windows, c, wide_a);
     else
-      return fold_windows_te64<F>(fp64_of<F>(), out, sums, windows, c);
+      return fold_windows_te64<F>(fp64_of<F>(), out, sums, windows, c, wide_a);
   }
   static void to_abi(uint8_t* out, const Pt& a) { sw64_to_abi(fp64_of<F>(), out, a); }
 };
@@ -1073,11 +1104,20 @@ struct HostTail<FpEl<F>> {
 // them, flag 1 re-armed: one tiny kernel instead of a 2-D copy, a copy and a memset -- the runtime's copy path alone left a
 // 22-us hole in the timeline of a small MSM (tools/gap_probe.py).
 __global__ void __launch_bounds__(256) k_collect_sums(const uint4* __restrict__ src, uint32_t row_stride_u4, uint32_t row_u4, uint32_t rows,
-                                                      uint4* __restrict__ dst_host, uint32_t* __restrict__ flags, uint32_t* __restrict__ flags_host) {
+                                                      uint4* __restrict__ dst_host, uint32_t* __restrict__ flags, uint32_t* __restrict__ flags_host,
+                                                      const uint4* __restrict__ extra = nullptr, uint32_t* __restrict__ wide_flag = nullptr,
+                                                      uint32_t* __restrict__ wide_flag_host = nullptr) {
+  // `extra`: one more row that lies elsewhere (the plain sum a wide anchored window needs); `wide_flag`: handed over and re-armed like flag 1
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i < rows * row_u4) {
     const uint32_t r = i / row_u4, c = i - r * row_u4;
     dst_host[i] = src[(size_t)r * row_stride_u4 + c];
+  } else if (extra && i < (rows + 1) * row_u4) {
+    dst_host[i] = extra[i - rows * row_u4];
+  }
+  if (wide_flag && i == 0) {
+    wide_flag_host[0] = wide_flag[0];
+    wide_flag[0] = 0;
   }
   if (flags_host && i == 0) {
     flags_host[0] = flags[0];
@@ -1229,16 +1269,22 @@ XyzzDevT<typename LawMem<G>::MemT>* accumulate_chunk(mi355_msm_ctx* ctx, const P
 }
 
 // Buckets -> one point per window.  The W window sums end up in element 0 of rows of the returned array that are `sums_stride` elements apart.
+// A wide anchored window (p.wide) also needs R, the PLAIN sum of bucket set anchor + 1 (its buckets weigh 2^(c-1) more than their index): `r_src`.
+// The first chunked level holds every chunk's plain sum anyway (k_bucket_reduce, run_win); those enter the levels that follow as one more row
+// with empty X, whose "window sum" is R.  A direct scan has R in element 0 of the set's row once the suffix scan is through.
 template <class G>
 const XyzzDevT<typename LawMem<G>::MemT>* reduce_buckets(mi355_msm_ctx* ctx, const Plan& p, XyzzDevT<typename LawMem<G>::MemT>* bucket_src, hipStream_t st,
-                                                         uint32_t& sums_stride) {
+                                                         uint32_t& sums_stride, const XyzzDevT<typename LawMem<G>::MemT>*& r_src) {
   using XyzzDev = XyzzDevT<typename LawMem<G>::MemT>;
   uint32_t* const flags = law_flags<G>(ctx);
+  r_src = nullptr;
+  const uint32_t run_win = p.wide ? p.anchor + 1 : 0xffffffffu;
+  const uint32_t rows = p.bucket_windows + (p.wide ? 1 : 0);   // ... of every level after the first
   // one chunked level: windows x chunks walkers, each over L elements of its window's n_per_win
   auto bucket_reduce = [&](bool first, const XyzzDev* in_a, const XyzzDev* in_x, uint32_t n_per_win, uint32_t L, uint32_t chunks, uint32_t out_stride, int to) {
     HIP_OK(walk_form<G>(ctx, 2, false, [&]<class W>() {
-      return WalkLaunch<W>::bucket_reduce(first, in_a, in_x, n_per_win, L, chunks, p.bucket_windows, out_stride, ctx->red_a[to].as<XyzzDev>(),
-                                          ctx->red_x[to].as<XyzzDev>(), flags, st);
+      return WalkLaunch<W>::bucket_reduce(first, in_a, in_x, n_per_win, L, chunks, first ? p.bucket_windows : rows, out_stride, ctx->red_a[to].as<XyzzDev>(),
+                                          ctx->red_x[to].as<XyzzDev>(), flags, st, first ? run_win : 0xffffffffu);
     }));
   };
   if (p.reduce_scan) {
@@ -1250,8 +1296,11 @@ const XyzzDevT<typename LawMem<G>::MemT>* reduce_buckets(mi355_msm_ctx* ctx, con
     if (!p.scan_direct) {
       if (p.scan_nb != p.T0) {
         // rows of scan_nb elements, T0 of them written: the rest must read as empty
-        HIP_OK(hipMemsetAsync(ctx->red_a[0].p, 0, (size_t)p.bucket_windows * p.scan_nb * sizeof(XyzzDev), st));
-        HIP_OK(hipMemsetAsync(ctx->red_x[0].p, 0, (size_t)p.bucket_windows * p.scan_nb * sizeof(XyzzDev), st));
+        HIP_OK(hipMemsetAsync(ctx->red_a[0].p, 0, (size_t)rows * p.scan_nb * sizeof(XyzzDev), st));
+        HIP_OK(hipMemsetAsync(ctx->red_x[0].p, 0, (size_t)rows * p.scan_nb * sizeof(XyzzDev), st));
+      } else if (p.wide) {
+        // the X of the row of plain sums: empty
+        HIP_OK(hipMemsetAsync(ctx->red_x[0].as<XyzzDev>() + (size_t)p.bucket_windows * p.scan_nb, 0, (size_t)p.scan_nb * sizeof(XyzzDev), st));
       }
       bucket_reduce(true, nullptr, bucket_src, p.half, p.L0, p.T0, p.scan_nb, 0);
       nb = p.scan_nb;
@@ -1260,25 +1309,34 @@ const XyzzDevT<typename LawMem<G>::MemT>* reduce_buckets(mi355_msm_ctx* ctx, con
       bufs[1] = ctx->red_x[1].as<XyzzDev>();
     }
     int cur = 0;
+    const uint32_t scan_rows = a_sums ? rows : p.bucket_windows;
     auto step = [&](uint32_t d, uint32_t mode) {
-      const bool small = (uint64_t)p.bucket_windows * (mode == 1 ? d : nb) <= ctx->quad_limit;
+      const bool small = (uint64_t)scan_rows * (mode == 1 ? d : nb) <= ctx->quad_limit;
       HIP_OK(walk_form<G>(ctx, 8, small, [&]<class W>() {
-        return WalkLaunch<W>::reduce_scan_step(bufs[cur], a_sums, bufs[cur ^ 1], nb, p.bucket_windows, d, mode, ctx->quad_limit, flags, st);
+        return WalkLaunch<W>::reduce_scan_step(bufs[cur], a_sums, bufs[cur ^ 1], nb, scan_rows, d, mode, ctx->quad_limit, flags, st);
       }));
       cur ^= 1;
     };
     for (uint32_t d = 1; d < nb; d <<= 1) step(d, 0);
     if (a_sums) step(0, 2);
+    if (p.wide && !a_sums) {
+      // direct scan: element 0 of a row is now the plain sum of its buckets (a single bucket: the bucket itself)
+      ctx->wide_r.reserve(sizeof(XyzzDev));
+      HIP_OK(hipMemcpyAsync(ctx->wide_r.p, bufs[cur] + (size_t)run_win * nb, sizeof(XyzzDev), hipMemcpyDeviceToDevice, st));
+      r_src = ctx->wide_r.as<XyzzDev>();
+    }
     if (nb & (nb - 1)) bad_arg("scan reduction needs a power-of-two element count per window (%u)", nb);
     for (uint32_t h = nb >> 1; h >= 1; h >>= 1) step(h, 1);   // out_j = in_j + in_(j+h) for j < h
     if (nb == 1 && !a_sums) step(1, 0);   // a single bucket per window: one pass that normalises an empty bucket to the identity
     // the window sums sit at the head of each window's row
     sums_stride = nb;
+    if (p.wide && a_sums) r_src = bufs[cur] + (size_t)p.bucket_windows * nb;
     return bufs[cur];
   }
   uint32_t n_per_win = p.half, logL = p.logL0, chunks = p.T0;
   int rb = 0;
   bucket_reduce(true, nullptr, bucket_src, n_per_win, 1u << logL, chunks, chunks, 0);
+  if (p.wide && chunks > 1) HIP_OK(hipMemsetAsync(ctx->red_x[0].as<XyzzDev>() + (size_t)p.bucket_windows * chunks, 0, (size_t)chunks * sizeof(XyzzDev), st));
   while (chunks > 1) {
     n_per_win = chunks;
     logL = p.logL;
@@ -1287,37 +1345,43 @@ const XyzzDevT<typename LawMem<G>::MemT>* reduce_buckets(mi355_msm_ctx* ctx, con
     rb ^= 1;
   }
   sums_stride = 1;
+  if (p.wide) r_src = ctx->red_a[rb].as<XyzzDev>() + p.bucket_windows;
   return ctx->red_a[rb].as<XyzzDev>();
 }
 
 // `rows` window sums -> ctx->pinned, with the flag words of a law that can fail -> ctx->h_flags
+// (`r_src`: a wide anchored window's plain sum, row `rows` on the host, and its flag word -> ctx->h_wide_flag)
 template <class G>
-void collect_sums(mi355_msm_ctx* ctx, const XyzzDevT<typename LawMem<G>::MemT>* src, uint32_t stride, uint32_t rows, hipStream_t st) {
+void collect_sums(mi355_msm_ctx* ctx, const XyzzDevT<typename LawMem<G>::MemT>* src, uint32_t stride, uint32_t rows, hipStream_t st,
+                  const XyzzDevT<typename LawMem<G>::MemT>* r_src = nullptr) {
   using XyzzDev = XyzzDevT<typename LawMem<G>::MemT>;
   static_assert(sizeof(XyzzDev) % 16 == 0, "window sums are collected in 16-byte pieces");
-  const uint32_t row_u4 = sizeof(XyzzDev) / 16, total = rows * row_u4;
+  const uint32_t row_u4 = sizeof(XyzzDev) / 16, total = (rows + (r_src ? 1 : 0)) * row_u4;
   hipLaunchKernelGGL(k_collect_sums, dim3((total + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4*>(src), stride * row_u4, row_u4, rows,
-                     reinterpret_cast<uint4*>(ctx->pinned), law_flags<G>(ctx), kEdwards<G> ? ctx->h_flags : nullptr);
+                     reinterpret_cast<uint4*>(ctx->pinned), law_flags<G>(ctx), kEdwards<G> ? ctx->h_flags : nullptr,
+                     reinterpret_cast<const uint4*>(r_src), r_src ? ctx->wide_flag.as<uint32_t>() : nullptr, r_src ? ctx->h_wide_flag : nullptr);
   HIP_OK(hipGetLastError());
 }
 
 // the host tail over collected sums; false when the law reported an addition it could not compute (h_flags) or the fold meets one
 template <class C, class G>
-bool fold_sums(mi355_msm_ctx* ctx, typename HostTail<typename C::E>::Pt& out, const XyzzT<typename C::E::T>* sums, int windows, int c) {
+// (`wide_a` >= 0: rows wide_a and wide_a + 1 are the two bucket sets of a wide anchored window and row `windows` is the plain sum of the upper one)
+bool fold_sums(mi355_msm_ctx* ctx, typename HostTail<typename C::E>::Pt& out, const XyzzT<typename C::E::T>* sums, int windows, int c, int wide_a = -1) {
   if constexpr (kEdwards<G>) {
-    return ctx->h_flags[1] == 0 && HostTail<typename C::E>::fold_te(out, sums, windows, c);
+    return ctx->h_flags[1] == 0 && HostTail<typename C::E>::fold_te(out, sums, windows, c, wide_a);
   } else {
-    HostTail<typename C::E>::fold(out, sums, windows, c);
+    HostTail<typename C::E>::fold(out, sums, windows, c, wide_a);
     return true;
   }
 }
 
 // Window sums -> the folded chunk sum in `out`: collect (ev[6] behind it), wait, fold, stage times.
 template <class C, class G>
-bool finish_chunk(mi355_msm_ctx* ctx, const Plan& p, const XyzzDevT<typename C::E::T>* sums_src, uint32_t sums_stride, hipStream_t st, hipEvent_t* ev,
+bool finish_chunk(mi355_msm_ctx* ctx, const Plan& p, const XyzzDevT<typename C::E::T>* sums_src, uint32_t sums_stride,
+                  const XyzzDevT<typename C::E::T>* r_src, hipStream_t st, hipEvent_t* ev,
                   const BucketCarry* carry, const std::function<void()>* while_gpu_busy, typename HostTail<typename C::E>::Pt& out) {
   using XyzzDev = XyzzDevT<typename C::E::T>;
-  collect_sums<G>(ctx, sums_src, sums_stride, p.bucket_windows, st);
+  collect_sums<G>(ctx, sums_src, sums_stride, p.bucket_windows, st, r_src);
   HIP_OK(hipEventRecord(ev[6], st));
   // everything for this chunk is enqueued: host work that should hide behind it (the next batch's H2D copy) goes here
   if (while_gpu_busy) (*while_gpu_busy)();
@@ -1333,11 +1397,14 @@ bool finish_chunk(mi355_msm_ctx* ctx, const Plan& p, const XyzzDevT<typename C::
   }
   HIP_OK(hipStreamSynchronize(st));
 
-  std::vector<XyzzT<typename C::E::T>> sums(p.bucket_windows);
+  const uint32_t nsums = p.bucket_windows + (r_src ? 1 : 0);
+  std::vector<XyzzT<typename C::E::T>> sums(nsums);
   const XyzzDev* hs = reinterpret_cast<const XyzzDev*>(ctx->pinned);
-  for (uint32_t w = 0; w < p.bucket_windows; w++) sums[w] = hs[w].p;
+  for (uint32_t w = 0; w < nsums; w++) sums[w] = hs[w].p;
   const auto t_fold = std::chrono::steady_clock::now();
-  const bool ok = fold_sums<C, G>(ctx, out, sums.data(), (int)p.bucket_windows, (int)p.c);
+  // a scalar with bits above bits(r) under a wide anchored window: those bits were not read, the sums are void (run_chunk repeats)
+  ctx->wide_overflowed = r_src && ctx->h_wide_flag[0] != 0;
+  const bool ok = !ctx->wide_overflowed && fold_sums<C, G>(ctx, out, sums.data(), (int)p.bucket_windows, (int)p.c, r_src ? (int)p.anchor : -1);
   ctx->last_ms[MI355_T_HOST_FOLD] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_fold).count();
 
   // stage times: of this chunk, or of every chunk of the carried batch (their events have all completed by now)
@@ -1373,12 +1440,24 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
   }
   reserve_work(ctx, chunk_work_bytes(p, n, use_tables, sizeof(XyzzDev), carry != nullptr));
   const uint32_t table_stride = use_tables ? (uint32_t)ctx->nbases : 0u;
-  const PartPlan gp = part_plan((uint32_t)n, p.c, p.windows, use_tables ? p.levels : 1, (uint32_t)base0, table_stride, ctx->opt_assume_subgroup != 0, p.anchor);
+  const PartPlan gp = part_plan((uint32_t)n, p.c, p.windows, use_tables ? p.levels : 1, (uint32_t)base0, table_stride, ctx->opt_assume_subgroup != 0, p.anchor, p.wide);
+  if ((gp.wide != 0) != p.wide) throw HipFailure(-2, "mi355_msm: the plan and the grouping disagree about the wide anchored window (internal error)");
   ctx->last_anchor = gp.anchor;
-  reserve_pinned(ctx, p.windows, sizeof(XyzzDev));
+  ctx->last_wide = p.wide;
+  reserve_pinned(ctx, p.windows + 1, sizeof(XyzzDev));
+  if (p.wide) {
+    if (!ctx->h_wide_flag) {
+      HIP_OK(hipHostMalloc((void**)&ctx->h_wide_flag, sizeof(uint32_t), hipHostMallocDefault));
+      ctx->h_wide_flag[0] = 0;
+    }
+    ctx->wide_flag.reserve(sizeof(uint32_t));
+    // (armed here and not only by k_collect_sums: a batch that was given up half-way must not leave its flag to the next one)
+    if (!carry || carry->first) HIP_OK(hipMemsetAsync(ctx->wide_flag.p, 0, sizeof(uint32_t), st));
+  }
 
   HIP_OK(hipEventRecord(ev[0], st));
   PartBuffers gb{};
+  gb.wide_flag = p.wide ? ctx->wide_flag.as<uint32_t>() : nullptr;
   const uint2* entries = group_chunk(ctx, d_scalars, gp, gb, st, ev[1]);
   XyzzDev* const bucket_src = accumulate_chunk<G>(ctx, p, gp, gb, entries, carry, st, ev);
   HIP_OK(hipEventRecord(ev[4], st));
@@ -1406,9 +1485,10 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
     return true;
   }
   uint32_t sums_stride = 1;
-  const XyzzDev* sums_src = reduce_buckets<G>(ctx, p, bucket_src, st, sums_stride);
+  const XyzzDev* r_src = nullptr;
+  const XyzzDev* sums_src = reduce_buckets<G>(ctx, p, bucket_src, st, sums_stride, r_src);
   HIP_OK(hipEventRecord(ev[5], st));
-  return finish_chunk<C, G>(ctx, p, sums_src, sums_stride, st, ev, carry, while_gpu_busy, out);
+  return finish_chunk<C, G>(ctx, p, sums_src, sums_stride, r_src, st, ev, carry, while_gpu_busy, out);
 }
 
 // A base set that trips the incomplete law twice in a row (points outside the prime-order subgroup) would pay for both paths
@@ -1421,10 +1501,20 @@ void te_fell_back(mi355_msm_ctx* ctx) {
   }
 }
 
+// A context whose scalars keep having bits above bits(r) would pay for the wide anchored window's run AND its repeat on every call: after
+// two repeats in a row it stops using the wide window.
+void wide_fell_back(mi355_msm_ctx* ctx) {
+  ctx->fitted_chunk = 0;
+  if (++ctx->wide_streak >= 2) {
+    ctx->wide_off = true;
+    ctx->wide_demotions++;
+  }
+}
+
 // Returns false only for a chunk of a CARRIED batch whose twisted-Edwards run failed: the batch's buckets are Edwards sums then, so
 // the caller repeats the whole batch with allow_te = false (a lone chunk is repeated here, on the XYZZ path).
 template <class C>
-bool run_chunk(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0, size_t n, hipStream_t st,
+bool run_chunk_law(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0, size_t n, hipStream_t st,
                typename HostTail<typename C::E>::Pt& out, const std::function<void()>* while_gpu_busy = nullptr,
                const BucketCarry* carry = nullptr, bool allow_te = true) {
   if constexpr (std::is_same_v<C, Bls12_377_G1>) {
@@ -1433,6 +1523,7 @@ bool run_chunk(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0, size
         if (!carry || carry->last) ctx->te_fallback_streak = 0;
         return true;
       }
+      if (ctx->wide_overflowed) return false;   // (not the law's failure: run_chunk)
       ctx->te_fallbacks++;
       if (carry) return false;
       // (the hook -- the next batch's H2D copy -- has run already)
@@ -1441,7 +1532,32 @@ bool run_chunk(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0, size
       return true;
     }
   }
-  run_chunk_impl<C, SwLaw<typename C::E>>(ctx, d_scalars, base0, n, st, out, while_gpu_busy, carry);
+  return run_chunk_impl<C, SwLaw<typename C::E>>(ctx, d_scalars, base0, n, st, out, while_gpu_busy, carry) || !ctx->wide_overflowed;
+}
+
+// ... and false for the last chunk of a carried batch that ran with a wide anchored window and met a scalar with bits above bits(r)
+// (ctx->wide_overflowed says which): the caller repeats the whole batch with ctx->wide_suppress set.  A lone chunk is repeated here.
+template <class C>
+bool run_chunk(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0, size_t n, hipStream_t st,
+               typename HostTail<typename C::E>::Pt& out, const std::function<void()>* while_gpu_busy = nullptr,
+               const BucketCarry* carry = nullptr, bool allow_te = true) {
+  ctx->wide_overflowed = false;
+  const bool ok = run_chunk_law<C>(ctx, d_scalars, base0, n, st, out, while_gpu_busy, carry, allow_te);
+  if (!ctx->wide_overflowed) {
+    if (ok && ctx->last_wide && (!carry || carry->last)) ctx->wide_streak = 0;
+    return ok;
+  }
+  ctx->wide_fallbacks++;
+  if (carry) return false;
+  struct Suppress {
+    mi355_msm_ctx* c;
+    ~Suppress() { c->wide_suppress = false; }
+  } suppress{ctx};
+  ctx->wide_suppress = true;
+  ctx->wide_overflowed = false;
+  // (the hook -- the next batch's H2D copy -- has run already)
+  run_chunk_law<C>(ctx, d_scalars, base0, n, st, out, nullptr, nullptr, allow_te);
+  wide_fell_back(ctx);
   return true;
 }
 
@@ -1584,7 +1700,7 @@ void run_device_t(mi355_msm_ctx* ctx, uint8_t* out, const uint32_t* d_scalars, s
   typename HostTail<E>::Pt anchor_S;
   struct AnchorScope {
     mi355_msm_ctx* c;
-    ~AnchorScope() { c->anchor_armed = false; }
+    ~AnchorScope() { c->anchor_armed = c->wide_suppress = false; }
   } anchor_scope{ctx};
   ctx->anchor_armed = false;
   ctx->anchor_sum_ms = 0;
@@ -1618,8 +1734,9 @@ void run_device_t(mi355_msm_ctx* ctx, uint8_t* out, const uint32_t* d_scalars, s
     };
     // A batch that runs as several chunks carries one bucket array through them (BucketCarry): decided at its first chunk
     BucketCarry carry{};
-    bool carried = false, allow_te = true;
+    bool carried = false, allow_te = true, wide_repeat = false;
     uint32_t batch_anchor = kNoAnchor, batch_c = 0;   // the anchored window of the batch's chunks (all of them, or none)
+    bool batch_wide = false;                          // ... and whether it is a wide one
     size_t reclaimed_at = (size_t)-1;   // chunk position at which the idle stateless contexts were last reclaimed
     for (size_t off = 0; off < n;) {
       // plan the chunk against the memory that is there (ML msm.cu:453-466 plans first, too) ...
@@ -1696,8 +1813,13 @@ void run_device_t(mi355_msm_ctx* ctx, uint8_t* out, const uint32_t* d_scalars, s
         continue;
       }
       if (!ok) {
-        // the twisted-Edwards run of a carried batch failed (flagged at its last chunk): the whole batch again, on the XYZZ path
-        allow_te = false;
+        // the twisted-Edwards run of a carried batch failed (flagged at its last chunk): the whole batch again, on the XYZZ path --
+        // or its wide anchored window met a scalar with bits above bits(r): the whole batch again, without it
+        if (ctx->wide_overflowed)
+          ctx->wide_suppress = wide_repeat = true;
+        else
+          allow_te = false;
+        HostTail<E>::set_inf(total);
         off = 0;
         carry.index = 0;
         ctx->fitted_chunk = 0;
@@ -1711,8 +1833,9 @@ void run_device_t(mi355_msm_ctx* ctx, uint8_t* out, const uint32_t* d_scalars, s
       }
       if (off == 0) {
         batch_anchor = ctx->last_anchor;
+        batch_wide = ctx->last_wide;
         batch_c = (uint32_t)ctx->last_info[0];
-      } else if (ctx->last_anchor != batch_anchor || (batch_anchor != kNoAnchor && (uint32_t)ctx->last_info[0] != batch_c)) {
+      } else if (ctx->last_anchor != batch_anchor || ctx->last_wide != batch_wide || (batch_anchor != kNoAnchor && (uint32_t)ctx->last_info[0] != batch_c)) {
         throw HipFailure(-2, "mi355_msm: the chunks of a batch disagree about its anchored window (internal error)");
       }
       HostTail<E>::add(total, part);
@@ -1720,12 +1843,17 @@ void run_device_t(mi355_msm_ctx* ctx, uint8_t* out, const uint32_t* d_scalars, s
       carry.index++;
     }
     if (batch_anchor != kNoAnchor) {
-      // every scalar's digit in the anchored window was taken relative to 2^(c-1): add 2^(c a + c - 1) x (sum of the bases)
+      // every scalar's digit in the anchored window was taken relative to 2^(c-1): add 2^(c a + c - 1) x (sum of the bases) --
+      // relative to 2^c in a wide one: 2^(c a + c) x (the kept multiples are per shift: anchor_term)
       typename HostTail<E>::Pt term;
-      anchor_term<C>(ctx, n, (int)(batch_c * batch_anchor + batch_c - 1), anchor_S, term);
+      anchor_term<C>(ctx, n, (int)(batch_c * batch_anchor + batch_c - 1 + (batch_wide ? 1 : 0)), anchor_S, term);
       HostTail<E>::add(total, term);
     }
     if (!allow_te) te_fell_back(ctx);
+    if (wide_repeat) {
+      ctx->wide_suppress = false;
+      wide_fell_back(ctx);
+    }
     if (!prefetched) prefetch();   // n == 0
     const auto t0 = std::chrono::steady_clock::now();
     HostTail<E>::to_abi(out + b * out_bytes, total);
@@ -2128,6 +2256,9 @@ RustError mi355_msm_destroy(mi355_msm_ctx* ctx) {
     release_work_buffers(ctx);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
+    ctx->wide_flag.release();
+    ctx->wide_r.release();
+    if (ctx->h_wide_flag) (void)hipHostFree(ctx->h_wide_flag);
     for (auto& ev : ctx->ev)
       if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : ctx->carry_ev)
@@ -2412,6 +2543,15 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value) 
       // (2: a test setting -- any batch size, any window size, gain or not)
       if (value < 0 || value > 2) bad_arg("anchor %ld out of range [0, 2]", value);
       ctx->opt_anchor = value;
+    } else if (k == "anchor_wide") {
+      // 1 (default): where exactly one bit of r lies above the anchored window (BLS12-377 at c = 12, 14, 18, 21, ...) the window carries that bit
+      // too and the one-bit window above it has no entries of its own (partition_plan.hpp, part_plan); 0: round 6's recoding.  Setting
+      // it re-arms a context that had stopped using it after two repeats in a row.
+      if (value < 0 || value > 1) bad_arg("anchor_wide %ld out of range [0, 1]", value);
+      ctx->opt_anchor_wide = value;
+      ctx->wide_off = false;
+      ctx->wide_streak = 0;
+      ctx->fitted_chunk = 0;
     } else if (k == "first_piece_div") {
       if (value != 0 && (value < 2 || value > 64)) bad_arg("first_piece_div %ld out of range [2, 64]", value);
       ctx->opt_first_piece_div = value;
@@ -2506,8 +2646,8 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
       //  the per-shard value (the largest, should the slices differ), not the sum over the shards)
       static const char* const kAll[] = {"twisted_edwards", "assume_subgroup", "carry"};
       static const char* const kMean[] = {"table_levels", "table_window_bits"};
-      static const char* const kFirst[] = {"precompute", "g2_paired", "guard_tail", "te_limb_bits", "anchor"};
-      static const char* const kMax[] = {"bucket_windows", "l1_bits", "l1_bins", "group_passes", "anchored_window", "anchor_sum_us"};
+      static const char* const kFirst[] = {"precompute", "g2_paired", "guard_tail", "te_limb_bits", "anchor", "anchor_wide"};
+      static const char* const kMax[] = {"bucket_windows", "l1_bits", "l1_bins", "group_passes", "anchored_window", "anchor_sum_us", "anchor_wide_active"};
       auto in = [&](const char* const* set, size_t n) {
         for (size_t i = 0; i < n; i++)
           if (k == set[i]) return true;
@@ -2517,7 +2657,7 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
         *value = all;
       } else if (in(kMean, 2)) {
         *value = sum / ctx->shards.size();
-      } else if (in(kFirst, 5) || in(kMax, 6)) {
+      } else if (in(kFirst, 6) || in(kMax, 7)) {
         uint64_t first = 0, mx = 0;
         for (size_t g = 0; g < ctx->shards.size(); g++) {
           uint64_t v = 0;
@@ -2530,7 +2670,7 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
           if (g == 0) first = v;
           mx = std::max(mx, v);
         }
-        *value = in(kFirst, 5) ? first : mx;
+        *value = in(kFirst, 6) ? first : mx;
       } else {
         *value = sum;
       }
@@ -2573,6 +2713,14 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
       *value = ctx->opt_carry ? 1 : 0;
     else if (k == "anchor")
       *value = (uint64_t)ctx->opt_anchor;
+    else if (k == "anchor_wide")         // the option, 0 once the context has stopped using it (two repeats in a row)
+      *value = (ctx->opt_anchor_wide && !ctx->wide_off) ? 1 : 0;
+    else if (k == "anchor_wide_active")  // the most recent chunk ran with a wide anchored window
+      *value = ctx->last_wide ? 1 : 0;
+    else if (k == "anchor_wide_fallbacks")   // chunks or batches repeated without it because a scalar had bits above bits(r)
+      *value = ctx->wide_fallbacks;
+    else if (k == "anchor_wide_demotions")
+      *value = ctx->wide_demotions;
     else if (k == "anchored_window")   // of the most recent chunk: 1 + the window whose digits were taken relative to 2^(c-1); 0 = plain digits
       *value = ctx->last_anchor == kNoAnchor ? 0 : (uint64_t)ctx->last_anchor + 1;
     else if (k == "sorted_entries") {  // non-zero digits of the most recent chunk = its mixed additions (read back from the device: synchronises)

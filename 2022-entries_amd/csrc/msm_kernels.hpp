@@ -474,12 +474,16 @@ __global__ void __launch_bounds__(256) k_segreduce(const XyzzDevT<typename G::Me
 // L need not be a power of two: the first level of a large window is cut so that its chunks fill the chip's SIMDs with exactly one
 // wave each (Plan::L0) -- 13 windows x 4096 chunks of 128 buckets are 832 waves on 1024 SIMDs, 4994 chunks of 105 are 1015; the
 // outputs of window w start at w * out_stride (a power of two for the scan that follows, the tail of a row stays empty).
+// `run_win` (first level; 0xffffffff: none): the chunks of this window also leave their PLAIN sums, as the A of one more row -- row `windows`,
+// whose X the caller keeps empty -- so that the levels that follow deliver the plain sum of the window's buckets as one more "window sum":
+// what the wide anchored window's upper bucket set is short of (partition_plan.hpp, part_plan).
 template <class G, bool FIRST>
 __global__ void __launch_bounds__(256, G::ACC_WAVES) k_bucket_reduce(const XyzzDevT<typename G::MemT>* __restrict__ in_a,
                                                        const XyzzDevT<typename G::MemT>* __restrict__ in_x,
                                                        uint32_t n_per_win, uint32_t L, uint32_t chunks_per_win,
                                                        uint32_t windows, uint32_t out_stride, XyzzDevT<typename G::MemT>* __restrict__ out_a,
-                                                       XyzzDevT<typename G::MemT>* __restrict__ out_x, uint32_t* __restrict__ flags) {
+                                                       XyzzDevT<typename G::MemT>* __restrict__ out_x, uint32_t* __restrict__ flags,
+                                                       uint32_t run_win) {
   using E = typename G::E;
   using XD = XyzzDevT<typename G::MemT>;
   const uint32_t g = (blockIdx.x * 256 + threadIdx.x) / G::LANES, half = threadIdx.x % G::LANES;
@@ -530,6 +534,7 @@ __global__ void __launch_bounds__(256, G::ACC_WAVES) k_bucket_reduce(const XyzzD
   }
   const size_t at = (size_t)w * out_stride + t;
   G::store_pt(out_a + at, wsum, half);
+  if (FIRST && w == run_win) G::store_pt(out_a + (size_t)windows * out_stride + t, run, half);
   // X'_t = L * run, most significant bit of L first: doublings, and an addition of the sum itself for every further set bit
   if ((L & (L - 1)) == 0) {
     G::mul_pow2(run, 31 - __builtin_clz(L), md);

@@ -129,9 +129,13 @@ __device__ __forceinline__ uint32_t scalar_window(const uint32_t (&s)[8], uint32
 // value v = bits + carry in [0, 2^c] is written as 2^(c-1) + s with s in [-2^(c-1), 2^(c-1)]: |s| fits the same buckets, nothing is
 // carried up, and the constant 2^(c-1) of EVERY scalar -- zero or not -- is a multiple of the plain sum of the bases that the engine
 // adds on the host (msm_engine.hip, "anchored window").  The windows above start a fresh chain on the raw top bits.
+//
+// `wide` (wave-uniform, PartPlan::wide -- partition_plan.hpp): 1 / 2 = the two steps of the wide anchored window.  `u` then holds c + 1 raw
+// bits (step_offset / step_mask), v = u + carry in [0, 2^(c+1)] is written 2^c + s, and the step keeps the magnitude |s| if it belongs to its
+// bucket set: step 1 those up to 2^(c-1), step 2 the larger ones, less 2^(c-1).  The carry is left alone: step 2 needs it again, nothing follows.
 template <bool FOLD>
 __device__ __forceinline__ void next_digit(ScalarDigits& st, uint32_t u, uint32_t c, uint32_t half, uint32_t wmask, bool flip, uint32_t rwin,
-                                           uint32_t& mag, bool& neg, bool anchor = false) {
+                                           uint32_t& mag, bool& neg, bool anchor = false, uint32_t wide = 0) {
   if constexpr (FOLD) {
     const uint32_t sub = u + ((st.carry >> 1) & 1u);   // <= 2^c
     const bool borrow = flip && rwin < sub;
@@ -143,7 +147,12 @@ __device__ __forceinline__ void next_digit(ScalarDigits& st, uint32_t u, uint32_
     st.carry = (over ? 1u : 0u) | (borrow ? 2u : 0u);
   } else {
     const uint32_t v = u + st.carry;
-    if (anchor) {
+    if (wide) {
+      const uint32_t full = 1u << c;
+      neg = v < full;
+      const uint32_t m = neg ? full - v : v - full;
+      mag = wide == 1 ? (m <= half ? m : 0u) : (m > half ? m - half : 0u);
+    } else if (anchor) {
       neg = v < half;
       mag = neg ? half - v : v - half;
       st.carry = 0;
@@ -153,6 +162,22 @@ __device__ __forceinline__ void next_digit(ScalarDigits& st, uint32_t u, uint32_
       st.carry = neg ? 1u : 0u;
     }
   }
+}
+
+// Step w of a plan (wave-uniform): 0 an ordinary window, 1 / 2 the two steps of the wide anchored window; where its raw bits start and how
+// many there are.
+__device__ __forceinline__ uint32_t step_wide(const PartPlan& p, uint32_t w) { return (p.wide && w >= p.anchor) ? w - p.anchor + 1 : 0u; }
+__device__ __forceinline__ uint32_t step_offset(const PartPlan& p, uint32_t w) { return (p.wide && w > p.anchor ? p.anchor : w) * p.c; }
+__device__ __forceinline__ uint32_t step_mask(const PartPlan& p, uint32_t w) { return (p.wide && w >= p.anchor) ? (2u << p.c) - 1 : (1u << p.c) - 1; }
+// a bit of the scalar at or above position `top` (< 256) is set
+__device__ __forceinline__ bool scalar_bits_from(const uint32_t (&s)[8], uint32_t top) {
+  uint32_t any = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    if ((uint32_t)j == (top >> 5)) any |= s[j] >> (top & 31);
+    if ((uint32_t)j > (top >> 5)) any |= s[j];
+  }
+  return any != 0;
 }
 
 // window w of the scalar-field modulus (w, c wave-uniform)
@@ -266,9 +291,11 @@ __device__ __forceinline__ uint32_t l1_bin(const PartPlan& p, uint32_t w, uint32
 
 // ------------------------------------------------------------------------------------------------------------------------
 // L1 histogram: one block per tile, matrix row = the tile's entry count per level-1 bin.
+// (eight waves per SIMD asked for by name: two blocks per CU.  The kernel needs 29 VGPRs, but with the wide window's steps behind the loop it
+//  took 106 SGPRs -- seven waves, ONE block per CU, and 1.88 ms instead of 1.05 at 2^26 pairs: profiles/anchor_wide_rocprof_*.txt)
 template <class FR, int MODE, bool FOLD>
-__global__ void __launch_bounds__(PART_THREADS) k_l1_hist(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf, PartPlan p,
-                                                          uint32_t* __restrict__ matrix) {
+__global__ void __launch_bounds__(PART_THREADS, 8) k_l1_hist(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf, PartPlan p,
+                                                          uint32_t* __restrict__ matrix, uint32_t* __restrict__ wide_flag) {
   extern __shared__ uint32_t hist[];   // nbins
   const uint32_t tile = l1_tile(blockIdx.x / p.wgroups, p.ntiles);
   if (tile >= p.ntiles) return;
@@ -295,7 +322,9 @@ __global__ void __launch_bounds__(PART_THREADS) k_l1_hist(const uint32_t* __rest
       st.carry = 0;
     }
     const bool dead0 = !have || (p.table_stride ? false : inf[p.idx0 + i] != 0);
-    for (uint32_t w = 0; w < p.windows; w++) {
+    // (the two steps of a wide anchored window follow the loop: its body stays what it is for every other window)
+    const uint32_t w_plain = p.wide ? p.anchor : p.windows;
+    for (uint32_t w = 0; w < w_plain; w++) {
       uint32_t mag;
       bool neg;
       next_digit<FOLD>(st, scalar_window(st.s, w * p.c) & wmask, p.c, p.half, wmask, flip, FOLD ? fr_window<FR>(w, p.c, wmask) : 0u, mag, neg, w == p.anchor);
@@ -320,6 +349,23 @@ __global__ void __launch_bounds__(PART_THREADS) k_l1_hist(const uint32_t* __rest
 #else
         atomicAdd(&hist[l1_bin(p, w, mag - 1)], 1u);
 #endif
+      }
+    }
+    if (p.wide) {   // (wave-uniform; never with tables, shared buckets or FOLD: part_plan)
+      // the wide anchored window reads no bit from wide_top on: the engine repeats the chunk without it (every block of the tile may say so)
+      if (have && scalar_bits_from(st.s, p.wide_top)) *wide_flag = 1;
+      const uint32_t u = scalar_window(st.s, p.anchor * p.c) & ((2u << p.c) - 1);
+      for (uint32_t t = 1; t <= 2; t++) {
+        const uint32_t w = p.anchor + t - 1;
+        uint32_t mag;
+        bool neg;
+        next_digit<false>(st, u, p.c, p.half, wmask, false, 0u, mag, neg, false, t);
+        if (w < w_lo || w >= w_hi) continue;
+        const bool ok = mag != 0 && !dead0;
+        if (few)
+          few_bins_count(hist, p.b1, w * p.b1, ok, ok ? (mag - 1) >> p.lb : 0);
+        else if (ok)
+          atomicAdd(&hist[w * p.b1 + ((mag - 1) >> p.lb)], 1u);
       }
     }
   }
@@ -489,8 +535,8 @@ __global__ void __launch_bounds__(PART_THREADS) k_l1_scatter(const uint32_t* __r
       for (uint32_t w = 0; w < w_lo; w++) {
         uint32_t mag;
         bool neg;
-        next_digit<FOLD>(st[k], scalar_window(st[k].s, w * p.c) & wmask, p.c, p.half, wmask, ((alive >> (8 + k)) & 1) != 0,
-                         FOLD ? fr_window<FR>(w, p.c, wmask) : 0u, mag, neg, w == p.anchor);
+        next_digit<FOLD>(st[k], scalar_window(st[k].s, step_offset(p, w)) & step_mask(p, w), p.c, p.half, wmask, ((alive >> (8 + k)) & 1) != 0,
+                         FOLD ? fr_window<FR>(w, p.c, wmask) : 0u, mag, neg, w == p.anchor, step_wide(p, w));
       }
     }
   }
@@ -506,9 +552,10 @@ __global__ void __launch_bounds__(PART_THREADS) k_l1_scatter(const uint32_t* __r
                                        // two registers per entry, not three -- this kernel runs at the 128-VGPR limit of a 1024-thread block;
                                        // same speed as three, same-box A/B)
     const uint32_t rwin = FOLD ? fr_window<FR>(w, p.c, wmask) : 0u;
+    const uint32_t wide = step_wide(p, w), smask = step_mask(p, w);   // (wave-uniform)
     uint32_t raw[PART_PER_THREAD];    // the window's bits of the eight scalars: ONE uniform branch on the word pair, eight v_alignbit
     {
-      const uint32_t o = w * p.c, sh = o & 31;
+      const uint32_t o = step_offset(p, w), sh = o & 31;
 #define PART_RAW(L) case L: _Pragma("unroll") for (int k = 0; k < PART_PER_THREAD; k++) raw[k] = scalar_bits_at<L>(st[k].s, sh); break;
       switch (o >> 5) {
         PART_RAW(0) PART_RAW(1) PART_RAW(2) PART_RAW(3) PART_RAW(4) PART_RAW(5) PART_RAW(6) PART_RAW(7)
@@ -526,7 +573,7 @@ __global__ void __launch_bounds__(PART_THREADS) k_l1_scatter(const uint32_t* __r
       }
       uint32_t mag;
       bool neg;
-      next_digit<FOLD>(st[k], raw[k] & wmask, p.c, p.half, wmask, ((alive >> (8 + k)) & 1) != 0, rwin, mag, neg, w == p.anchor);
+      next_digit<FOLD>(st[k], raw[k] & smask, p.c, p.half, wmask, ((alive >> (8 + k)) & 1) != 0, rwin, mag, neg, w == p.anchor, wide);
       const uint32_t i = i0 + threadIdx.x + k * PART_THREADS;
       bool ok = ((alive >> k) & 1) && mag != 0;
       const uint32_t idx = l1_base_index(p, i, w);
@@ -886,12 +933,15 @@ __global__ void __launch_bounds__(256) k_dbg_count_digits(const uint32_t* __rest
     const bool flip = FOLD ? fold_decision<FR>(st) : false;
     const uint32_t wmask = (1u << p.c) - 1;
     for (uint32_t w = 0; w < p.windows; w++) {
-      const uint32_t u = st.s[0] & wmask;                 // the plain way: low bits, then the whole scalar down by c
-      for (int j = 0; j < 7; j++) st.s[j] = (st.s[j] >> p.c) | (st.s[j + 1] << (32 - p.c));
-      st.s[7] >>= p.c;
+      const uint32_t wide = step_wide(p, w);
+      const uint32_t u = st.s[0] & step_mask(p, w);       // the plain way: low bits, then the whole scalar down by c
+      if (wide != 1) {   // (the second step of a wide anchored window sees the same bits once more)
+        for (int j = 0; j < 7; j++) st.s[j] = (st.s[j] >> p.c) | (st.s[j + 1] << (32 - p.c));
+        st.s[7] >>= p.c;
+      }
       uint32_t mag;
       bool neg;
-      next_digit<FOLD>(st, u, p.c, p.half, wmask, flip, FOLD ? fr_window<FR>(w, p.c, wmask) : 0u, mag, neg, w == p.anchor);
+      next_digit<FOLD>(st, u, p.c, p.half, wmask, flip, FOLD ? fr_window<FR>(w, p.c, wmask) : 0u, mag, neg, w == p.anchor, wide);
       const bool dead = inf[l1_base_index(p, i, w)] != 0;
       if (mag != 0 && !dead) count++;
     }
@@ -992,9 +1042,9 @@ inline int part_run(const uint32_t* d_scalars, const uint8_t* d_inf, const PartP
   const dim3 scan_grid(part_ceil_div(p.nbins, 256), PART_SCAN_GROUPS);
   const uint32_t l1_grid = 8 * ((p.ntiles + 7) / 8) * p.wgroups;   // l1_tile(): a contiguous tile range per XCD; wgroups blocks per tile
   if (p.fold)
-    hipLaunchKernelGGL((k_l1_hist<FR, MODE, true>), dim3(l1_grid), dim3(PART_THREADS), p.nbins * 4, st, d_scalars, d_inf, p, b.matrix);
+    hipLaunchKernelGGL((k_l1_hist<FR, MODE, true>), dim3(l1_grid), dim3(PART_THREADS), p.nbins * 4, st, d_scalars, d_inf, p, b.matrix, b.wide_flag);
   else
-    hipLaunchKernelGGL((k_l1_hist<FR, MODE, false>), dim3(l1_grid), dim3(PART_THREADS), p.nbins * 4, st, d_scalars, d_inf, p, b.matrix);
+    hipLaunchKernelGGL((k_l1_hist<FR, MODE, false>), dim3(l1_grid), dim3(PART_THREADS), p.nbins * 4, st, d_scalars, d_inf, p, b.matrix, b.wide_flag);
   PART_MARK("l1_hist");
   hipLaunchKernelGGL(k_l1_scan_a, scan_grid, dim3(256), 0, st, b.matrix, p, b.partial);
   hipLaunchKernelGGL(k_l1_scan_b, dim3(1), dim3(1024), 0, st, b.partial, p, b.segs[0], b.subjob_first, b.totals);

@@ -60,6 +60,10 @@ struct PartPlan {
   uint32_t wgroups, wper;            // level-1 blocks per tile (each takes `wper` consecutive windows): fills the chip when tiles are few
   uint32_t fold;                     // 1: a scalar k in (r/2, r) is replaced by r - k with all its digits negated (load_scalar)
   uint32_t anchor;                   // the window whose digit is taken relative to 2^(c-1) and ends the carry chain (next_digit); PART_NO_ANCHOR: none
+  uint32_t wide;                     // 1: the anchored window also takes the ONE scalar bit above it (see part_plan): steps `anchor` and `anchor` + 1
+                                     // both read its c + 1 bits, and the magnitudes above 2^(c-1) go to bucket set `anchor` + 1
+  uint32_t wide_top;                 // ... and the first bit position no step reads: (anchor + 1) c + 1 = the bits of r (a scalar with a bit set from
+                                     // there on raises the flag word of k_l1_hist)
 };
 constexpr uint32_t PART_NO_ANCHOR = 0xffffffffu;
 
@@ -76,11 +80,22 @@ inline uint32_t part_ceil_div(uint64_t a, uint64_t b) { return (uint32_t)((a + b
 
 // `levels` = precomputed table levels (0 or 1: none).  With k levels the windows g, g + G, g + 2G, ... (G = ceil(windows / k)) feed bucket
 // set g: yrrid's shape is k = 6, G = 2 (CMB PrecomputePoints.cu:10-39, MSM.cu:380-383); k >= windows is "one bucket set for all".
+//
+// The wide anchored window (`wide`; no tables, no fold, `anchor` + 2 == windows).  Where exactly ONE bit of a canonical scalar lies above the
+// anchored window a -- BLS12-377's Fr: 253 = 12 x 21 + 1 -- that bit rides in window a: its value v = (c + 1 raw bits) + carry lies in
+// [0, 2^(c+1)] and is written 2^c + s, |s| <= 2^c, nothing carried up.  A magnitude m = |s| <= 2^(c-1) goes to (set a, bucket m) as before,
+// a larger one to (set a + 1, bucket m - 2^(c-1)): the bucket set that the one-bit window owned.  Steps a and a + 1 of the level-1 kernels read
+// the same bits and the same carry, and exactly one of them has an entry (none when s = 0), so the kernels keep their shape: `windows`
+// steps, `windows` bucket sets of 2^(c-1) buckets, at most one entry per scalar and DIGIT window -- a + 1 of those (12.0 n entries at c = 21 where the one-bit window made it 12.14 n).  The host adds
+// 2^(c-1) times the plain sum of set a + 1 and 2^(c a + c) times the sum of the bases (msm_engine.hip).  Bits from `wide_top` on are not read:
+// a scalar that has one raises a flag and the engine repeats the chunk without `wide`.
 inline PartPlan part_plan(uint32_t n, uint32_t c, uint32_t windows, uint32_t levels, uint32_t idx0, uint32_t table_stride, bool fold = false,
-                          uint32_t anchor = 0xffffffffu) {
+                          uint32_t anchor = 0xffffffffu, bool wide = false) {
   PartPlan p{};
   p.fold = fold ? 1 : 0;
   p.anchor = fold ? 0xffffffffu : anchor;
+  p.wide = (wide && p.anchor != 0xffffffffu && levels <= 1 && p.anchor + 2 == windows) ? 1 : 0;
+  p.wide_top = p.wide ? (p.anchor + 1) * c + 1 : 0;
   p.n = n;
   p.c = c;
   p.windows = windows;
@@ -190,6 +205,7 @@ struct PartBuffers {
   uint32_t* subjob_first;
   uint32_t* counts;
   uint32_t* totals;          // [0] = real entries (read by the accumulation), [1] = sub-jobs of the pass in flight
+  uint32_t* wide_flag;       // PartPlan::wide: set to 1 when a scalar has a bit at or above wide_top (never cleared here)
 };
 
 

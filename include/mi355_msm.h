@@ -258,6 +258,14 @@ RustError mi355_msm_job_wait(mi355_msm_job* job);
  * additions; 2^26 pairs of BLS12-377 G1 then run at c = 21 instead of 20 (-1.0 %; with tables -1..-2.5 %: profiles/r06_ab_anchor.txt).
  * The price: a scalar of ZERO costs one addition (its digit in the anchored window is -2^(c-1)) instead of none -- a batch that is
  * mostly zeros should set "anchor" = 0.  The stateless call never uses it (its bases change with every call).
+ * "anchor_wide" (default 1; 0 = the recoding above as it is): where exactly ONE bit of r lies above the anchored window a -- BLS12-377's
+ * Fr wherever c divides 252: c = 21 at 2^26 pairs; never BLS12-381's -- that bit rides in window a.  Its value v in [0, 2^(c+1)] is taken
+ * as 2^c + s, |s| <= 2^c; magnitudes up to 2^(c-1) keep their buckets, the larger ones use the bucket set of the one-bit window above, which
+ * has no entries of its own any more: 12.0 n additions instead of 12.14 n at c = 21, the same bucket sets and kernels.  The host adds
+ * 2^(c-1) times that set's plain sum (one more row of the bucket reduction) and 2^(c a + c) times the sum of the bases.  -1.3 % at 2^26
+ * pairs of BLS12-377 G1, -1.8 % of G2 (profiles/ab_anchor_wide.txt).  A scalar with a bit at or above bits(r) = 253 set is not read
+ * that far: the device reports it and the chunk -- of a carried batch: the batch -- runs again without the option, so any 256-bit scalar
+ * stays legal; after two such repeats in a row the context stops using it until the option is set again.
  * "carry" (default 1): a batch that runs as several chunks (max_chunk, the memory budget, the pieces of a host-scalar batch) carries
  * ONE bucket array through them -- every chunk uses the window size of the whole batch and only the last one reduces; 0 = every
  * chunk reduces its own buckets and the partial sums are added on the host.  "first_piece_div" (default 13; 4 with carry = 0): the
@@ -288,6 +296,8 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value);
  * contexts of the stateless pool were given back and the same chunk retried), "debug_checks" (invariant checks a -DMSM_DEBUG
  * build has run; always 0 in this library), "chunk_cap", "anchor" (the option), "anchored_window" (1 + the anchored window of the most
  * recent chunk, 0 = plain digits), "anchor_sums" (sums of bases computed so far), "anchor_sum_us" (host time the most recent run spent on one),
+ * "anchor_wide" (the option; 0 once the context has stopped using it), "anchor_wide_active" (the most recent chunk ran with it),
+ * "anchor_wide_fallbacks" (chunks / batches repeated without it), "anchor_wide_demotions",
  * "device", "bases", "table_levels", "table_window_bits", "base_bytes" (device bytes held for the bases). */
 RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value);
 /* Per-stage device time (ms, HIP events on the launch stream) of the most recent run, summed over its chunks
