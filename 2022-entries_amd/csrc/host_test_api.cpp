@@ -1653,6 +1653,158 @@ int ht_sparse_apply(int field, unsigned tile_log, unsigned create_flags, unsigne
 }
 }
 
+// ---- multilinear extensions and sumcheck rounds (mle.hpp): the chains of launches the engine runs, every block lane by lane, with the
+// limb-bound checker armed ---------------------------------------------------------------------------------------------------------
+#include "mle.hpp"
+
+template <class FR>
+struct HostMleRun {
+  std::vector<Fr> lds;
+  HostMleRun() : lds(POLY_MAX_TILE) {}
+  void tree(uint32_t lanes) {
+    for (uint32_t s = 0; (2u << s) <= lanes; s++)
+      for (uint32_t l = 0; l < (lanes >> (s + 1)); l++) mle_tree_level<FR>(lds.data(), lanes, s, l);
+  }
+  void fix(const MleFix& p) {
+    const uint32_t T = 1u << p.tile_log;
+    for (uint64_t tile = 0; tile < (p.n >> p.tile_log); tile++) {
+      for (uint32_t i = 0; i < T; i++) mle_fix_load<FR>(lds.data(), p, tile << p.tile_log, i);
+      for (uint32_t s = 0; s < p.kk; s++)
+        for (uint32_t j = 0; j < (T >> (s + 1)); j++) mle_fix_level<FR>(lds.data(), p, s, j);
+      for (uint32_t i = 0; i < (T >> p.kk); i++) mle_fix_store<FR>(lds.data(), p, tile, i);
+    }
+  }
+  void eq(const MleEq& p) {
+    for (uint64_t b = 0; b < p.n; b++) mle_eq_elem<FR>(p, b);
+  }
+  template <int D>
+  void round(const MleRound& p) {
+    const uint32_t lanes = poly_lanes(p.tile_log);
+    std::vector<Fr> acc((size_t)lanes * (D + 1));
+    for (uint64_t blk = 0; blk < mle_blocks(p.npts, p.tile_log); blk++) {
+      for (uint32_t l = 0; l < lanes; l++) {
+        Fr a[D + 1];
+        mle_round_lane<FR, D>(a, p, blk, l);
+        for (int t = 0; t <= D; t++) acc[(size_t)l * (D + 1) + t] = a[t];
+      }
+      for (int t = 0; t <= D; t++) {
+        for (uint32_t l = 0; l < lanes; l++) lds[l] = acc[(size_t)l * (D + 1) + t];
+        tree(lanes);
+        poly_store_m<FR>(p.part + blk * MLE_EVALS + t, lds[0]);
+      }
+    }
+  }
+  void sum(const MleSum& p) {
+    const uint32_t lanes = poly_lanes(p.tile_log);
+    for (uint64_t blk = 0; blk < mle_blocks(p.n, p.tile_log); blk++)
+      for (uint32_t t = 0; t < p.ne; t++) {
+        for (uint32_t l = 0; l < lanes; l++) mle_sum_lane<FR>(lds[l], p, blk, l, t);
+        tree(lanes);
+        poly_store_m<FR>(p.dst + blk * MLE_EVALS + t, lds[0]);
+      }
+  }
+};
+
+template <class FR>
+static int t_mle_fix(uint32_t tile_log, unsigned flags, uint32_t nv, uint32_t k, const uint8_t* in, const uint8_t* point, uint8_t* out) {
+  const bool normal = (flags & kMleNormal) != 0;
+  const size_t n_in = (size_t)1 << nv, n_out = (size_t)1 << (nv - k);
+  std::vector<uint32_t> src(n_in * 8), dst(n_out * 8, 0xa5a5a5a5u);
+  memcpy(src.data(), in, n_in * 32);
+  std::vector<Fr> work(mle_fix_work_elems(nv, k, tile_log) + 2);
+  Fr pt[MLE_MAX_VARS];
+  for (uint32_t i = 0; i < k; i++) poly_scalar<FR>(pt[i], point + 32 * i, normal);
+  HostMleRun<FR> run;
+  mle_chain_fix<FR>(run, dst.data(), src.data(), nv, pt, k, normal, tile_log, work.data());
+  memcpy(out, dst.data(), n_out * 32);
+  return 0;
+}
+
+template <class FR>
+static int t_mle_eq(unsigned flags, uint32_t k, const uint8_t* point, uint8_t* out) {
+  const bool normal = (flags & kMleNormal) != 0;
+  const uint32_t lo_log = (k + 1) / 2;
+  std::vector<uint32_t> dst(((size_t)8) << k, 0xa5a5a5a5u);
+  std::vector<Fr> lo, hi;
+  Fr pt[MLE_MAX_VARS], one, cout;
+  for (uint32_t i = 0; i < k; i++) poly_scalar<FR>(pt[i], point + 32 * i, normal);
+  fr_set<FR>(one, FR::ONE);
+  fr_const<FR>(cout, normal ? 3 : 2);
+  mle_eq_half<FR>(lo, pt, lo_log, one);
+  mle_eq_half<FR>(hi, pt + lo_log, k - lo_log, cout);
+  HostMleRun<FR> run;
+  mle_chain_eq<FR>(run, dst.data(), lo.data(), hi.data(), k);
+  memcpy(out, dst.data(), (size_t)32 << k);
+  return 0;
+}
+
+template <class FR>
+static int t_mle_round(uint32_t tile_log, unsigned flags, uint32_t m, uint32_t nv, const uint8_t* tables, uint32_t n_terms, const uint8_t* coeffs,
+                       const uint32_t* nfs, const uint32_t* factors, const uint8_t* r_prev, uint8_t* folded, uint8_t* evals_out) {
+  const bool normal = (flags & kMleNormal) != 0, fused = r_prev != nullptr;
+  const size_t n_in = (size_t)1 << nv, n_half = n_in / 2;
+  std::vector<uint32_t> src((size_t)m * n_in * 8), fold(fused ? (size_t)m * n_half * 8 : 8, 0xa5a5a5a5u);
+  memcpy(src.data(), tables, (size_t)m * n_in * 32);
+  MleRound p{};
+  p.npts = (fused ? n_half : n_in) / 2;
+  p.m = m;
+  p.n_terms = n_terms;
+  p.tile_log = tile_log;
+  p.fused = fused ? 1u : 0u;
+  fr_const<FR>(p.cin, normal ? 1 : 0);
+  fr_const<FR>(p.cout, normal ? 3 : 2);
+  uint32_t D = 0;
+  for (uint32_t i = 0; i < m; i++) {
+    p.src[i] = src.data() + (size_t)i * n_in * 8;
+    p.folded[i] = fold.data() + (size_t)i * n_half * 8;
+    p.tab[i] = fused ? p.folded[i] : p.src[i];
+  }
+  for (uint32_t j = 0; j < n_terms; j++) {
+    poly_scalar<FR>(p.term[j].c, coeffs + 32 * j, normal);
+    p.term[j].nf = nfs[j];
+    for (uint32_t q = 0; q < nfs[j]; q++) p.term[j].f[q] = factors[j * MLE_MAX_FACTORS + q];
+    if (nfs[j] > D) D = nfs[j];
+  }
+  if (fused) {
+    Fr r;
+    poly_scalar<FR>(r, r_prev, normal);
+    mle_one_minus<FR>(p.fa, r);
+    mle_mul_canon<FR>(p.fa, p.fa, p.cin);
+    mle_mul_canon<FR>(p.fb, r, p.cin);
+  }
+  std::vector<Fr> work(mle_round_work_elems(p.npts, tile_log) + 2);
+  HostMleRun<FR> run;
+  const Fr* res = mle_chain_round<FR>(run, p, D, work.data());
+  for (uint32_t t = 0; t <= D; t++) poly_scalar_out<FR>(evals_out + 32 * t, res[t], normal);
+  if (fused) memcpy(folded, fold.data(), (size_t)m * n_half * 32);
+  return (int)mle_round_levels(p.npts, tile_log);
+}
+
+extern "C" {
+// mi355_msm_domain_mle_fix / mle_eq / sumcheck_round on the host; flags bit 0: plain integers.  The tables of a round lie one behind
+// the other, the folded ones too; factors holds MLE_MAX_FACTORS indices per term; ht_mle_round returns the launches of the round.
+int ht_mle_fix(int field, unsigned tile_log, unsigned flags, unsigned nv, unsigned k, const uint8_t* in, const uint8_t* point, uint8_t* out) {
+  if (tile_log < POLY_TILE_LOG_MIN || tile_log > POLY_TILE_LOG_MAX || (flags & ~kMleNormal) || nv > 20 || k > nv || !in || !out || (k && !point)) return -1;
+  return POLY_FIELD(t_mle_fix, tile_log, flags, nv, k, in, point, out);
+}
+int ht_mle_eq(int field, unsigned flags, unsigned k, const uint8_t* point, uint8_t* out) {
+  if ((flags & ~kMleNormal) || k > 20 || !out || (k && !point)) return -1;
+  return POLY_FIELD(t_mle_eq, flags, k, point, out);
+}
+int ht_mle_round(int field, unsigned tile_log, unsigned flags, unsigned m, unsigned nv, const uint8_t* tables, unsigned n_terms, const uint8_t* coeffs,
+                 const uint32_t* nfs, const uint32_t* factors, const uint8_t* r_prev, uint8_t* folded, uint8_t* evals_out) {
+  if (tile_log < POLY_TILE_LOG_MIN || tile_log > POLY_TILE_LOG_MAX || (flags & ~kMleNormal) || m < 1 || m > MLE_MAX_TABLES || nv < 1 || nv > 16 ||
+      n_terms < 1 || n_terms > MLE_MAX_TERMS || !tables || !coeffs || !nfs || !factors || !evals_out || (r_prev && (nv < 2 || !folded)))
+    return -1;
+  for (unsigned j = 0; j < n_terms; j++) {
+    if (nfs[j] < 1 || nfs[j] > MLE_MAX_FACTORS) return -1;
+    for (unsigned q = 0; q < nfs[j]; q++)
+      if (factors[j * MLE_MAX_FACTORS + q] >= m) return -1;
+  }
+  return POLY_FIELD(t_mle_round, tile_log, flags, m, nv, tables, n_terms, coeffs, nfs, factors, r_prev, folded, evals_out);
+}
+}
+
 // ---- transforms of vectors of points (group_fft.hpp) with the limb-bound checker armed ------------------------------------------
 // The SAME MSM_HD functions the kernels of kernels_gfft.hip wrap: the index maps, the twiddle exponent, the twiddle and the factor as
 // canonical words, the table of a butterfly's B, the walk and the butterfly; records by fb_host_records, the vector between two

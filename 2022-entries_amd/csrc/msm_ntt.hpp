@@ -10,6 +10,7 @@
 
 #include "launch_ntt.hpp"
 #include "launch_poly.hpp"
+#include "mle.hpp"      // (the limits of a sumcheck round, for the queries)
 
 struct mi355_msm_domain {
   int curve = 0;
@@ -22,6 +23,8 @@ struct mi355_msm_domain {
   uint32_t poly_tile_log = POLY_DEFAULT_TILE_LOG;
   DevBuf scan, sstage;    // msm_scan.hpp: the levels of the scans and the rows of the permutation product; the staged vectors of its host-pointer calls
   DevBuf quot, qstage;    // msm_quot.hpp: x - 1 per row, its inverses and their tile products; the staged vectors of its host-pointer calls
+  DevBuf mle, mstage;     // msm_mle.hpp: the passes of fix_variables, the half tables of eq, the partial rows of a round; the staged vectors of its host-pointer calls
+  uint32_t mle_levels = 0;   // launches of the most recent sumcheck round: the round and its further sums
   Fr size_inv{};
   Fr g_have{};            // the (inverted, for the inverse kinds) offset the offset tables hold
   bool g_valid = false;
@@ -62,7 +65,7 @@ void with_fr(int curve, Fn&& fn) {
 }
 
 void domain_release(mi355_msm_domain* d) {
-  for (DevBuf* b : {&d->tables, &d->work, &d->stage, &d->poly, &d->pstage, &d->scan, &d->sstage, &d->quot, &d->qstage}) b->release();
+  for (DevBuf* b : {&d->tables, &d->work, &d->stage, &d->poly, &d->pstage, &d->scan, &d->sstage, &d->quot, &d->qstage, &d->mle, &d->mstage}) b->release();
   for (hipEvent_t& e : d->ev)
     if (e) { (void)hipEventDestroy(e); e = nullptr; }
   if (d->own_stream) { (void)hipStreamDestroy(d->own_stream); d->own_stream = nullptr; }
@@ -365,8 +368,13 @@ RustError mi355_msm_domain_set_option(mi355_msm_domain* d, const char* key, long
 
 RustError mi355_msm_domain_query(mi355_msm_domain* d, const char* key, uint64_t* value) {
   return guarded([&] {
-    if (!d || !key || !value) bad_arg("null argument");
+    if (!key || !value) bad_arg("null argument");
     const std::string k(key);
+    // the limits of a sumcheck round need no handle
+    if (k == "sumcheck_max_tables") { *value = MLE_MAX_TABLES; return; }
+    if (k == "sumcheck_max_terms") { *value = MLE_MAX_TERMS; return; }
+    if (k == "sumcheck_max_factors") { *value = MLE_MAX_FACTORS; return; }
+    if (!d) bad_arg("null argument");
     uint32_t radix[NTT_MAX_LOG];
     if (k == "size") *value = (uint64_t)1 << d->k;
     else if (k == "log_size") *value = d->k;
@@ -377,6 +385,8 @@ RustError mi355_msm_domain_query(mi355_msm_domain* d, const char* key, uint64_t*
     else if (k == "poly_work_bytes") *value = d->poly.bytes + d->pstage.bytes;
     else if (k == "scan_work_bytes") *value = d->scan.bytes + d->sstage.bytes;
     else if (k == "quotient_work_bytes") *value = d->quot.bytes + d->qstage.bytes;
+    else if (k == "mle_work_bytes") *value = d->mle.bytes + d->mstage.bytes;
+    else if (k == "sumcheck_levels") *value = d->mle_levels;
     else if (k == "poly_tile_log") *value = d->poly_tile_log;
     else if (k == "device") *value = (uint64_t)d->device;
     else if (k == "last_us") *value = d->last_us;

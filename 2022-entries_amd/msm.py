@@ -163,6 +163,9 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_sparse_apply": [vp, vp, vp, ctypes.c_uint, vp],
         "mi355_msm_sparse_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_sparse_destroy": [vp],
+        "mi355_msm_domain_mle_fix": [vp, vp, vp, ctypes.c_uint, vp, ctypes.c_uint, ctypes.c_uint, vp],
+        "mi355_msm_domain_mle_eq": [vp, vp, vp, ctypes.c_uint, ctypes.c_uint, vp],
+        "mi355_msm_domain_sumcheck_round": [vp, vp, vp, sz, ctypes.c_uint, vp, sz, vp, vp, ctypes.c_uint, vp],
         "mi355_msm_trim": [],
         "mi355_msm_pool_stats": [ctypes.POINTER(ctypes.c_uint64), sz],
     }
@@ -1448,6 +1451,135 @@ class Radix2EvaluationDomain:
         _check(self._lib.mi355_msm_domain_linear_combination(self.handle, ob.ptr if n else None, ptrs, lv, cb, m, flags))
         return _like_input(cols[lens.index(n)], res, (n, 32))
 
+    # ---- dense multilinear extensions and sumcheck prover rounds (mi355_msm_domain_mle_*, _sumcheck_round) --------------------------
+
+    def _point(self, point, montgomery):
+        pts = [int(x) for x in point]
+        return pts, b"".join(self._scalar(x, montgomery) for x in pts)
+
+    def _table(self, evals, what="evals"):
+        """(the buffer of a table of 2^nv 32-byte elements, nv)"""
+        (b,), n = self._vectors(evals)
+        if n < 1 or n & (n - 1):
+            raise ValueError(f"{what}: a table holds 2^num_vars 32-byte elements, not {n}")
+        return b, n.bit_length() - 1
+
+    def _mle_fix(self, evals, point, montgomery, out):
+        b, nv = self._table(evals)
+        pts, raw = self._point(point, montgomery)
+        if len(pts) > nv:
+            raise ValueError(f"point: {len(pts)} values for a table of {nv} variables")
+        n_out = 1 << (nv - len(pts))
+        res, ob = self._out(evals, b, out, n_out)
+        flags = (0 if montgomery else 1) | (2 if b.is_device else 0)
+        _check(self._lib.mi355_msm_domain_mle_fix(self.handle, ob.ptr, b.ptr, nv, raw if pts else None, len(pts), flags, b.stream if b.is_device else None))
+        return res, b.is_device, n_out
+
+    def mle_fix_variables(self, evals, point, montgomery: bool = True, out=None):
+        """``DenseMultilinearExtension::fix_variables``: ``evals`` is a table of ``2^nv`` elements, index ``b`` standing for the point
+        ``(b_0, .., b_{nv-1})`` with ``b_0`` the lowest bit; ``point`` (integers) fixes ``x_1 .. x_k`` from the lowest bit upward and the
+        result holds ``2^(nv - k)`` canonical elements.  ``out`` must not overlap ``evals``.  GPU tensors are read in place on their
+        current stream and give a GPU tensor."""
+        res, dev, n_out = self._mle_fix(evals, point, montgomery, out)
+        return res if dev else _like_input(evals, res, (n_out, 32))
+
+    def mle_evaluate(self, evals, point, montgomery: bool = True) -> int:
+        """``DenseMultilinearExtension::evaluate``: the value at ``point`` (``nv`` integers) as an integer"""
+        res, dev, n_out = self._mle_fix(evals, point, montgomery, None)
+        if n_out != 1:
+            raise ValueError(f"point: {len(point)} values do not fix every variable of the table")
+        return self._scalar_out(res.cpu().numpy().tobytes() if dev else res.tobytes(), montgomery)
+
+    def eq_table(self, point, montgomery: bool = True, out=None, device: bool = False):
+        """the ``2^k`` values ``eq(b, point) = prod_i (b_i ? point[i] : 1 - point[i])``.  A NumPy array ``(2^k, 32)``, or with ``out=`` /
+        ``device=True`` a GPU tensor written on the current stream."""
+        if not self.handle:
+            raise MsmError(-1, "the domain is closed")
+        pts, raw = self._point(point, montgomery)
+        n, flags = 1 << len(pts), 0 if montgomery else 1
+        if out is not None or device:
+            import torch
+
+            if out is None:
+                out = torch.empty((n, 32), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            ob = _Buf(out)
+            if not ob.is_device or ob.nbytes != n * 32 or ob.keep is not out or ob.device_index != self.device:
+                raise ValueError(f"out must be a contiguous uint8 tensor of {n * 32} bytes on cuda:{self.device}")
+            _check(self._lib.mi355_msm_domain_mle_eq(self.handle, ob.ptr, raw if pts else None, len(pts), flags | 2, ob.stream))
+            return out
+        import numpy as np
+
+        res = np.zeros((n, 32), dtype=np.uint8)
+        _check(self._lib.mi355_msm_domain_mle_eq(self.handle, res.ctypes.data, raw if pts else None, len(pts), flags, None))
+        return res
+
+    def _terms(self, terms, montgomery):
+        recs, d = [], 0
+        for coeff, factors in terms:
+            fs = [int(f) for f in factors]
+            if len(fs) > 5 or any(f < 0 or f >= 1 << 32 for f in fs):
+                raise ValueError("a term takes at most 5 factor indices, each a table index")
+            recs.append(self._scalar(coeff, montgomery) + len(fs).to_bytes(4, "little") + b"".join(f.to_bytes(4, "little") for f in fs + [0] * (5 - len(fs))))
+            d = max(d, len(fs))
+        return b"".join(recs), len(recs), d
+
+    def sumcheck_round(self, tables, terms, r_prev=None, montgomery: bool = True, out=None):
+        """One prover round of the sumcheck protocol for ``g = sum_j c_j prod_{k in S_j} f_k``: ``tables`` is a list of ``m <= 12``
+        tables of ``2^nv`` elements, ``terms`` a list of ``(c_j, [table indices])`` with at most 8 terms of at most 5 factors (a repeated
+        index is a power).  Returns the ``d + 1`` integers ``P(t) = sum_b sum_j c_j prod_k (f_k[2b] + t (f_k[2b+1] - f_k[2b]))``,
+        ``t = 0 .. d``.  With ``r_prev`` the call first fixes ``x_1 = r_prev`` in every table, in the same pass, and returns
+        ``(evals, folded)``: the evaluations of the folded tables and the list of the ``m`` folded tables (``out=``: a list of ``m``
+        GPU tensors of ``2^(nv - 1)`` elements to write them into; none may overlap a table)."""
+        tables = list(tables)
+        bufs, n = self._vectors(*tables)
+        if n < 2 or n & (n - 1):
+            raise ValueError(f"tables: each holds 2^num_vars >= 2 32-byte elements, not {n}")
+        nv, m, dev = n.bit_length() - 1, len(bufs), bufs[0].is_device
+        recs, n_terms, d = self._terms(terms, montgomery)
+        flags = (0 if montgomery else 1) | (2 if dev else 0)
+        ptrs = (ctypes.c_void_p * m)(*[b.ptr for b in bufs])
+        evals = ctypes.create_string_buffer(32 * 6)
+        stream = bufs[0].stream if dev else None
+        if r_prev is None:
+            if out is not None:
+                raise ValueError("out= goes with r_prev")
+            _check(self._lib.mi355_msm_domain_sumcheck_round(self.handle, evals, ptrs, m, nv, recs, n_terms, None, None, flags, stream))
+            return [self._scalar_out(evals.raw[32 * t:32 * t + 32], montgomery) for t in range(d + 1)]
+        outs = list(out) if out is not None else [None] * m
+        if len(outs) != m:
+            raise ValueError(f"out: one tensor per table, {m}")
+        made = [self._out(tables[i], bufs[i], outs[i], n // 2) for i in range(m)]
+        fptrs = (ctypes.c_void_p * m)(*[ob.ptr for _, ob in made])
+        _check(self._lib.mi355_msm_domain_sumcheck_round(self.handle, evals, ptrs, m, nv, recs, n_terms, self._scalar(r_prev, montgomery), fptrs, flags, stream))
+        folded = [res if dev else _like_input(tables[i], res, (n // 2, 32)) for i, (res, _) in enumerate(made)]
+        return [self._scalar_out(evals.raw[32 * t:32 * t + 32], montgomery) for t in range(d + 1)], folded
+
+    def sumcheck_prove(self, tables, terms, challenge, montgomery: bool = True):
+        """The prover of the sumcheck protocol over ``nv`` rounds; Fiat-Shamir is the caller's: ``challenge(i, evals) -> int`` gets the
+        round index and the round's ``d + 1`` evaluations and returns ``r_i``.  The first round is plain, every later one fused with the
+        fold by the previous challenge, ping-ponging between two sets of buffers whose sizes halve; the caller's tables are not modified.
+        Returns ``(rounds, point, finals)``: the evaluations of every round, the point ``(r_0, .., r_{nv-1})`` and the ``m`` values
+        ``f_k(point)``."""
+        tables = list(tables)
+        bufs, n = self._vectors(*tables)
+        if n < 2 or n & (n - 1):
+            raise ValueError(f"tables: each holds 2^num_vars >= 2 32-byte elements, not {n}")
+        nv, m, dev = n.bit_length() - 1, len(bufs), bufs[0].is_device
+        sets = [None, None]
+        if dev and nv >= 2:
+            import torch
+
+            sets = [[torch.empty((n >> (1 + j), 32), dtype=torch.uint8, device=bufs[0].keep.device) for _ in range(m)] for j in range(2 if nv >= 3 else 1)] + [None]
+        ev = self.sumcheck_round(tables, terms, montgomery=montgomery)
+        rounds, point, cur = [ev], [int(challenge(0, ev))], tables
+        for i in range(1, nv):
+            outs = [t[:n >> i] for t in sets[(i - 1) & 1]] if dev else None
+            ev, cur = self.sumcheck_round(cur, terms, r_prev=point[-1], montgomery=montgomery, out=outs)
+            rounds.append(ev)
+            point.append(int(challenge(i, ev)))
+        finals = [self.mle_evaluate(t, [point[-1]], montgomery=montgomery) for t in cur]
+        return rounds, point, finals
+
     # ---- resident sparse matrices and Groth16's witness map (mi355_msm_sparse_*) -----------------------------------------------------
 
     def sparse_matrix(self, rows, cols, row_ptr, col_idx, values, montgomery: bool = True) -> "SparseMatrix":
@@ -1505,7 +1637,7 @@ class Radix2EvaluationDomain:
 
     def query(self, key: str) -> int:
         """ "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "scan_work_bytes", "quotient_work_bytes",
-        "poly_tile_log",
+        "mle_work_bytes", "sumcheck_levels", "sumcheck_max_tables", "sumcheck_max_terms", "sumcheck_max_factors", "poly_tile_log",
         "device", "last_us", "last_device_us" """
         v = ctypes.c_uint64(0)
         _check(self._lib.mi355_msm_domain_query(self.handle, key.encode(), ctypes.byref(v)))

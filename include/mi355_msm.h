@@ -674,6 +674,54 @@ RustError mi355_msm_sparse_apply(mi355_msm_sparse* m, void* out, const void* z, 
 RustError mi355_msm_sparse_query(mi355_msm_sparse* m, const char* key, uint64_t* value);
 RustError mi355_msm_sparse_destroy(mi355_msm_sparse* m);
 
+/* ---- dense multilinear extensions and sumcheck prover rounds over Fr (ark-poly's DenseMultilinearExtension, ark-linear-sumcheck) -------
+ * The other half of ark-poly: a table of 2^num_vars evaluations over the boolean cube, and the prover's side of the sumcheck protocol
+ * for g(x) = sum_j c_j prod_{k in S_j} f_k(x) (ListOfProductsOfPolynomials: Spartan, HyperPlonk, GKR, Lasso).  The calls live on the
+ * domain handle, which lends its field, its stream for host-pointer calls, its host arithmetic and its work memory; the vector lengths
+ * have nothing to do with the domain's size.  Index b of a table is the point (b_0, .., b_{nv-1}) with b_0 the lowest bit, and
+ * variables are fixed from x_1 (the lowest bit) upward, as in ARK poly/src/evaluations/multivariate/multilinear/dense.rs.
+ * Elements are 32 bytes: arkworks Fr images or, with flag bit 0, plain integers; ANY 256-bit input is read as its residue and every
+ * output is canonical.  Flag bit 1 (value 2): the vectors are DEVICE pointers (4-byte aligned) and `stream` is the hipStream_t on which
+ * the inputs become ready (NULL = the default stream): the work is enqueued there and the call returns when the outputs are written.
+ * Without bit 1 they are host pointers, staged through buffers the handle keeps, and a non-null stream is an error.  Points,
+ * challenges, term coefficients and round results are HOST elements in the form of the call, also with bit 1.
+ *   mle_fix   fix_variables: out[b] = in[2b] + r (in[2b+1] - in[2b]) for r = point[0], then point[1] on the result, .., k times:
+ *             0 <= k <= num_vars <= 30, in holds 2^num_vars elements, out 2^(num_vars - k).  k == num_vars is evaluate (one element);
+ *             k == 0 writes the canonical copy.  out may not overlap in: a lane's pair is another block's output, so the fold cannot
+ *             be done in place.  A tile through LDS fixes up to "poly_tile_log" variables in ONE pass, as a pass of the transform does
+ *             several levels: evaluating a table reads it once, plus ceil(k / tile_log) - 1 much smaller passes that ping-pong through
+ *             the handle's work memory.
+ *   mle_eq    out[b] = prod_i (b_i ? point[i] : 1 - point[i]) for b < 2^k, k <= 30; k == 0 writes the one element 1.  Two half tables
+ *             of 2^ceil(k/2) and 2^floor(k/2) entries are built in host arithmetic; the kernel is one product per output.
+ *   sumcheck_round   one prover round.  `tables` is a HOST array of m pointers, 1 <= m <= 12, each a table of 2^num_vars elements,
+ *             1 <= num_vars <= 30; `terms` a host array of 1 <= n_terms <= 8 records: a coefficient, a factor count 1 .. 5 and the
+ *             factor indices, each below m (a repeated index is a power).  With d the largest factor count and r_prev == NULL:
+ *               evals_out[t] = sum_{b < 2^(nv-1)} sum_j c_j prod_k (f_k[2b] + t (f_k[2b+1] - f_k[2b])),   t = 0 .. d
+ *             -- d + 1 host elements, written when the call returns; there are no output vectors and `folded` is not read.  With
+ *             r_prev the call first fixes x_1 = r_prev in every table, writes the m halved tables (2^(nv-1) elements each) to the m
+ *             pointers of `folded`, none of which may overlap a table or another folded table, and returns the round evaluations of
+ *             the FOLDED tables (nv - 1 variables, so num_vars >= 2), in the same pass over the inputs: round i of a prover is one
+ *             read of every table and one write of half of it.  Lane sums, block sums, then the partial rows reduced by further
+ *             launches; sums in Fr are exact, nothing is atomic, no block waits on another.
+ *   query (mi355_msm_domain_query)   "mle_work_bytes"; "sumcheck_levels", the launches of the most recent round; "sumcheck_max_tables",
+ *             "sumcheck_max_terms" and "sumcheck_max_factors", the limits above (answered without a handle too).
+ * One call each with a flag bit, and no twin whose name ends in _device: this is the route mi355_msm_sparse_apply took, for the reason
+ * given there; the stream-ordering promise of flag bit 1 is pinned by late-producer tests in tests/test_gpu_mle.py.
+ * Results are canonical and never depend on "poly_tile_log", on host versus device pointers or on the form of the call.  There is no
+ * CPU fallback.  Errors: -1 with a message, decided before any device call, in this order: unknown flag bits, sizes outside their
+ * limits, null pointers, alignment, a stream without flag bit 1, overlap, the term list, and last the null handle. */
+typedef struct mi355_msm_sumcheck_term {
+  uint8_t coeff[32];
+  uint32_t n_factors;
+  uint32_t factors[5];
+} mi355_msm_sumcheck_term;
+RustError mi355_msm_domain_mle_fix(mi355_msm_domain* d, void* out, const void* in, unsigned num_vars, const void* point, unsigned k,
+                                   unsigned flags, void* stream);
+RustError mi355_msm_domain_mle_eq(mi355_msm_domain* d, void* out, const void* point, unsigned k, unsigned flags, void* stream);
+RustError mi355_msm_domain_sumcheck_round(mi355_msm_domain* d, void* evals_out, const void* const* tables, size_t m, unsigned num_vars,
+                                          const mi355_msm_sumcheck_term* terms, size_t n_terms, const void* r_prev, void* const* folded,
+                                          unsigned flags, void* stream);
+
 /* ---- transforms of vectors of curve points over a domain (ARK poly/src/domain/mod.rs:99-170 on DomainCoeff = G1Projective / G2Projective) ----
  * domain.fft / ifft / coset_fft / coset_ifft on GROUP elements: what turns a monomial SRS [tau^j] G into the Lagrange SRS
  * [L_i(tau)] G (kind 1), and the transform behind FK20, cq and Caulk tables.  With in[j] a point and the products scalar multiples:

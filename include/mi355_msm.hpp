@@ -7,7 +7,9 @@
 // code panics on the Rust side and throws here.  VariableBaseMSM::msm chops to the shorter slice
 // (ARK ec/src/msm/variable_base/mod.rs:44-53).
 #pragma once
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -453,6 +455,78 @@ inline std::vector<BigInteger256> groth16_witness_map(const Radix2EvaluationDoma
   const std::vector<BigInteger256> c = dom.mul(a, b);
   const std::vector<BigInteger256> h = dom.mul_sub(dom.coset_fft(dom.ifft(a)), dom.coset_fft(dom.ifft(b)), dom.coset_fft(dom.ifft(c)));
   return dom.coset_ifft(dom.divide_by_vanishing_poly_on_coset(h));
+}
+
+// ark-poly's DenseMultilinearExtension and the prover of ark-linear-sumcheck's ListOfProductsOfPolynomials on host vectors
+// (mi355_msm_domain_mle_fix, _mle_eq, _sumcheck_round): a table holds 2^nv evaluations, index b the point (b_0, .., b_{nv-1}) with b_0 the
+// lowest bit, and variables are fixed from the lowest bit upward.  The domain lends its field and its device; its size plays no part.
+inline unsigned mle_num_vars(size_t len) {
+  unsigned nv = 0;
+  while (((size_t)1 << nv) < len) nv++;
+  if (((size_t)1 << nv) != len) throw std::invalid_argument("a table holds 2^num_vars elements");
+  return nv;
+}
+
+inline std::vector<BigInteger256> mle_fix_variables(const Radix2EvaluationDomain& dom, const std::vector<BigInteger256>& evals,
+                                                    const std::vector<BigInteger256>& point) {
+  const unsigned nv = mle_num_vars(evals.size());
+  if (point.size() > nv) throw std::invalid_argument("more values than variables");
+  std::vector<BigInteger256> out(evals.size() >> point.size());
+  check(mi355_msm_domain_mle_fix(dom.handle, out.data(), evals.data(), nv, point.data(), (unsigned)point.size(), 0, nullptr));
+  return out;
+}
+
+inline BigInteger256 mle_evaluate(const Radix2EvaluationDomain& dom, const std::vector<BigInteger256>& evals, const std::vector<BigInteger256>& point) {
+  if (point.size() != mle_num_vars(evals.size())) throw std::invalid_argument("one value per variable");
+  return mle_fix_variables(dom, evals, point)[0];
+}
+
+inline std::vector<BigInteger256> eq_table(const Radix2EvaluationDomain& dom, const std::vector<BigInteger256>& point) {
+  std::vector<BigInteger256> out((size_t)1 << point.size());
+  check(mi355_msm_domain_mle_eq(dom.handle, out.data(), point.data(), (unsigned)point.size(), 0, nullptr));
+  return out;
+}
+
+// one term c * prod_k f_k of g: the coefficient and the indices of its factors (at most 5; a repeated index is a power)
+struct SumcheckTerm {
+  BigInteger256 coeff;
+  std::vector<uint32_t> factors;
+};
+
+// One prover round for g = sum_j c_j prod_k f_k over m tables of 2^nv elements: the d + 1 evaluations P(0) .. P(d).  With r_prev the
+// tables are folded by it first, in the same pass, `folded` receives the m halved tables and the evaluations are those of the folded
+// tables.
+inline std::vector<BigInteger256> sumcheck_round(const Radix2EvaluationDomain& dom, const std::vector<std::vector<BigInteger256>>& tables,
+                                                 const std::vector<SumcheckTerm>& terms, const BigInteger256* r_prev = nullptr,
+                                                 std::vector<std::vector<BigInteger256>>* folded = nullptr) {
+  if (tables.empty()) throw std::invalid_argument("no tables");
+  const size_t n = tables[0].size();
+  const unsigned nv = mle_num_vars(n);
+  std::vector<mi355_msm_sumcheck_term> recs(terms.size());
+  size_t d = 0;
+  for (size_t j = 0; j < terms.size(); j++) {
+    if (terms[j].factors.empty() || terms[j].factors.size() > 5) throw std::invalid_argument("a term takes 1 .. 5 factors");
+    std::memcpy(recs[j].coeff, &terms[j].coeff, 32);
+    recs[j].n_factors = (uint32_t)terms[j].factors.size();
+    for (size_t q = 0; q < 5; q++) recs[j].factors[q] = q < terms[j].factors.size() ? terms[j].factors[q] : 0;
+    d = std::max(d, terms[j].factors.size());
+  }
+  std::vector<const void*> ptrs;
+  for (const auto& t : tables) {
+    if (t.size() != n) throw std::invalid_argument("the tables differ in length");
+    ptrs.push_back(t.data());
+  }
+  std::vector<void*> fptrs;
+  if (r_prev) {
+    if (!folded) throw std::invalid_argument("r_prev needs a place for the folded tables");
+    folded->assign(tables.size(), std::vector<BigInteger256>(n / 2));
+    for (auto& t : *folded) fptrs.push_back(t.data());
+  }
+  std::vector<BigInteger256> evals(6);
+  check(mi355_msm_domain_sumcheck_round(dom.handle, evals.data(), ptrs.data(), ptrs.size(), nv, recs.data(), recs.size(), r_prev,
+                                        r_prev ? fptrs.data() : nullptr, 0, nullptr));
+  evals.resize(d + 1);
+  return evals;
 }
 
 // domain.fft / ifft / coset_fft / coset_ifft on a vector of G1 points (mi355_msm_fft_points): kind 0 .. 3 as for Fr; `points` may be

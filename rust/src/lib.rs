@@ -99,6 +99,15 @@ pub mod sys {
     /// completion callback of `mi355_msm_run_async` (include/mi355_msm.h `mi355_msm_done_fn`)
     pub type DoneFn = extern "C" fn(user: *mut c_void, status: Error);
 
+    /// one term `c prod_k f_k` of a sumcheck round (include/mi355_msm.h `mi355_msm_sumcheck_term`, 56 bytes): `coeff` is an Fr image
+    #[repr(C)]
+    #[derive(Clone, Copy)]
+    pub struct SumcheckTerm {
+        pub coeff: super::Fr,
+        pub n_factors: u32,
+        pub factors: [u32; 5],
+    }
+
     pub const MI355_BLS12_377_G1: c_int = 0;
     pub const MI355_BLS12_381_G1: c_int = 1;
     pub const MI355_BLS12_377_G2: c_int = 2;
@@ -249,6 +258,15 @@ pub mod sys {
         pub fn mi355_msm_sparse_apply(m: *mut c_void, out: *mut c_void, z: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
         pub fn mi355_msm_sparse_query(m: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
         pub fn mi355_msm_sparse_destroy(m: *mut c_void) -> Error;
+        // dense multilinear extensions and sumcheck prover rounds on a domain handle (ark-poly's DenseMultilinearExtension, the prover of
+        // ark-linear-sumcheck): flags bit 0: plain integers, bit 1 (value 2): the vectors are device pointers and `stream` is where they
+        // become ready, else host pointers and a null stream; points, challenges, coefficients and round results are host elements
+        pub fn mi355_msm_domain_mle_fix(d: *mut c_void, out: *mut c_void, input: *const c_void, num_vars: c_uint, point: *const c_void, k: c_uint,
+                                        flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_mle_eq(d: *mut c_void, out: *mut c_void, point: *const c_void, k: c_uint, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_sumcheck_round(d: *mut c_void, evals_out: *mut c_void, tables: *const *const c_void, m: usize, num_vars: c_uint,
+                                               terms: *const SumcheckTerm, n_terms: usize, r_prev: *const c_void, folded: *const *mut c_void,
+                                               flags: c_uint, stream: *mut c_void) -> Error;
         // the same four transforms on a vector of curve points (ark-poly's domains over DomainCoeff = G1Projective / G2Projective):
         // Affine images in and out (flags bit 1: Projective images out), offset: one arkworks Fr image on the host or null
         pub fn mi355_msm_fft_points(ctx: *mut c_void, domain: *mut c_void, out: *mut c_void, out_stride: usize, input: *const c_void, in_len: usize,
@@ -700,5 +718,88 @@ pub mod sparse {
             });
             out
         }
+    }
+}
+
+/// ark-poly's `DenseMultilinearExtension` and the prover of ark-linear-sumcheck's `ListOfProductsOfPolynomials` on the GPU
+/// (`mi355_msm_domain_mle_fix`, `_mle_eq`, `_sumcheck_round`): tables of `2^nv` evaluations, index `b` the point `(b_0, .., b_{nv-1})`
+/// with `b_0` the lowest bit, variables fixed from the lowest bit upward.
+pub mod mle {
+    use super::sys;
+    use super::Fr;
+    use ark_std::Zero;
+    use std::os::raw::c_void;
+
+    fn check(err: super::Error) {
+        if err.code != 0 {
+            panic!("{}", String::from(err));
+        }
+    }
+
+    fn num_vars(len: usize) -> u32 {
+        assert!(len.is_power_of_two(), "a table holds 2^num_vars elements");
+        len.trailing_zeros()
+    }
+
+    /// `fix_variables`: `2^(nv - point.len())` elements
+    ///
+    /// # Safety
+    /// `domain` is a live handle of `sys::mi355_msm_domain_create` over the field of `Fr`.
+    pub unsafe fn fix_variables(domain: *mut c_void, evals: &[Fr], point: &[Fr]) -> Vec<Fr> {
+        let nv = num_vars(evals.len());
+        assert!(point.len() as u32 <= nv, "more values than variables");
+        let mut out = vec![Fr::zero(); evals.len() >> point.len()];
+        check(sys::mi355_msm_domain_mle_fix(domain, out.as_mut_ptr() as *mut c_void, evals.as_ptr() as *const c_void, nv,
+                                            point.as_ptr() as *const c_void, point.len() as u32, 0, std::ptr::null_mut()));
+        out
+    }
+
+    /// `evaluate`
+    ///
+    /// # Safety
+    /// as `fix_variables`
+    pub unsafe fn evaluate(domain: *mut c_void, evals: &[Fr], point: &[Fr]) -> Fr {
+        assert_eq!(point.len() as u32, num_vars(evals.len()), "one value per variable");
+        fix_variables(domain, evals, point)[0]
+    }
+
+    /// `eq(b, point)` for `b < 2^point.len()`
+    ///
+    /// # Safety
+    /// as `fix_variables`
+    pub unsafe fn eq_table(domain: *mut c_void, point: &[Fr]) -> Vec<Fr> {
+        let mut out = vec![Fr::zero(); 1usize << point.len()];
+        check(sys::mi355_msm_domain_mle_eq(domain, out.as_mut_ptr() as *mut c_void, point.as_ptr() as *const c_void, point.len() as u32, 0,
+                                           std::ptr::null_mut()));
+        out
+    }
+
+    /// One prover round for `sum_j c_j prod_{k in S_j} f_k`: the `d + 1` evaluations; with `r_prev` the tables are folded first and
+    /// come back halved beside the evaluations of the folded tables.
+    ///
+    /// # Safety
+    /// as `fix_variables`
+    pub unsafe fn sumcheck_round(domain: *mut c_void, tables: &[Vec<Fr>], terms: &[(Fr, Vec<usize>)], r_prev: Option<Fr>) -> (Vec<Fr>, Vec<Vec<Fr>>) {
+        let n = tables[0].len();
+        let nv = num_vars(n);
+        let recs: Vec<sys::SumcheckTerm> = terms.iter().map(|(c, fs)| {
+            assert!(!fs.is_empty() && fs.len() <= 5, "a term takes 1 .. 5 factors");
+            let mut rec = sys::SumcheckTerm { coeff: *c, n_factors: fs.len() as u32, factors: [0; 5] };
+            for (q, f) in fs.iter().enumerate() {
+                rec.factors[q] = *f as u32;
+            }
+            rec
+        }).collect();
+        let d = terms.iter().map(|(_, fs)| fs.len()).max().unwrap_or(0);
+        let ptrs: Vec<*const c_void> = tables.iter().map(|t| { assert_eq!(t.len(), n); t.as_ptr() as *const c_void }).collect();
+        let mut evals = vec![Fr::zero(); 6];
+        let mut folded: Vec<Vec<Fr>> = if r_prev.is_some() { tables.iter().map(|_| vec![Fr::zero(); n / 2]).collect() } else { Vec::new() };
+        let fptrs: Vec<*mut c_void> = folded.iter_mut().map(|t| t.as_mut_ptr() as *mut c_void).collect();
+        let r = r_prev.unwrap_or_else(Fr::zero);
+        check(sys::mi355_msm_domain_sumcheck_round(domain, evals.as_mut_ptr() as *mut c_void, ptrs.as_ptr(), tables.len(), nv, recs.as_ptr(), recs.len(),
+                                                   if r_prev.is_some() { &r as *const Fr as *const c_void } else { std::ptr::null() },
+                                                   if r_prev.is_some() { fptrs.as_ptr() } else { std::ptr::null() }, 0, std::ptr::null_mut()));
+        evals.truncate(d + 1);
+        (evals, folded)
     }
 }

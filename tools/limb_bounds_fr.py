@@ -21,6 +21,7 @@ All margins must be positive (tests/test_fr_consts.py runs it); the host build c
     python tools/limb_bounds_fr.py --scan     (the sum scan and the permutation product of csrc/scan.hpp: analyse_scan below)
     python tools/limb_bounds_fr.py --quotient (the rows of the Plonk quotient and the linear combination of csrc/quotient.hpp: analyse_quotient below)
     python tools/limb_bounds_fr.py --sparse   (the lane sums of the sparse matrix-vector product of csrc/sparse.hpp: analyse_sparse below)
+    python tools/limb_bounds_fr.py --mle      (the folds, extrapolations, products and sums of csrc/mle.hpp: analyse_mle below)
 """
 import sys
 
@@ -378,8 +379,110 @@ def analyse_sparse(name, r, out):
     return ok
 
 
+MLE_POINTS, MLE_TERMS, MLE_FACTORS = 4, 8, 5     # MLE_PTS, MLE_MAX_TERMS, MLE_MAX_FACTORS of csrc/mle.hpp
+MLE_TREE_LEVELS, MLE_TREE_REDUCE = 8, 4           # a block tree has at most 256 lanes and multiplies by 1 after its fourth level
+
+
+def analyse_mle(name, r, out):
+    """The chains of csrc/mle.hpp (python tools/limb_bounds_fr.py --mle), carried exactly as the code performs them.  The lazy value is
+    always the FIRST operand of a product; the second is a canonical constant or, inside a term, the running product in class M
+    (normalised, below 2r) -- so that product is judged with a class-M second operand: r + a b / R must stay below 2r.
+      the fold            (1 - r) x + r y: two products by canonical constants, one limb-wise sum (below 4r, limbs below 2^30), which is
+                          the first operand of the next level's products, of the conversion on the way out, or of nothing else.
+      the extrapolation   lo, hi in class M; diff = hi + BIAS4 - lo, one carry pass; e_2 = hi + diff, e_3 = e_2 + diff, one carry
+                          pass, e_4, e_5.
+      a term              P starts as the canonical coefficient; factor by factor P = fr_mul(e_t, P).
+      the sums            MLE_POINTS * MLE_TERMS class-M products into a lane accumulator, one carry pass each; the product by 1; the
+                          block tree with a carry pass per level and the product by 1 after its fourth level."""
+    import math
+
+    rl = limbs(r)
+    ok = True
+    worst_col = 0
+
+    def margin(what, have, limit):
+        nonlocal ok
+        m = limit - have
+        ok &= m > 0
+        out.append("  %-86s %s (limit 2^%.2f, margin %.3e)" % (what, "ok " if m > 0 else "BAD", math.log2(limit), m))
+
+    top_m = (2 * r) >> (B * (N - 1))
+    class_m = [MASK] * (N - 1) + [top_m]
+    w = [MASK] * (N - 1) + [rl[N - 1]]
+    any256 = [MASK] * (N - 1) + [(1 << (256 - B * (N - 1))) - 1]
+    bias = bias4(r)
+
+    def first_operand(what, l, val, second):
+        """val: the value bound in units of r (a fraction for a raw input); second: w (canonical) or class_m"""
+        nonlocal worst_col
+        col = max(columns(l, second, rl))
+        worst_col = max(worst_col, col)
+        margin(what + ": value %.1fr against R" % val, int(val * r), R)
+        margin(what + ": largest limb against 2^31", max(l), 1 << 31)
+        margin(what + ": largest column against 2^64", col, 1 << 64)
+        sec_val = 2 * r if second is class_m else r
+        margin(what + ": product r + a b / R against 2r", r + int(val * r) * sec_val // R + 1, 2 * r)
+
+    def add(what, a, b, carry=True):
+        sm = [x + y for x, y in zip(a, b)]
+        margin(what + ": limb-wise sum against 2^32", max(sm), 1 << 32)
+        if not carry:
+            return sm
+        margin(what + ": top limb into the carry pass against 2^31", sm[N - 1] + (sm[N - 2] >> B), 1 << 31)
+        return carry_pass(sm)
+
+    raw = (1 << 256) / r
+    out.append("%s: r = %.3f * 2^252, R / r = %.2f  (the chains of mle.hpp: %d points a lane, %d terms of %d factors)"
+               % (name, r / 2**252, R / r, MLE_POINTS, MLE_TERMS, MLE_FACTORS))
+    margin("2r against a packed element (2^256)", 2 * r, 1 << 256)
+    first_operand("an element or a pair on the way in: any 256-bit value times a canonical constant", any256, raw, w)
+    # the fold
+    lazy = add("the fold (1 - r) x + r y: two class-M products", class_m, class_m, carry=False)
+    first_operand("the fold (1 - r) x + r y as the first operand of the next level or of the conversion", lazy, 4, w)
+    # the extrapolation
+    for i in range(N):
+        margin("BIAS4 limb %d covers the limb of lo" % i, class_m[i], bias[i] + 1)
+    diff = add("diff = hi + 4r - lo", class_m, bias)
+    e, val = list(class_m), 2                     # e_1 = hi
+    first_operand("e_0 = lo, e_1 = hi against the running product", e, val, class_m)
+    for t in range(2, MLE_FACTORS + 1):
+        e = add("e_%d = e_%d + diff" % (t, t - 1), e, diff, carry=False)
+        val += 6
+        first_operand("e_%d against the running product" % t, e, val, class_m)
+        if t == 3:
+            margin("e_3: top limb into the carry pass against 2^31", e[N - 1] + (e[N - 2] >> B), 1 << 31)
+            e = carry_pass(e)
+    for k in range(1, MLE_FACTORS + 1):
+        # every factor meets a class-M running product (the first one the canonical coefficient, which is smaller)
+        first_operand("factor %d of a term at t = %d" % (k, MLE_FACTORS), e, val, class_m)
+    # the sums
+    acc, av = [0] * N, 0
+    for i in range(1, MLE_POINTS * MLE_TERMS + 1):
+        acc = add("the lane accumulator, add %2d" % i, acc, class_m)
+        av += 2
+    first_operand("the lane accumulator as the first operand of the product by 1", acc, av, w)
+    node, nv = list(class_m), 2
+    for lvl in range(1, MLE_TREE_LEVELS + 1):
+        node = add("the block tree, level %d" % lvl, node, node)
+        nv *= 2
+        if lvl == MLE_TREE_REDUCE:
+            first_operand("the block tree after level %d as the first operand of the product by 1" % lvl, node, nv, w)
+            node, nv = list(class_m), 2
+    first_operand("the block sum as the first operand of the product by 1", node, nv, w)
+    rows = add("a lane of a further level: four class-M rows", add("two rows", class_m, class_m), add("two rows", class_m, class_m))
+    first_operand("a lane of a further level as the first operand of the product by 1", rows, 8, w)
+    margin("the chain's largest column against 2^64", worst_col, 1 << 64)
+    out.append("  largest column: %d = 2^%.3f" % (worst_col, math.log2(worst_col)))
+    return ok
+
+
 def main():
     out = []
+    if "--mle" in sys.argv[1:]:
+        ok = all([analyse_mle(name, r, out) for name, r in FIELDS.items()])
+        print("\n".join(out))
+        print("all margins positive" if ok else "A MARGIN IS NOT POSITIVE")
+        return 0 if ok else 1
     if "--sparse" in sys.argv[1:]:
         ok = all([analyse_sparse(name, r, out) for name, r in FIELDS.items()])
         print("\n".join(out))
