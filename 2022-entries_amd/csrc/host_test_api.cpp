@@ -486,6 +486,60 @@ extern "C" int ht_fold_both(int curve, const uint8_t* pts, size_t stride, const 
   return t_fold_both<Bls12_377_G1>(pts, stride, mult, windows, c, te, out_generic, out_fold64);
 }
 
+// The fold of a wide anchored window (host_fold64.hpp fold_windows64 / fold_windows_te64 with `wide_a`): `windows + 1` window sums given
+// as affine images -- rows 0 .. windows - 1 the bucket sets, row `windows` the plain sum R of bucket set wide_a + 1 -- folded on the
+// short-Weierstrass image into out_sw and, te != 0 (BLS12-377 G1 only), on the twisted-Edwards image into out_te.  ok[0], ok[1]: what the
+// two folds returned (the short-Weierstrass one cannot fail: 1; -1: not run).  wide_a = -1 is the plain fold of rows 0 .. windows - 1.
+template <class C>
+static int t_fold_wide(const uint8_t* pts, size_t stride, int windows, int c, int wide_a, int te, uint8_t* out_sw, uint8_t* out_te, int* ok) {
+  using E = typename C::E;
+  using F = typename E::Fld;
+  using El = typename E::T;
+  typename E::Md md;
+  const auto& f = Fold64Of<E>::get();
+  using FC = std::decay_t<decltype(f)>;
+  if (windows < 1 || windows + 1 > 64 || c < 2 || wide_a < -1 || (wide_a >= 0 && wide_a + 2 != windows)) return 1;
+  XyzzT<El> sums[64];
+  ok[0] = ok[1] = -1;
+  for (int w = 0; w <= windows; w++) {
+    AffineT<El> a;
+    xyzz_set_inf<E>(sums[w]);
+    if (!affine_from_abi<E>(a, pts + (size_t)w * stride, md)) {
+      const uint64_t k[4] = {1, 0, 0, 0};
+      xyzz_mul_u64x4<E>(sums[w], a, k, md);
+    }
+  }
+  XyzzG64<typename FC::El> h;
+  fold_windows64<F>(f, h, sums, windows, c, wide_a);
+  ok[0] = 1;
+  sw64_to_abi(f, out_sw, h);
+  if (te) {
+    if constexpr (std::is_same<E, FpEl<Bls12_377_Fq>>::value) {
+      for (int w = 0; w <= windows; w++) {
+        AffineT<El> a;
+        te_set_identity<F>(sums[w]);
+        if (!affine_from_abi<E>(a, pts + (size_t)w * stride, md)) {
+          TeAffine t;
+          if (!te_map_host(t, pts + (size_t)w * stride, md)) return 1;
+          te_madd<F>(sums[w], t, false, md);
+        }
+      }
+      ok[1] = fold_windows_te64<F>(f, h, sums, windows, c, wide_a) ? 1 : 0;
+      if (ok[1]) sw64_to_abi(f, out_te, h);
+    } else {
+      return 1;
+    }
+  }
+  return 0;
+}
+extern "C" int ht_fold_wide(int curve, const uint8_t* pts, size_t stride, int windows, int c, int wide_a, int te, uint8_t* out_sw, uint8_t* out_te,
+                            int* ok) {
+  if (!pts || !out_sw || !ok || (te && !out_te)) return 1;
+  if (curve == 0) return t_fold_wide<Bls12_377_G1>(pts, stride, windows, c, wide_a, te, out_sw, out_te, ok);
+  if (curve == 2) return te ? 1 : t_fold_wide<Bls12_377_G2>(pts, stride, windows, c, wide_a, 0, out_sw, out_te, ok);
+  return 1;
+}
+
 // ---- the op table of devtest_ops.hpp on the host: the twin of libmsm_devtest.so's msm_devtest_run ------------------------
 // Same raw limb records in, same limbs out (the device build replaces the portable multiply loops, the Montgomery step and
 // the selects with GCN assembly); MSM_CHECK is armed here, so a record that would overflow a 64-bit column or underflow a

@@ -440,6 +440,9 @@ struct mi355_msm_ctx {
   uint64_t peer_stagings = 0;     // sharded contexts: slices (bases or scalars) pulled from ANOTHER device's memory into a shard's own (msm_sharded.hpp)
   long opt_force_peer_staging = 0;   // test hook: take those branches although the source lies on the shard's own device (logical shards)
   uint32_t last_bucket_windows = 0, last_l1_bits = 0, last_l1_bins = 0, last_passes = 0;   // grouping geometry of the most recent chunk
+  // ... and how its buckets were reduced: 0 recursive chunked levels, 1 direct scan, 2 / 3 one chunked level then a scan on full / padded rows;
+  // the chunks per bucket set of the first level (T0) and the elements of a scan row (scan_nb)
+  uint32_t last_reduce_path = 0, last_reduce_chunks = 0, last_reduce_row = 0;
   uint32_t auto_levels = 0;       // "precompute" = 2: the table levels chosen from the free HBM at the last set_bases (0 = none)
   uint64_t debug_checks = 0;      // -DMSM_DEBUG builds: invariant checks run so far (csrc/partition.hpp)
   size_t chunk_cap = 0;           // what the most recent run had to cap its chunks at after an allocation failed (0 = it never had to); reported, not kept
@@ -1470,6 +1473,9 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
   ctx->last_info[5] = p.nlanes;
   ctx->last_info[7] = kEdwards<G> ? 1 : 0;
   ctx->last_bucket_windows = p.bucket_windows;
+  ctx->last_reduce_path = !p.reduce_scan ? 0 : p.scan_direct ? 1 : p.scan_nb == p.T0 ? 2 : 3;
+  ctx->last_reduce_chunks = p.T0;
+  ctx->last_reduce_row = p.scan_nb;
   ctx->last_l1_bits = gp.hb;
   ctx->last_l1_bins = gp.nbins;
   {
@@ -2647,7 +2653,8 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
       static const char* const kAll[] = {"twisted_edwards", "assume_subgroup", "carry"};
       static const char* const kMean[] = {"table_levels", "table_window_bits"};
       static const char* const kFirst[] = {"precompute", "g2_paired", "guard_tail", "te_limb_bits", "anchor", "anchor_wide"};
-      static const char* const kMax[] = {"bucket_windows", "l1_bits", "l1_bins", "group_passes", "anchored_window", "anchor_sum_us", "anchor_wide_active"};
+      static const char* const kMax[] = {"bucket_windows", "l1_bits", "l1_bins", "group_passes", "anchored_window", "anchor_sum_us", "anchor_wide_active",
+                                          "reduce_path", "reduce_chunks", "reduce_row"};
       auto in = [&](const char* const* set, size_t n) {
         for (size_t i = 0; i < n; i++)
           if (k == set[i]) return true;
@@ -2657,7 +2664,7 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
         *value = all;
       } else if (in(kMean, 2)) {
         *value = sum / ctx->shards.size();
-      } else if (in(kFirst, 6) || in(kMax, 7)) {
+      } else if (in(kFirst, 6) || in(kMax, 10)) {
         uint64_t first = 0, mx = 0;
         for (size_t g = 0; g < ctx->shards.size(); g++) {
           uint64_t v = 0;
@@ -2753,6 +2760,12 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
       *value = ctx->bases.bytes + ctx->te_bases.bytes + ctx->inf.bytes;
     else if (k == "bucket_windows")   // of the most recent chunk: bucket sets the reduction walks (= windows without tables)
       *value = ctx->last_bucket_windows;
+    else if (k == "reduce_path")      // ... how they were reduced: 0 recursive chunked levels only, 1 direct scan on the buckets,
+      *value = ctx->last_reduce_path; //     2 one chunked level then a scan on full rows (reduce_row == reduce_chunks), 3 the same on padded rows
+    else if (k == "reduce_chunks")    // ... chunks per bucket set on the first chunked level (Plan::T0)
+      *value = ctx->last_reduce_chunks;
+    else if (k == "reduce_row")       // ... elements of a scan row (Plan::scan_nb)
+      *value = ctx->last_reduce_row;
     else if (k == "l1_bits")          // ... bucket bits level 1 of the grouping resolved, its bins, and the generic passes behind it
       *value = ctx->last_l1_bits;
     else if (k == "l1_bins")

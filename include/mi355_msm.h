@@ -298,6 +298,9 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value);
  * recent chunk, 0 = plain digits), "anchor_sums" (sums of bases computed so far), "anchor_sum_us" (host time the most recent run spent on one),
  * "anchor_wide" (the option; 0 once the context has stopped using it), "anchor_wide_active" (the most recent chunk ran with it),
  * "anchor_wide_fallbacks" (chunks / batches repeated without it), "anchor_wide_demotions",
+ * "reduce_path" (how the most recent chunk's buckets were reduced: 0 recursive chunked levels only, 1 direct scan on the buckets, 2 one
+ * chunked level then a scan on full rows, 3 the same on rows padded to a power of two), "reduce_chunks" (chunks per bucket set on the
+ * first level) and "reduce_row" (elements of a scan row),
  * "device", "bases", "table_levels", "table_window_bits", "base_bytes" (device bytes held for the bases). */
 RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value);
 /* Per-stage device time (ms, HIP events on the launch stream) of the most recent run, summed over its chunks

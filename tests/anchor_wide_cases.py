@@ -1,5 +1,6 @@
 """Host model of the signed-digit recoding with an anchored window (csrc/partition.hpp next_digit, csrc/partition_plan.hpp part_plan),
-in plain Python integers, for tests/test_anchor_wide_model.py (CPU) and tests/test_gpu_anchor_wide.py (GPU).
+in plain Python integers, for tests/test_anchor_wide_model.py (CPU), tests/test_gpu_anchor_wide.py and tests/test_gpu_anchor_wide_paths.py
+(GPU; the scalar lists of the latter are built at the end of this file).
 
 recode(k, c, bits, wide) returns what the level-1 kernels emit for the 256-bit scalar k and what the host adds for it:
 
@@ -9,6 +10,8 @@ recode(k, c, bits, wide) returns what the level-1 kernels emit for the 256-bit s
 or None when the wide window refuses the scalar (a bit at or above `bits` is set: the engine repeats the chunk with wide off).
 value(entries, constant, c, bits, wide) folds them the way the bucket reduction and HostTail::fold do: bucket (g, j) weighs j 2^(c g),
 except the upper bucket set of a wide window, which shares the weight of the window below it and whose buckets weigh 2^(c-1) more."""
+
+import random
 
 R377 = 0x12ab655e9a2ca55660b44d1e5c37b00159aa76fed00000010a11800000000001
 R381 = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
@@ -84,3 +87,63 @@ def edge_scalars(c, bits=253, r=R377):
         vals.append((v << (c * a)) | low)           # ... with a carry arriving: v + 1 (2^(c+1) for v = 2^(c+1) - 1)
         vals.append((v << (c * a)) | (low >> 1))    # ... and without one
     return [v for v in vals if v < top]
+
+
+# ---- scalar lists for tests/test_gpu_anchor_wide_paths.py -----------------------------------------------------------------------------
+def uniform_scalars(n, seed, r=R377):
+    rng = random.Random(seed)
+    return [rng.randrange(r) for _ in range(n)]
+
+
+def planted_edges(c, n, seed, bits=253, r=R377):
+    """edge_scalars(c) planted among n uniform canonical scalars (every fifth index from 3 on)"""
+    vals = uniform_scalars(n, seed, r)
+    planted = edge_scalars(c, bits, r)
+    assert 3 + 5 * len(planted) < n
+    for i, v in enumerate(planted):
+        vals[3 + 5 * i] = v
+    return vals
+
+
+def equal_values(c, bits=253):
+    """name -> the value every scalar of an all-equal list takes: the wide window's digit at its ends, on both sides of the two bucket sets"""
+    a = anchor_of(c, bits)
+    full, half = 1 << c, 1 << (c - 1)
+    return {
+        "zero": 0,                                             # every digit -2^c: the last bucket of the upper set holds -(sum of the bases)
+        "upper_first": (full + half + 1) << (c * a),           # bucket 1 of the upper set, the lower set empty
+        "lower_last": (full + half) << (c * a),                # the last bucket of the lower set, the upper set and R empty
+        "no_entry": full << (c * a),                           # s = 0: no entry at all in the window
+        "all_ones": (1 << bits) - 1,
+    }
+
+
+def bad_scalar(seed, bits=253):
+    """a scalar with bit `bits` set: the wide window refuses it"""
+    return (1 << bits) | random.Random(seed).randrange(1 << bits)
+
+
+def entry_count(vals, c, wide, skip=(), bits=253):
+    """non-zero digits the device groups for these scalars (bases at the indices `skip` are at infinity: no entries)"""
+    memo = {}
+    total = 0
+    for i, v in enumerate(vals):
+        if i in skip:
+            continue
+        if v not in memo:
+            memo[v] = len(recode(v, c, bits, wide)[0])
+        total += memo[v]
+    return total
+
+
+def montgomery_images(vals, r=R377, bit=253):
+    """v 2^256 mod r for canonical v, every other one moved up by r or 2 r so that bit `bit` of the IMAGE is set (the value is the same)"""
+    out = []
+    for i, v in enumerate(vals):
+        assert 0 <= v < r
+        img = (v << 256) % r
+        if i % 2 == 0:
+            img += r if (img + r) >> bit & 1 else 2 * r
+            assert img >> bit & 1 and img < 1 << 256
+        out.append(img)
+    return out

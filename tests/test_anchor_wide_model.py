@@ -15,7 +15,7 @@ def test_where_the_wide_window_exists():
     assert [c for c in range(5, 24) if m.wide_fits(c, 255)] == []
 
 
-@pytest.mark.parametrize("c", [12, 14, 18, 21])
+@pytest.mark.parametrize("c", [6, 7, 9, 12, 14, 18, 21])
 def test_recoding_is_exact(c):
     rng = random.Random(c)
     ks = m.edge_scalars(c) + [rng.randrange(m.R377) for _ in range(8000)] + [rng.randrange(1 << 253) for _ in range(2000)]
@@ -34,7 +34,7 @@ def test_recoding_is_exact(c):
     assert seen_sets == set(range(a + 2))          # both bucket sets of the wide window are in use
 
 
-@pytest.mark.parametrize("c", [12, 21])
+@pytest.mark.parametrize("c", [6, 12, 14, 18, 21])
 def test_the_wide_windows_edges(c):
     a, full, half = m.anchor_of(c, 253), 1 << c, 1 << (c - 1)
 

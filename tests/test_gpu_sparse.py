@@ -192,8 +192,8 @@ def test_refusals_on_the_handle(ea, domains, torch_, consts):
 @pytest.mark.parametrize("field", FIELDS)
 def test_apply_after_late_producers_on_a_side_stream(domains, torch_, consts, field):
     """flag bit 1 promises what the _device calls promise: the work is enqueued on the stream on which z becomes ready.  z has a producer
-    that is late on a side stream and out= has a late producer of its own; both windows are open immediately before the call, both
-    producers took their time, the result is the model's and no poison is left"""
+    that is late on a side stream and fills out= behind the same delay (a result written on any other stream is overwritten afterwards);
+    the window is open immediately before the call, the producer took its time, the result is the model's and no poison is left"""
     torch = torch_
     E, L = consts
     dom = domains(field, 4)
@@ -205,8 +205,11 @@ def test_apply_after_late_producers_on_a_side_stream(domains, torch_, consts, fi
     delay = st.Delay(torch, stream)
     with matrix_of(dom, c, 0) as M:
         for with_out in (False, True):
-            z = st.late(torch, c.z_raw(), stream, delay, shape=(c.cols, 32))
-            out = st.late_out(torch, (c.rows, 32), stream, delay) if with_out else None
+            # (out= is allocated and poisoned BEFORE the delay is enqueued, as everywhere else: poisoned() synchronises the default stream,
+            #  and a default-stream launch can queue up behind the delay -- which hardware queue a stream shares depends on how many streams
+            #  the process has made -- so that z's producer would be through by the time the call is made)
+            out = st.poisoned(torch, (c.rows, 32)) if with_out else None
+            z = st.late(torch, c.z_raw(), stream, delay, shape=(c.cols, 32), fill=[out] if with_out else ())
             made = [z] + ([out] if with_out else [])
             with torch.cuda.stream(stream):
                 assert all(st.window_open(t.produced) for t in made), "invalid: a producer had finished before the call was made"
