@@ -36,6 +36,9 @@ from .msm import (  # noqa: F401
     mul_by_cofactor,
     Radix2EvaluationDomain,
     SparseMatrix,
+    Poseidon,
+    PoseidonMerkleTree,
+    poseidon_parameters,
 )
 from .dist import all_gather_partials, shard_bounds, sharded_msm  # noqa: F401,E402
 from . import formats  # noqa: F401,E402

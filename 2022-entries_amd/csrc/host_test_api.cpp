@@ -1859,6 +1859,163 @@ int ht_mle_round(int field, unsigned tile_log, unsigned flags, unsigned m, unsig
 }
 }
 
+// ---- Poseidon sponges and Merkle trees (poseidon.hpp): the table create derives and the kernel body, lane by lane, with the limb-bound
+// checker armed ---------------------------------------------------------------------------------------------------------------------
+#include "poseidon.hpp"
+
+template <class FR>
+struct HostPosRun {
+  void hash(const PosRun& p) {
+    if (p.n_out == 0) return;
+    std::vector<uint32_t> state((size_t)2 * p.tab.t * FR_NL);
+    for (uint64_t i = 0; i < p.n; i++) pos_lane<FR>(PosState<1>{state.data()}, p, i);
+  }
+  void fill(uint32_t* first, uint64_t count) {
+    for (uint64_t i = 1; i < count; i++) memcpy(first + i * 8, first, 32);
+  }
+};
+
+template <class FR>
+static int t_pos_plan(PosPlan& pl, std::vector<uint8_t>& img, PosTab& tab, unsigned create_flags, uint32_t rate, uint32_t alpha, uint32_t rf, uint32_t rp,
+                      const uint8_t* ark, const uint8_t* mds) {
+  const uint32_t t = rate + 1;
+  std::vector<Fr> a((size_t)(rf + rp) * t), m((size_t)t * t);
+  for (size_t i = 0; i < a.size(); i++) poly_scalar<FR>(a[i], ark + 32 * i, (create_flags & kPosNormal) != 0);
+  for (size_t i = 0; i < m.size(); i++) poly_scalar<FR>(m[i], mds + 32 * i, (create_flags & kPosNormal) != 0);
+  char why[256];
+  if (!pos_build<FR>(pl, rate, alpha, rf, rp, a.data(), m.data(), why, sizeof why)) return -2;
+  pos_table_fill(img, pl);
+  tab = pos_table_at(img.data(), pl);
+  return 0;
+}
+
+template <class FR>
+static PosRun t_pos_base(const PosTab& tab, unsigned flags, int sparse) {
+  PosRun r{};
+  r.tab = tab;
+  r.sparse = sparse ? 1u : 0u;
+  fr_const<FR>(r.cin, (flags & kPosNormal) ? 1 : 0);
+  fr_const<FR>(r.cout, (flags & kPosNormal) ? 3 : 2);
+  return r;
+}
+
+template <class FR>
+static int t_pos_hash(unsigned create_flags, unsigned flags, uint32_t rate, uint32_t alpha, uint32_t rf, uint32_t rp, const uint8_t* ark, const uint8_t* mds,
+                      int sparse, uint64_t n, uint32_t in_len, uint32_t n_out, const uint8_t* header, const uint8_t* in, uint8_t* out) {
+  PosPlan pl;
+  std::vector<uint8_t> img;
+  PosTab tab;
+  if (int e = t_pos_plan<FR>(pl, img, tab, create_flags, rate, alpha, rf, rp, ark, mds)) return e;
+  // buffers of the exact size
+  std::vector<uint32_t> src(n * in_len * 8), dst(n * n_out * 8, 0xa5a5a5a5u);
+  if (src.size()) memcpy(src.data(), in, src.size() * 4);
+  PosRun r = t_pos_base<FR>(tab, flags, sparse);
+  r.in = src.data();
+  r.out = dst.data();
+  r.n = n;
+  r.row_stride = in_len;
+  r.in_len = in_len;
+  r.n_out = n_out;
+  r.has_header = header ? 1u : 0u;
+  if (header)
+    for (uint32_t e = 0; e < rate; e++) poly_scalar<FR>(r.hdr[e], header + 32 * e, (flags & kPosNormal) != 0);
+  HostPosRun<FR> run;
+  run.hash(r);
+  if (dst.size()) memcpy(out, dst.data(), dst.size() * 4);
+  return 0;
+}
+
+template <class FR>
+static int t_pos_merkle(unsigned create_flags, unsigned flags, uint32_t rate, uint32_t alpha, uint32_t rf, uint32_t rp, const uint8_t* ark, const uint8_t* mds,
+                        int sparse, uint64_t n_leaves, uint32_t leaf_len, const uint8_t* domain_sep, const uint8_t* leaves, uint8_t* tree_out) {
+  PosPlan pl;
+  std::vector<uint8_t> img;
+  PosTab tab;
+  if (int e = t_pos_plan<FR>(pl, img, tab, create_flags, rate, alpha, rf, rp, ark, mds)) return e;
+  uint64_t P = 1;
+  while (P < n_leaves) P *= 2;
+  std::vector<uint32_t> src(n_leaves * leaf_len * 8), dst((2 * P - 1) * 8, 0xa5a5a5a5u), zeros(16, 0);
+  if (src.size()) memcpy(src.data(), leaves, src.size() * 4);
+  const PosRun base = t_pos_base<FR>(tab, flags, sparse);
+  Fr hl[POS_MAX_RATE], hn[POS_MAX_RATE];
+  for (uint32_t e = 0; e < POS_MAX_RATE; e++) {
+    fr_zero(hl[e]);
+    fr_zero(hn[e]);
+  }
+  uint8_t len[32] = {0};
+  poly_scalar<FR>(hl[0], domain_sep, (flags & kPosNormal) != 0);
+  hn[0] = hl[0];
+  for (int q = 0; q < 4; q++) len[q] = (uint8_t)((leaf_len + 1) >> (8 * q));
+  poly_scalar<FR>(hl[1], len, true);
+  len[0] = 3;
+  len[1] = len[2] = len[3] = 0;
+  poly_scalar<FR>(hn[1], len, true);
+  HostPosRun<FR> run;
+  pos_merkle_chain(run, base, dst.data(), src.data(), n_leaves, leaf_len, hl, hn, zeros.data());
+  memcpy(tree_out, dst.data(), dst.size() * 4);
+  return 0;
+}
+
+template <class FR>
+static int t_pos_permute(unsigned create_flags, uint32_t rate, uint32_t alpha, uint32_t rf, uint32_t rp, const uint8_t* ark, const uint8_t* mds, int sparse,
+                         const uint8_t* state_in, uint8_t* state_out, uint64_t* info) {
+  PosPlan pl;
+  std::vector<uint8_t> img;
+  PosTab tab;
+  if (int e = t_pos_plan<FR>(pl, img, tab, create_flags, rate, alpha, rf, rp, ark, mds)) return e;
+  const uint32_t t = rate + 1;
+  std::vector<uint32_t> state((size_t)2 * t * FR_NL);
+  const PosState<1> st{state.data()};
+  for (uint32_t e = 0; e < t; e++) {
+    Fr x;
+    poly_scalar<FR>(x, state_in + 32 * e, true);
+    st.store(e, x);
+  }
+  const uint32_t cur = pos_permute<FR>(st, tab, sparse != 0, 0);
+  for (uint32_t e = 0; e < t; e++) {
+    Fr x;
+    st.load(x, cur * t + e);
+    poly_scalar_out<FR>(state_out + 32 * e, x, true);
+  }
+  if (info) {
+    info[0] = pl.products_d;
+    info[1] = pl.products_s;
+    info[2] = info[3] = 0;
+    for (uint32_t f : pl.red_d) info[2] += (f != 0);
+    for (uint32_t f : pl.red_s) info[3] += (f != 0);
+  }
+  return 0;
+}
+
+extern "C" {
+// mi355_msm_poseidon_create + _hash / _merkle on the host: create_flags bit 0, ark and mds are plain integers; flags bit 0, the elements
+// of the call are.  -2: create refuses the parameters.  ht_poseidon_permute: one permutation of t plain integers; info receives the
+// products of the dense and the sparse form and the rounds with a reduction in each.
+unsigned ht_poseidon_block_lanes(void) { return POS_LANES; }
+static int ht_pos_shape(int field, unsigned create_flags, unsigned rate, unsigned alpha, unsigned rf, unsigned rp, const void* ark, const void* mds) {
+  return (field == 0 || field == 1) && !(create_flags & ~kPosNormal) && !pos_check_shape(rate, alpha, rf, rp) && ark && mds;
+}
+int ht_poseidon_hash(int field, unsigned create_flags, unsigned flags, unsigned rate, unsigned alpha, unsigned rf, unsigned rp, const uint8_t* ark,
+                     const uint8_t* mds, int sparse, uint64_t n, unsigned in_len, unsigned n_out, const uint8_t* header, const uint8_t* in, uint8_t* out) {
+  if (!ht_pos_shape(field, create_flags, rate, alpha, rf, rp, ark, mds) || (flags & ~kPosNormal) || n > (1u << 16) || in_len > 4096 || n_out > 4096 ||
+      (n && in_len && !in) || (n && n_out && !out))
+    return -1;
+  return POLY_FIELD(t_pos_hash, create_flags, flags, rate, alpha, rf, rp, ark, mds, sparse, n, in_len, n_out, header, in, out);
+}
+int ht_poseidon_merkle(int field, unsigned create_flags, unsigned flags, unsigned rate, unsigned alpha, unsigned rf, unsigned rp, const uint8_t* ark,
+                       const uint8_t* mds, int sparse, uint64_t n_leaves, unsigned leaf_len, const uint8_t* domain_sep, const uint8_t* leaves, uint8_t* tree_out) {
+  if (!ht_pos_shape(field, create_flags, rate, alpha, rf, rp, ark, mds) || (flags & ~kPosNormal) || rate < 2 || n_leaves < 1 || n_leaves > (1u << 12) ||
+      leaf_len > 4096 || !domain_sep || (leaf_len && !leaves) || !tree_out)
+    return -1;
+  return POLY_FIELD(t_pos_merkle, create_flags, flags, rate, alpha, rf, rp, ark, mds, sparse, n_leaves, leaf_len, domain_sep, leaves, tree_out);
+}
+int ht_poseidon_permute(int field, unsigned create_flags, unsigned rate, unsigned alpha, unsigned rf, unsigned rp, const uint8_t* ark, const uint8_t* mds,
+                        int sparse, const uint8_t* state_in, uint8_t* state_out, uint64_t* info) {
+  if (!ht_pos_shape(field, create_flags, rate, alpha, rf, rp, ark, mds) || !state_in || !state_out) return -1;
+  return POLY_FIELD(t_pos_permute, create_flags, rate, alpha, rf, rp, ark, mds, sparse, state_in, state_out, info);
+}
+}
+
 // ---- transforms of vectors of points (group_fft.hpp) with the limb-bound checker armed ------------------------------------------
 // The SAME MSM_HD functions the kernels of kernels_gfft.hip wrap: the index maps, the twiddle exponent, the twiddle and the factor as
 // canonical words, the table of a butterfly's B, the walk and the butterfly; records by fb_host_records, the vector between two

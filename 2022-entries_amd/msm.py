@@ -163,6 +163,12 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_sparse_apply": [vp, vp, vp, ctypes.c_uint, vp],
         "mi355_msm_sparse_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_sparse_destroy": [vp],
+        "mi355_msm_poseidon_create": [ctypes.POINTER(vp), vp, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, vp, vp, ctypes.c_uint],
+        "mi355_msm_poseidon_hash": [vp, vp, vp, sz, sz, sz, vp, ctypes.c_uint, vp],
+        "mi355_msm_poseidon_merkle": [vp, vp, vp, sz, sz, vp, ctypes.c_uint, vp],
+        "mi355_msm_poseidon_set_option": [vp, ctypes.c_char_p, ctypes.c_long],
+        "mi355_msm_poseidon_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_poseidon_destroy": [vp],
         "mi355_msm_domain_mle_fix": [vp, vp, vp, ctypes.c_uint, vp, ctypes.c_uint, ctypes.c_uint, vp],
         "mi355_msm_domain_mle_eq": [vp, vp, vp, ctypes.c_uint, ctypes.c_uint, vp],
         "mi355_msm_domain_sumcheck_round": [vp, vp, vp, sz, ctypes.c_uint, vp, sz, vp, vp, ctypes.c_uint, vp],
@@ -1777,6 +1783,292 @@ class SparseMatrix:
             self.close()
         except Exception:
             pass
+
+
+# ---- Poseidon sponges and Merkle trees over Fr (mi355_msm_poseidon_*) ------------------------------------------------------------------
+
+SNARKVM_POSEIDON = {"alpha": 17, "full_rounds": 8, "partial_rounds": 31, "skip_matrices": 0}   # BLS12-377, every rate 2 .. 8
+
+
+class _Grain:
+    """The 80-bit Grain LFSR of the Poseidon paper in self-shrinking mode, as a shift register in one integer (bit 79 is b0)."""
+
+    TAPS = (0, 13, 23, 38, 51, 62)
+
+    def __init__(self, field_bits, t, full_rounds, partial_rounds):
+        state = 0
+        # b0 b1 = 01: a prime field; b2 .. b5 = 0000: x^alpha; then n in 12 bits, t in 12, R_F in 10, R_P in 10, and thirty ones
+        for value, width in ((1, 2), (0, 4), (field_bits, 12), (t, 12), (full_rounds, 10), (partial_rounds, 10), ((1 << 30) - 1, 30)):
+            if value >> width:
+                raise ValueError("a parameter does not fit the generator's seed")
+            state = (state << width) | value
+        self.state, self.bits = state, field_bits
+        for _ in range(160):
+            self._next()
+
+    def _next(self):
+        b = 0
+        for k in self.TAPS:
+            b ^= (self.state >> (79 - k)) & 1
+        self.state = ((self.state << 1) & ((1 << 80) - 1)) | b
+        return b
+
+    def integer(self):
+        """field_bits bits, the first the most significant: pairs of bits, the second of which counts when the first is 1"""
+        v = 0
+        for _ in range(self.bits):
+            while True:
+                first, second = self._next(), self._next()
+                if first:
+                    break
+            v = (v << 1) | second
+        return v
+
+
+def poseidon_parameters(curve, rate: int, alpha: int, full_rounds: int, partial_rounds: int, skip_matrices: int = 0):
+    """Round constants and MDS matrix of a Poseidon instance over the scalar field of ``curve``, by the rule of snarkVM's
+    ``find_poseidon_ark_and_mds``: ``(full_rounds + partial_rounds)`` rows of ``rate + 1`` constants by rejection sampling from the
+    Grain LFSR, ``skip_matrices`` discarded matrices, then ``xs`` and ``ys`` reduced mod p and ``mds[i][j] = 1 / (xs[i] + ys[j])``.
+    Returns ``(ark, mds)`` as lists of rows of integers.  ``alpha`` does not enter the generator (only its sign does)."""
+    p = FR_MODULUS[_curve_id(curve) & 1]
+    t = int(rate) + 1
+    if not 1 <= rate <= 8:
+        raise ValueError("rate: 1 .. 8")
+    if alpha < 3 or not alpha & 1:
+        raise ValueError("alpha: odd, at least 3")
+    g = _Grain(p.bit_length(), t, int(full_rounds), int(partial_rounds))
+    ark = []
+    for _ in range(full_rounds + partial_rounds):
+        row = []
+        while len(row) < t:
+            v = g.integer()
+            if v < p:
+                row.append(v)
+        ark.append(row)
+    for _ in range(2 * t * skip_matrices):
+        g.integer()
+    xs = [g.integer() % p for _ in range(t)]
+    ys = [g.integer() % p for _ in range(t)]
+    if any((x + y) % p == 0 for x in xs for y in ys):
+        raise ValueError("this matrix does not exist (x + y = 0): skip it")
+    return ark, [[pow(x + y, -1, p) for y in ys] for x in xs]
+
+
+def _rows_of(inputs, in_len, what):
+    """(buffer, n, in_len) of a batch of rows: shape (n, in_len, 32), (in_len, 32) for one row, or flat bytes with in_len given"""
+    shape = getattr(inputs, "shape", None)
+    b = _Buf(inputs)
+    if b.nbytes % 32:
+        raise ValueError(f"{what}: 32-byte elements")
+    if shape is not None and len(shape) == 3 and shape[2] == 32:
+        n, ln = int(shape[0]), int(shape[1])
+    elif shape is not None and len(shape) == 2 and shape[1] == 32 and in_len is None:
+        n, ln = 1, int(shape[0])
+    else:
+        total = b.nbytes // 32
+        ln = total if in_len is None else int(in_len)
+        if ln < 0 or (ln == 0 and total) or (ln and total % ln):
+            raise ValueError(f"{what}: {total} elements are no whole number of rows of {ln}")
+        n = total // ln if ln else 1
+    if in_len is not None and ln != int(in_len):
+        raise ValueError(f"{what}: rows of {ln} elements, not in_len = {in_len}")
+    return b, n, ln
+
+
+class Poseidon:
+    """Poseidon over ``Fr`` on one GPU (mi355_msm_poseidon_*): snarkVM's ``PoseidonSponge``, ``Poseidon::hash_many`` / ``hash`` and its
+    Poseidon Merkle tree, for batches.  ``parameters``: ``None`` for snarkVM's instance on BLS12-377 (alpha 17, 8 full and 31 partial
+    rounds), or a dict with ``alpha``, ``full_rounds``, ``partial_rounds`` and either ``ark`` and ``mds`` (rows of integers) or
+    ``skip_matrices`` for ``poseidon_parameters``.  ``domain``: the domain separator of ``hash_many``, ``hash`` and ``merkle_tree``, a
+    string read as snarkVM's ``from_bytes_le_mod_order`` or an integer.  Inputs are batches of rows of 32-byte elements -- a NumPy
+    array or torch tensor of shape ``(n, in_len, 32)``, or bytes with ``in_len=`` -- ``montgomery`` selects arkworks images (default) or
+    plain integers; a torch GPU tensor is read in place on its current stream and gives a GPU tensor (``out=``: one to write into)."""
+
+    def __init__(self, dom, rate: int, parameters=None, domain=None):
+        self.handle = ctypes.c_void_p()
+        self.dom = dom
+        if not dom.handle:
+            raise MsmError(-1, "the domain is closed")
+        self._lib = dom._lib
+        if parameters is None:
+            if dom.curve & 1:
+                raise ValueError("parameters=None is snarkVM's instance over BLS12-377; the reference fixes none for BLS12-381: pass parameters")
+            parameters = dict(SNARKVM_POSEIDON)
+        par = dict(parameters)
+        alpha, rf, rp = int(par["alpha"]), int(par["full_rounds"]), int(par["partial_rounds"])
+        if "ark" in par or "mds" in par:
+            ark, mds = par["ark"], par["mds"]
+        else:
+            ark, mds = poseidon_parameters(dom.curve, rate, alpha, rf, rp, int(par.get("skip_matrices", 0)))
+        t = int(rate) + 1
+        if len(ark) != rf + rp or any(len(r) != t for r in ark) or len(mds) != t or any(len(r) != t for r in mds):
+            raise ValueError(f"ark: {rf + rp} rows of {t} integers, mds: {t} rows of {t}")
+        p = dom.modulus
+        ab = b"".join((int(v) % p).to_bytes(32, "little") for r in ark for v in r)
+        mb = b"".join((int(v) % p).to_bytes(32, "little") for r in mds for v in r)
+        _check(self._lib.mi355_msm_poseidon_create(ctypes.byref(self.handle), dom.handle, int(rate), alpha, rf, rp, ab, mb, 1))
+        self.rate, self.alpha, self.full_rounds, self.partial_rounds = int(rate), alpha, rf, rp
+        if isinstance(domain, str):
+            domain = int.from_bytes(domain.encode(), "little")
+        self.domain = None if domain is None else int(domain) % p
+
+    def _element(self, value, montgomery):
+        p = self.dom.modulus
+        return ((value << 256) % p if montgomery else value % p).to_bytes(32, "little")
+
+    def _header(self, length, montgomery):
+        if self.domain is None:
+            raise ValueError("hash_many, hash and merkle_tree need the domain separator: Poseidon(.., domain=...)")
+        if self.rate < 2:
+            raise ValueError("the header [domain, length, 0 ..] needs a rate of at least 2")
+        return b"".join(self._element(v, montgomery) for v in [self.domain, length] + [0] * (self.rate - 2))
+
+    def _run(self, inputs, n_out, in_len, montgomery, out, header):
+        if not self.handle:
+            raise MsmError(-1, "the Poseidon handle is closed")
+        b, n, ln = _rows_of(inputs, in_len, "inputs")
+        n_out = int(n_out)
+        if n_out < 0:
+            raise ValueError("n_out must not be negative")
+        hdr = header(ln) if header else None
+        flags = 0 if montgomery else 1
+        if b.is_device:
+            import torch
+
+            if b.device_index != self.dom.device:
+                raise MsmError(-1, f"the input lives on cuda:{b.device_index} but this handle is bound to device {self.dom.device}")
+            if out is None:
+                out = torch.empty((n, n_out, 32), dtype=torch.uint8, device=b.keep.device)
+            ob = _Buf(out)
+            if not ob.is_device or ob.keep is not out or ob.nbytes != n * n_out * 32:
+                raise ValueError(f"out: a contiguous uint8 GPU tensor of {n} x {n_out} 32-byte elements")
+            _check(self._lib.mi355_msm_poseidon_hash(self.handle, ob.ptr if ob.nbytes else None, b.ptr if b.nbytes else None, n, ln, n_out, hdr,
+                                                     flags | 2, b.stream))
+            return out
+        if out is not None:
+            raise ValueError("out= goes with GPU tensors")
+        import numpy as np
+
+        res = np.zeros((n, n_out, 32), dtype=np.uint8)
+        _check(self._lib.mi355_msm_poseidon_hash(self.handle, res.ctypes.data if res.size else None, b.ptr if b.nbytes else None, n, ln, n_out, hdr,
+                                                 flags, None))
+        return res
+
+    def sponge(self, inputs, n_out: int, in_len=None, montgomery: bool = True, out=None):
+        """The raw ``PoseidonSponge``: absorb each row, squeeze ``n_out`` elements; the result has shape ``(n, n_out, 32)``."""
+        return self._run(inputs, n_out, in_len, montgomery, out, None)
+
+    def hash_many(self, inputs, n_out: int, in_len=None, montgomery: bool = True, out=None):
+        """``Poseidon::hash_many`` of each row: the preimage is ``[domain, in_len, 0 ..] || row``; shape ``(n, n_out, 32)``."""
+        return self._run(inputs, n_out, in_len, montgomery, out, lambda ln: self._header(ln, montgomery))
+
+    def hash(self, inputs, in_len=None, montgomery: bool = True, out=None):
+        """``Poseidon::hash`` of each row: ``hash_many(row, 1)[0]``; shape ``(n, 32)``"""
+        res = self.hash_many(inputs, 1, in_len=in_len, montgomery=montgomery, out=out)
+        return res.reshape(res.shape[0], 32)
+
+    def merkle_tree(self, leaves, leaf_len=None, montgomery: bool = True, out=None) -> "PoseidonMerkleTree":
+        """snarkVM's Poseidon Merkle tree over ``leaves`` -- shape ``(n_leaves, leaf_len, 32)`` -- as a ``PoseidonMerkleTree``: ``nodes`` are
+        the ``2P - 1`` nodes in the reference's order (root of the built part first, leaf hashes from ``P - 1``)."""
+        if not self.handle:
+            raise MsmError(-1, "the Poseidon handle is closed")
+        b, n, ln = _rows_of(leaves, leaf_len, "leaves")
+        if n < 1:
+            raise ValueError("a tree has at least one leaf")
+        self._header(3, montgomery)
+        P = 1 << (n - 1).bit_length()
+        sep = self._element(self.domain, montgomery)
+        flags = 0 if montgomery else 1
+        if b.is_device:
+            import torch
+
+            if b.device_index != self.dom.device:
+                raise MsmError(-1, f"the leaves live on cuda:{b.device_index} but this handle is bound to device {self.dom.device}")
+            if out is None:
+                out = torch.empty((2 * P - 1, 32), dtype=torch.uint8, device=b.keep.device)
+            ob = _Buf(out)
+            if not ob.is_device or ob.keep is not out or ob.nbytes != (2 * P - 1) * 32:
+                raise ValueError(f"out: a contiguous uint8 GPU tensor of shape ({2 * P - 1}, 32)")
+            _check(self._lib.mi355_msm_poseidon_merkle(self.handle, ob.ptr, b.ptr if b.nbytes else None, n, ln, sep, flags | 2, b.stream))
+            return PoseidonMerkleTree(self, out, n, montgomery)
+        if out is not None:
+            raise ValueError("out= goes with GPU tensors")
+        import numpy as np
+
+        res = np.zeros((2 * P - 1, 32), dtype=np.uint8)
+        _check(self._lib.mi355_msm_poseidon_merkle(self.handle, res.ctypes.data, b.ptr if b.nbytes else None, n, ln, sep, flags, None))
+        return PoseidonMerkleTree(self, res, n, montgomery)
+
+    def set_option(self, key: str, value: int) -> None:
+        """ "sparse": 1 (default) or 0, the partial rounds run densely from ark and mds (a test hook; the results are identical)"""
+        _check(self._lib.mi355_msm_poseidon_set_option(self.handle, key.encode(), int(value)))
+
+    def query(self, key: str) -> int:
+        """ "rate", "state", "rounds", "sparse", "products_per_permutation", "lds_bytes", "work_bytes", "block_lanes" """
+        v = ctypes.c_uint64(0)
+        _check(self._lib.mi355_msm_poseidon_query(self.handle, key.encode(), ctypes.byref(v)))
+        return int(v.value)
+
+    def close(self) -> None:
+        if self.handle:
+            _check(self._lib.mi355_msm_poseidon_destroy(self.handle))
+            self.handle = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PoseidonMerkleTree:
+    """The result of ``Poseidon.merkle_tree``: ``nodes`` (NumPy or GPU tensor, shape ``(2P - 1, 32)``), ``number_of_leaves``,
+    ``root(depth)`` and ``path(i)`` as snarkVM's ``MerkleTree::root`` and ``prove`` give them."""
+
+    def __init__(self, hasher, nodes, number_of_leaves, montgomery):
+        self.hasher, self.nodes, self.number_of_leaves, self.montgomery = hasher, nodes, int(number_of_leaves), montgomery
+        self.leaf_count = (int(nodes.shape[0]) + 1) // 2
+        self.levels = self.leaf_count.bit_length() - 1
+
+    def _node(self, i) -> bytes:
+        row = self.nodes[i]
+        return bytes(row.cpu().numpy().tobytes() if hasattr(row, "cpu") else row.tobytes())
+
+    def empty_hash(self) -> bytes:
+        """``hash_children(0, 0)``: a padding leaf of this tree when it has one, else one hash"""
+        if self.number_of_leaves < self.leaf_count:
+            return self._node(self.leaf_count - 1 + self.number_of_leaves)
+        one = self.hasher._element(1, self.montgomery)
+        return self.hasher.hash(one + bytes(64), in_len=3, montgomery=self.montgomery).tobytes()
+
+    def root(self, depth=None) -> bytes:
+        """The root of a tree of ``depth`` levels: the root of the built part hashed ``depth - levels`` times with the empty hash on its
+        right (a handful of single hashes); ``depth=None`` is the built part's own root."""
+        root = self._node(0)
+        if depth is None or depth == self.levels:
+            return root
+        if depth < self.levels:
+            raise ValueError(f"{self.number_of_leaves} leaves need a depth of at least {self.levels}")
+        one, empty = self.hasher._element(1, self.montgomery), self.empty_hash()
+        for _ in range(depth - self.levels):
+            root = self.hasher.hash(one + root + empty, in_len=3, montgomery=self.montgomery).tobytes()
+        return root
+
+    def path(self, i: int):
+        """The sibling hashes from leaf ``i`` up to below the root of the built part, as a list of 32-byte elements"""
+        if not 0 <= i < self.number_of_leaves:
+            raise ValueError("the leaf index is out of bounds")
+        idx, out = self.leaf_count - 1 + int(i), []
+        while idx:
+            out.append(self._node(idx + 1 if idx & 1 else idx - 1))
+            idx = (idx - 1) // 2
+        return out
 
 
 class FixedBase:

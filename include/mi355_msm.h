@@ -725,6 +725,63 @@ RustError mi355_msm_domain_sumcheck_round(mi355_msm_domain* d, void* evals_out, 
                                           const mi355_msm_sumcheck_term* terms, size_t n_terms, const void* r_prev, void* const* folded,
                                           unsigned flags, void* stream);
 
+/* ---- Poseidon sponges and Merkle trees over Fr (snarkVM's PoseidonSponge, Poseidon::hash_many and its Poseidon Merkle tree) -----------
+ * An algebraic hash on the device: batches of independent duplex sponges of one shape, and the Merkle tree built from them.  The
+ * parameters belong to a system, so like a sparse matrix they are uploaded once and kept.  The state is [capacity | rate] with capacity
+ * 1, t = rate + 1 elements; an absorbed element is ADDED to a rate cell; a round is ark, S-box x^alpha, mds; the rounds
+ * full_rounds / 2 .. full_rounds / 2 + partial_rounds - 1 are partial, their S-box acts on element 0 alone
+ * (console/algorithms/src/poseidon/helpers/sponge.rs).  Elements are 32 bytes: arkworks Fr images or, with flag bit 0, plain integers;
+ * ANY 256-bit input is read as its residue and every output is canonical.
+ *   create  1 <= rate <= 8; 3 <= alpha < 2^16, odd; full_rounds even, 2 .. 4096; partial_rounds 0 .. 4096.  ark holds
+ *           (full_rounds + partial_rounds) * t HOST elements, round by round, mds t * t, row by row; flag bit 0 (the only flag): plain
+ *           integers.  The caller always supplies the parameters: nothing about alpha = 17 or 8 + 31 rounds is in a kernel.  The field,
+ *           the device, the stream of host-pointer calls and the host arithmetic are those of the domain d, WHICH MUST OUTLIVE THE
+ *           HANDLE; nothing here has to do with the domain's size.  create derives the sparse form of the partial rounds (below) in host
+ *           arithmetic and refuses, with a message that names the round, parameters for which it does not exist.
+ *   hash    n <= 2^30 independent sponges: row i of `in` holds in_len <= 2^16 elements, row i of `out` receives n_out <= 2^16 squeezed
+ *           elements.  `header`, if not NULL, is `rate` HOST elements in the form of the call (also with bit 1), absorbed before every
+ *           row: with header = [domain, in_len, 0, ..] the call is Poseidon::hash_many, without it the raw sponge, absorb then squeeze.
+ *           The duplex rules are the reference's: permute before absorbing into a full rate block, once before the first squeeze (an
+ *           empty input still permutes once), and again when a squeeze passes `rate` outputs; n_out == 0 or n == 0 writes nothing.
+ *   merkle  the Poseidon Merkle tree of console/collections/src/merkle_tree: leaf hash hash([0] || leaf), node hash
+ *           hash([1, left, right]), empty hash hash([1, 0, 0]), hash(x) = hash_many(x, 1)[0] with the HOST element domain_sep as the
+ *           domain.  1 <= n_leaves <= 2^30 leaves of leaf_len < 2^16 elements each; the rate must be at least 2.  tree_out receives the
+ *           2P - 1 nodes, P = next_power_of_two(n_leaves), in the reference's order: the root of the built part at index 0, the
+ *           children of node i at 2i + 1 and 2i + 2, the leaf hashes from P - 1 on, missing leaves holding the empty hash.  One launch
+ *           of the hash kernel per level on one stream; levels are not fused.  The padding of root(depth) above the built part is a
+ *           handful of node hashes and is left to the caller (hash with in_len 3).
+ *   Flag bit 1 (value 2), hash and merkle: the vectors are DEVICE pointers (4-byte aligned) and `stream` is the hipStream_t on which
+ *           the input becomes ready (NULL = the default stream): the work is enqueued there and the call returns when the output is
+ *           written, as the device-pointer calls of the domain do.  Without bit 1 they are host pointers, staged through buffers the
+ *           handle keeps, and a non-null stream is an error.  Any overlap of output and input is refused.
+ *   set_option  "sparse": 1 (default), or 0 to run the partial rounds densely from the caller's ark and mds -- a test hook and the A/B of
+ *           the measurement; the results are identical.
+ *   query   "rate", "state" (t), "rounds", "sparse", "products_per_permutation" (Fr products of one permutation in the current form,
+ *           the reductions below included), "lds_bytes" (per block), "work_bytes" (everything the handle holds on the device);
+ *           "block_lanes", a constant of the kernel, is answered without a handle too.
+ * One call each with a flag bit, and no twin whose name ends in _device: this is the route mi355_msm_sparse_apply took, for the reason
+ * given there; the stream-ordering promise of flag bit 1 is pinned by late-producer tests in tests/test_gpu_poseidon.py.
+ * Scheme (csrc/poseidon.hpp).  One lane per sponge; the state lives in LDS, lane-interleaved, and every loop is rolled, so one kernel
+ * per field serves every rate; constants and matrices are indexed by the round counter and read on the scalar unit.  The linear layer N
+ * of a partial round factors as N'' N' with N' = [[1, 0], [0, N^]] commuting with the partial S-box: N' moves backward into the round
+ * constants and the previous layer, and a partial round costs the S-box and 2t - 1 products instead of t^2 (502 / 834 / 1690 products
+ * per permutation at rate 2 / 4 / 8 with alpha 17 and 8 + 31 rounds, against 626 / 1330 / 3674).  Elements that skip a product grow
+ * lazily; where a bound of csrc/fr.hpp would be passed (BLS12-381 only: 2^261 / r = 70.6) create schedules a product by 1, counted in
+ * "products_per_permutation".  Results never depend on "sparse", on host versus device pointers or on the form of the call.  There is
+ * no CPU fallback.
+ * Errors: -1 with a message, decided before any device call, in this order: unknown flag bits, sizes outside their limits, null
+ * pointers, alignment, a stream without flag bit 1, an output that overlaps the input, and last the null handle (create: the domain). */
+typedef struct mi355_msm_poseidon mi355_msm_poseidon;
+RustError mi355_msm_poseidon_create(mi355_msm_poseidon** out, mi355_msm_domain* d, unsigned rate, unsigned alpha, unsigned full_rounds,
+                                    unsigned partial_rounds, const void* ark, const void* mds, unsigned flags);
+RustError mi355_msm_poseidon_hash(mi355_msm_poseidon* p, void* out, const void* in, size_t n, size_t in_len, size_t n_out,
+                                  const void* header, unsigned flags, void* stream);
+RustError mi355_msm_poseidon_merkle(mi355_msm_poseidon* p, void* tree_out, const void* leaves, size_t n_leaves, size_t leaf_len,
+                                    const void* domain_sep, unsigned flags, void* stream);
+RustError mi355_msm_poseidon_set_option(mi355_msm_poseidon* p, const char* key, long value);
+RustError mi355_msm_poseidon_query(mi355_msm_poseidon* p, const char* key, uint64_t* value);
+RustError mi355_msm_poseidon_destroy(mi355_msm_poseidon* p);
+
 /* ---- transforms of vectors of curve points over a domain (ARK poly/src/domain/mod.rs:99-170 on DomainCoeff = G1Projective / G2Projective) ----
  * domain.fft / ifft / coset_fft / coset_ifft on GROUP elements: what turns a monomial SRS [tau^j] G into the Lagrange SRS
  * [L_i(tau)] G (kind 1), and the transform behind FK20, cq and Caulk tables.  With in[j] a point and the products scalar multiples:

@@ -457,6 +457,55 @@ inline std::vector<BigInteger256> groth16_witness_map(const Radix2EvaluationDoma
   return dom.coset_ifft(dom.divide_by_vanishing_poly_on_coset(h));
 }
 
+// snarkVM's PoseidonSponge, Poseidon::hash_many and its Poseidon Merkle tree for batches on the GPU (mi355_msm_poseidon_*): the caller
+// supplies the round constants (one row of rate + 1 per round) and the MDS matrix as Fr values in Montgomery form, uploaded once on a
+// domain that outlives them.
+struct Poseidon {
+  mi355_msm_poseidon* handle = nullptr;
+  unsigned rate;
+  Poseidon(const Radix2EvaluationDomain& dom, unsigned rate_, unsigned alpha, unsigned full_rounds, unsigned partial_rounds,
+           const std::vector<BigInteger256>& ark, const std::vector<BigInteger256>& mds)
+      : rate(rate_) {
+    if (ark.size() != (size_t)(full_rounds + partial_rounds) * (rate + 1) || mds.size() != (size_t)(rate + 1) * (rate + 1))
+      throw std::invalid_argument("ark: one row of rate + 1 constants per round; mds: rate + 1 rows of rate + 1");
+    check(mi355_msm_poseidon_create(&handle, dom.handle, rate, alpha, full_rounds, partial_rounds, ark.data(), mds.data(), 0));
+  }
+  Poseidon(const Poseidon&) = delete;
+  Poseidon& operator=(const Poseidon&) = delete;
+  Poseidon(Poseidon&& o) noexcept : handle(o.handle), rate(o.rate) { o.handle = nullptr; }
+  uint64_t query(const char* key) const {
+    uint64_t v = 0;
+    check(mi355_msm_poseidon_query(handle, key, &v));
+    return v;
+  }
+  // n = in.size() / in_len sponges: absorb the header (empty, or `rate` elements) and a row, squeeze n_out elements
+  std::vector<BigInteger256> hash(const std::vector<BigInteger256>& in, size_t in_len, size_t n_out,
+                                  const std::vector<BigInteger256>& header = {}) const {
+    if (!header.empty() && header.size() != rate) throw std::invalid_argument("a header holds `rate` elements");
+    const size_t n = in_len ? in.size() / in_len : 1;
+    if (n * in_len != in.size()) throw std::invalid_argument("whole rows of in_len elements");
+    std::vector<BigInteger256> out(n * n_out);
+    check(mi355_msm_poseidon_hash(handle, out.data(), in.data(), n, in_len, n_out, header.empty() ? nullptr : header.data(), 0, nullptr));
+    return out;
+  }
+  // the 2P - 1 nodes of the Poseidon Merkle tree under the domain separator, root of the built part first
+  std::vector<BigInteger256> merkle_tree(const BigInteger256& domain_sep, const std::vector<BigInteger256>& leaves, size_t leaf_len) const {
+    if (!leaf_len || leaves.empty() || leaves.size() % leaf_len) throw std::invalid_argument("whole leaves of leaf_len elements");
+    const size_t n = leaves.size() / leaf_len;
+    size_t P = 1;
+    while (P < n) P *= 2;
+    std::vector<BigInteger256> out(2 * P - 1);
+    check(mi355_msm_poseidon_merkle(handle, out.data(), leaves.data(), n, leaf_len, &domain_sep, 0, nullptr));
+    return out;
+  }
+  ~Poseidon() {
+    if (handle) {
+      RustError e = mi355_msm_poseidon_destroy(handle);
+      if (e.message) std::free(e.message);
+    }
+  }
+};
+
 // ark-poly's DenseMultilinearExtension and the prover of ark-linear-sumcheck's ListOfProductsOfPolynomials on host vectors
 // (mi355_msm_domain_mle_fix, _mle_eq, _sumcheck_round): a table holds 2^nv evaluations, index b the point (b_0, .., b_{nv-1}) with b_0 the
 // lowest bit, and variables are fixed from the lowest bit upward.  The domain lends its field and its device; its size plays no part.

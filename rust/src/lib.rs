@@ -258,6 +258,20 @@ pub mod sys {
         pub fn mi355_msm_sparse_apply(m: *mut c_void, out: *mut c_void, z: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
         pub fn mi355_msm_sparse_query(m: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
         pub fn mi355_msm_sparse_destroy(m: *mut c_void) -> Error;
+        // Poseidon parameters over Fr on a domain handle, which must outlive them: `ark` holds (full + partial rounds) * (rate + 1)
+        // host elements, `mds` (rate + 1)^2 (flags bit 0: plain integers).  hash: n sponges, row i of `input` holds in_len elements, row
+        // i of `out` receives n_out; `header` is null or `rate` host elements absorbed before every row.  merkle: snarkVM's Poseidon
+        // Merkle tree, 2P - 1 nodes.  Call flags bit 0: plain integers, bit 1 (value 2): device pointers and `stream` is where the
+        // input becomes ready, else host pointers and a null stream
+        pub fn mi355_msm_poseidon_create(out: *mut *mut c_void, d: *mut c_void, rate: c_uint, alpha: c_uint, full_rounds: c_uint, partial_rounds: c_uint,
+                                         ark: *const c_void, mds: *const c_void, flags: c_uint) -> Error;
+        pub fn mi355_msm_poseidon_hash(p: *mut c_void, out: *mut c_void, input: *const c_void, n: usize, in_len: usize, n_out: usize,
+                                       header: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_poseidon_merkle(p: *mut c_void, tree_out: *mut c_void, leaves: *const c_void, n_leaves: usize, leaf_len: usize,
+                                         domain_sep: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_poseidon_set_option(p: *mut c_void, key: *const c_char, value: c_long) -> Error;
+        pub fn mi355_msm_poseidon_query(p: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
+        pub fn mi355_msm_poseidon_destroy(p: *mut c_void) -> Error;
         // dense multilinear extensions and sumcheck prover rounds on a domain handle (ark-poly's DenseMultilinearExtension, the prover of
         // ark-linear-sumcheck): flags bit 0: plain integers, bit 1 (value 2): the vectors are device pointers and `stream` is where they
         // become ready, else host pointers and a null stream; points, challenges, coefficients and round results are host elements
@@ -715,6 +729,84 @@ pub mod sparse {
             let mut out = vec![Fr::zero(); self.rows];
             check(unsafe {
                 sys::mi355_msm_sparse_apply(self.handle, out.as_mut_ptr() as *mut c_void, z.as_ptr() as *const c_void, 0, std::ptr::null_mut())
+            });
+            out
+        }
+    }
+}
+
+/// snarkVM's `PoseidonSponge`, `Poseidon::hash_many` and its Poseidon Merkle tree for batches on the GPU (`mi355_msm_poseidon_*`): the
+/// caller supplies the round constants and the MDS matrix, which are uploaded once.
+pub mod poseidon {
+    use super::sys;
+    use super::Fr;
+    use ark_std::Zero;
+    use std::os::raw::c_void;
+
+    fn check(err: super::Error) {
+        if err.code != 0 {
+            panic!("{}", String::from(err));
+        }
+    }
+
+    /// Lives on a domain handle of `sys::mi355_msm_domain_create`, which the caller keeps alive for as long as the parameters.
+    pub struct Poseidon {
+        handle: *mut c_void,
+        pub rate: usize,
+    }
+
+    impl Drop for Poseidon {
+        fn drop(&mut self) {
+            if !self.handle.is_null() {
+                let _ = unsafe { sys::mi355_msm_poseidon_destroy(self.handle) };
+            }
+        }
+    }
+
+    impl Poseidon {
+        /// # Safety
+        /// `domain` is a live handle of `sys::mi355_msm_domain_create` over the field of `Fr` and outlives the parameters.
+        pub unsafe fn new(domain: *mut c_void, rate: usize, alpha: u32, full_rounds: u32, partial_rounds: u32, ark: &[Vec<Fr>], mds: &[Vec<Fr>]) -> Self {
+            let a: Vec<Fr> = ark.iter().flatten().copied().collect();
+            let m: Vec<Fr> = mds.iter().flatten().copied().collect();
+            assert_eq!(a.len(), (full_rounds + partial_rounds) as usize * (rate + 1), "ark: one row of rate + 1 constants per round");
+            assert_eq!(m.len(), (rate + 1) * (rate + 1), "mds: rate + 1 rows of rate + 1");
+            let mut handle: *mut c_void = std::ptr::null_mut();
+            check(sys::mi355_msm_poseidon_create(&mut handle, domain, rate as u32, alpha, full_rounds, partial_rounds, a.as_ptr() as *const c_void,
+                                                 m.as_ptr() as *const c_void, 0));
+            Poseidon { handle, rate }
+        }
+
+        /// `n = input.len() / in_len` sponges: absorb `header` (empty, or `rate` elements) and a row, squeeze `n_out` elements
+        pub fn hash(&self, input: &[Fr], in_len: usize, n_out: usize, header: &[Fr]) -> Vec<Fr> {
+            assert!(header.is_empty() || header.len() == self.rate, "a header holds `rate` elements");
+            let n = if in_len == 0 { 1 } else { input.len() / in_len };
+            assert_eq!(n * in_len, input.len(), "whole rows of in_len elements");
+            let mut out = vec![Fr::zero(); n * n_out];
+            let hdr = if header.is_empty() { std::ptr::null() } else { header.as_ptr() as *const c_void };
+            check(unsafe {
+                sys::mi355_msm_poseidon_hash(self.handle, out.as_mut_ptr() as *mut c_void, input.as_ptr() as *const c_void, n, in_len, n_out, hdr, 0,
+                                             std::ptr::null_mut())
+            });
+            out
+        }
+
+        /// `Poseidon::hash_many` of every row under the domain separator `domain`
+        pub fn hash_many(&self, domain: Fr, input: &[Fr], in_len: usize, n_out: usize) -> Vec<Fr> {
+            let mut header = vec![Fr::zero(); self.rate];
+            header[0] = domain;
+            header[1] = Fr::from(in_len as u64);
+            self.hash(input, in_len, n_out, &header)
+        }
+
+        /// the `2P - 1` nodes of snarkVM's Poseidon Merkle tree, root of the built part first
+        pub fn merkle_tree(&self, domain: Fr, leaves: &[Fr], leaf_len: usize) -> Vec<Fr> {
+            assert!(leaf_len > 0 && leaves.len() % leaf_len == 0 && !leaves.is_empty(), "whole leaves of leaf_len elements");
+            let n = leaves.len() / leaf_len;
+            let mut out = vec![Fr::zero(); 2 * n.next_power_of_two() - 1];
+            check(unsafe {
+                sys::mi355_msm_poseidon_merkle(self.handle, out.as_mut_ptr() as *mut c_void, leaves.as_ptr() as *const c_void, n, leaf_len,
+                                               &domain as *const Fr as *const c_void, 0, std::ptr::null_mut())
             });
             out
         }

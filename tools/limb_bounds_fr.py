@@ -22,6 +22,7 @@ All margins must be positive (tests/test_fr_consts.py runs it); the host build c
     python tools/limb_bounds_fr.py --quotient (the rows of the Plonk quotient and the linear combination of csrc/quotient.hpp: analyse_quotient below)
     python tools/limb_bounds_fr.py --sparse   (the lane sums of the sparse matrix-vector product of csrc/sparse.hpp: analyse_sparse below)
     python tools/limb_bounds_fr.py --mle      (the folds, extrapolations, products and sums of csrc/mle.hpp: analyse_mle below)
+    python tools/limb_bounds_fr.py --poseidon (the rounds of csrc/poseidon.hpp with the reductions its schedule sets: analyse_poseidon below)
 """
 import sys
 
@@ -476,8 +477,186 @@ def analyse_mle(name, r, out):
     return ok
 
 
+POSEIDON_SETS = ((17, 8, 31), (5, 6, 11), (3, 2, 120))      # alpha, full and partial rounds: snarkVM's, a short one, a long lazy chain
+
+
+def poseidon_schedule(t, alpha, rf, rp, sparse, K):
+    """pos_schedule of csrc/poseidon.hpp, statement by statement in the same double arithmetic: (reductions per round, products)"""
+    h, rounds = rf // 2, rf + rp
+    sq_limit, lazy_limit, leave = 0.95 * K, 0.9 * K, t * (1 + 2 / K)
+    top = alpha.bit_length() - 1
+    sbox_products = sum(1 + ((alpha >> b) & 1) for b in range(top))
+    b = [leave + 2] * t
+    red, products = [0] * rounds, 0
+    for r in range(rounds):
+        full = r < h or r >= h + rp
+        flags = 0
+        if full or not sparse:
+            nsb = t if full else 1
+            for e in range(nsb):
+                if (b[e] + 1) * (b[e] + 1) >= sq_limit:
+                    flags |= 1
+            total = 0.0
+            for e in range(t):
+                x = b[e] + 1
+                if x >= lazy_limit:
+                    return None
+                if e < nsb:
+                    if flags & 1:
+                        x = 1 + x / K
+                    if x * x >= sq_limit:
+                        return None
+                    x = 1 + 2 * x / K
+                total += 1 + x / K
+            products += nsb * (sbox_products + (flags & 1)) + t * t
+            b = [total] * t
+        else:
+            for e in range(1, t):
+                if b[e] + 3 >= lazy_limit:
+                    flags |= 2
+            x0 = b[0] + 1
+            if x0 >= lazy_limit:
+                return None
+            if x0 * x0 >= sq_limit:
+                flags |= 1
+                x0 = 1 + x0 / K
+            sb = 1 + 2 * x0 / K
+            out0 = 1 + sb / K
+            for e in range(1, t):
+                y = b[e]
+                if flags & 2:
+                    y = 1 + y / K
+                y += 1
+                out0 += 1 + y / K
+                b[e] = y + 1 + sb / K
+                if b[e] >= lazy_limit:
+                    return None
+            b[0] = out0
+            products += sbox_products + (flags & 1) + (2 * t - 1) + ((t - 1) if flags & 2 else 0)
+        red[r] = flags
+    if any(x > leave for x in b):
+        return None
+    return red, products
+
+
+def analyse_poseidon(name, r, out):
+    """The rounds of csrc/poseidon.hpp (python tools/limb_bounds_fr.py --poseidon) for every state width t = 2 .. 9, both forms of the
+    partial rounds and the parameter sets above, carried as pos_permute performs them with the reductions pos_schedule sets -- here in
+    exact integers: a value bound per state element, limbs in the carried form (fr_carry: limbs 0 .. 7 below 2^29 + 8, the top limb
+    holds the rest).  Every product is judged as fr_mul judges it: the first operand below R with limbs below 2^31, the second carried,
+    every column below 2^64, and the result r + a b / R below 2r (class M).  The state enters a permutation below what the last linear
+    layer leaves plus an absorbed class-M element and must leave below that again."""
+    import math
+
+    rl = limbs(r)
+    ok = True
+    K = float(R) / float(r)
+    worst = {}
+    col_memo = {}          # by the two top limbs: the other limbs are the same bounds everywhere
+
+    def margin(what, have, limit):
+        nonlocal ok
+        m = limit - have
+        ok &= m > 0
+        if what not in worst or m < worst[what][0]:
+            worst[what] = (m, have, limit)
+
+    canon = [MASK] * (N - 1) + [rl[N - 1]]
+
+    def lazy_limbs(val):
+        return [MASK + 8] * (N - 1) + [(val >> (B * (N - 1))) + 1]
+
+    def mul(what, a_val, b_val, b_limbs):
+        a = lazy_limbs(a_val)
+        margin(what + ": the first operand against R", a_val, R)
+        margin(what + ": its largest limb against 2^31", max(a), 1 << 31)
+        margin(what + ": the second operand's largest limb against 2^29 + 8", max(b_limbs), (1 << B) + 8)
+        key = (a[N - 1], b_limbs[N - 1])
+        if key not in col_memo:
+            col_memo[key] = max(columns(a, b_limbs, rl))
+        margin(what + ": the largest column against 2^64", col_memo[key], 1 << 64)
+        res = r + a_val * b_val // R + 1
+        margin(what + ": the result r + a b / R against 2r", res, 2 * r)
+        return res
+
+    def add(what, a_val, b_val):
+        # carried + normalised limbs, then one carry pass
+        margin(what + ": limb-wise sum against 2^32", 2 * MASK + 8, 1 << 32)
+        margin(what + ": top limb into the carry pass against 2^31", ((a_val + b_val) >> (B * (N - 1))) + 2, 1 << 31)
+        return a_val + b_val
+
+    def sbox(x, alpha):
+        top = alpha.bit_length() - 1
+        acc = x
+        for b in range(top - 1, -1, -1):
+            acc = mul("the first square of an S-box" if acc is x and b == top - 1 else "a later square of an S-box", acc, acc, lazy_limbs(acc))
+            if (alpha >> b) & 1:
+                acc = mul("x times the running power of an S-box", x, acc, lazy_limbs(acc))
+        return acc
+
+    out.append("%s: r = %.3f * 2^252, R / r = %.2f  (the rounds of poseidon.hpp)" % (name, r / 2**252, K))
+    margin("2r against a packed element (2^256)", 2 * r, 1 << 256)
+    mul("an absorbed element: any 256-bit value times a canonical constant", (1 << 256) - 1, r, canon)
+    for alpha, rf, rp in POSEIDON_SETS:
+        for t in range(2, 10):
+            counts = []
+            for sparse in (False, True):
+                sch = poseidon_schedule(t, alpha, rf, rp, sparse, K)
+                if sch is None:
+                    ok = False
+                    out.append("  t = %d, alpha %d, %d + %d rounds, %s: NO SCHEDULE  BAD" % (t, alpha, rf, rp, "sparse" if sparse else "dense"))
+                    continue
+                red, products = sch
+                counts.append((products, sum(1 for f in red if f)))
+                h = rf // 2
+                leave = int(t * (1 + 2 / K) * r) + 1
+                b = [leave + 2 * r] * t
+                for k in range(rf + rp):
+                    full = k < h or k >= h + rp
+                    if full or not sparse:
+                        nsb = t if full else 1
+                        nb = 0
+                        for e in range(t):
+                            x = add("state + round constant", b[e], r)
+                            if e < nsb:
+                                if red[k] & 1:
+                                    x = mul("an S-box input times 1", x, r, canon)
+                                x = sbox(x, alpha)
+                            nb += mul("a matrix entry times a state element", x, r, canon)
+                        for _ in range(t):
+                            add("the sum of a matrix row", nb, 0)
+                        b = [nb] * t
+                    else:
+                        x = add("state + round constant", b[0], r)
+                        if red[k] & 1:
+                            x = mul("an S-box input times 1", x, r, canon)
+                        sb = sbox(x, alpha)
+                        out0 = mul("N00 times the S-box output", sb, r, canon)
+                        for e in range(1, t):
+                            y = b[e]
+                            if red[k] & 2:
+                                y = mul("an element that skipped the products, times 1", y, r, canon)
+                            y = add("state + round constant", y, r)
+                            out0 = add("the sum out_0", out0, mul("v^_j times a lazy element", y, r, canon))
+                            b[e] = add("out_i = w_i s_0 + s_i", y, mul("w_i times the S-box output", sb, r, canon))
+                        b[0] = out0
+                margin("the state at the end of a permutation against what the next one assumes", max(b), leave + 1)
+                mul("a squeezed element times the conversion constant", max(b) + 2 * r, r, canon)
+            if len(counts) == 2:
+                out.append("  t = %d, alpha %2d, %d + %4d rounds: products per permutation %5d dense (%d rounds with a reduction), %5d sparse (%d)"
+                           % (t, alpha, rf, rp, counts[0][0], counts[0][1], counts[1][0], counts[1][1]))
+    for what, (m, have, limit) in worst.items():
+        out.append("  %-80s %s (worst 2^%.3f, limit 2^%.3f)" % (what, "ok " if m > 0 else "BAD", math.log2(max(have, 1)), math.log2(limit)))
+    return ok
+
+
 def main():
     out = []
+    if "--poseidon" in sys.argv[1:]:
+        ok = all([analyse_poseidon(name, r, out) for name, r in FIELDS.items()])
+        print("\n".join(out))
+        print("all margins positive" if ok else "A MARGIN IS NOT POSITIVE")
+        return 0 if ok else 1
     if "--mle" in sys.argv[1:]:
         ok = all([analyse_mle(name, r, out) for name, r in FIELDS.items()])
         print("\n".join(out))
