@@ -2016,6 +2016,148 @@ int ht_poseidon_permute(int field, unsigned create_flags, unsigned rate, unsigne
 }
 }
 
+// ---- pairings (pairing.hpp): the programs create writes and the three stage bodies, lane by lane, with the limb-bound checker armed -----
+#include "pairing.hpp"
+
+template <class E>
+struct HostPrRun {
+  void miller(const PrRun& p, uint64_t items) { for (uint64_t i = 0; i < items; i++) pr_miller_lane<E>(p, i); }
+  void product(const PrRun& p, uint64_t lanes) { for (uint64_t i = 0; i < lanes; i++) pr_product_lane<E>(p, i); }
+  void final(const PrRun& p, uint64_t groups) { for (uint64_t i = 0; i < groups; i++) pr_final_lane<E>(p, i); }
+};
+
+template <class E>
+static int t_pr_run(uint8_t* out, const uint8_t* g1, size_t g1_stride, const uint8_t* g2, size_t g2_stride, size_t n, size_t group, unsigned flags, int check) {
+  PrGen<E> gm, ga, gf;
+  gm.miller();
+  ga.accumulate();
+  gf.final_exponentiation();
+  if (!gm.check() || !ga.check() || !gf.check()) return -3;
+  Fe2 consts[PR_CONSTS];
+  pr_consts<E>(consts, check || (flags & kPrCanonical));
+  const PrPlan pl = pr_plan(n, group);
+  std::vector<uint32_t> ws(pr_ws_words(pl), 0xa5a5a5a5u), wsf(pr_wsf_words(pl), 0xa5a5a5a5u);
+  std::vector<uint32_t> a((n * g1_stride + 3) / 4), b((n * g2_stride + 3) / 4), o(((n / group) * (check ? 1 : PR_GT_BYTES) + 3) / 4 + 1);
+  memcpy(a.data(), g1, n * g1_stride);
+  memcpy(b.data(), g2, n * g2_stride);
+  PrRun r{};
+  r.miller = gm.ops.data(); r.miller_len = (uint32_t)gm.ops.size();
+  r.accum = ga.ops.data(); r.accum_len = (uint32_t)ga.ops.size();
+  r.fexp = gf.ops.data(); r.fexp_len = (uint32_t)gf.ops.size();
+  r.consts = consts;
+  r.ws = ws.data(); r.pitch = pr_ws_items(pl);
+  r.ws_f = wsf.data(); r.pitch_f = pl.chunk_groups;
+  r.g1 = (const uint8_t*)a.data(); r.g1_stride = g1_stride;
+  r.g2 = (const uint8_t*)b.data(); r.g2_stride = g2_stride;
+  r.group = pl.group; r.run = pl.run; r.parts = pl.parts;
+  r.flags = (flags & kPrCanonical) | (check ? (unsigned)kPrCheck : 0u);
+  HostPrRun<E> run;
+  pr_chain(run, r, pl, (uint8_t*)o.data(), check ? 1 : PR_GT_BYTES);
+  memcpy(out, o.data(), (n / group) * (check ? 1 : PR_GT_BYTES));
+  return 0;
+}
+
+// one tower routine on canonical Gt images: A in PR_F, B in PR_G, the result in PR_ACC
+template <class E>
+static int t_pr_op(int op, uint8_t* out, const uint8_t* a, const uint8_t* b, unsigned top) {
+  using F = typename E::Fld;
+  const Modulus<F> md;
+  PrGen<E> g;
+  const uint16_t A = PR_F, B = PR_G, R = PR_ACC, S = PR_REGION0;
+  switch (op) {
+    case 0: g.f12_mul(R, A, B); break;
+    case 1: g.f12_sqr(R, A); break;
+    case 2: g.f12_inv(R, S, A); break;
+    case 3: g.f12_mul(R, A, B, 0x0b); break;   // 034: w^0, w^1, w^3
+    case 4: g.f12_mul(R, A, B, 0x0d); break;   // 014: w^0, w^2, w^3
+    case 5: g.f12_cyclotomic_sqr(R, A); break;
+    case 6: g.f12_cyclotomic_exp(R, S, A); break;
+    case 7: case 8: case 9: g.f12_frobenius(R, A, op - 6); break;
+    case 10: g.f12_conj(R, A); break;
+    case 11: g.f12_mul(R, A, B, 0x15); break;  // Fp6: the even coefficients
+    case 12: g.f12_sqr(R, A); break;
+    case 13: g.f12_copy(R, A); g.f6_inv(R, R + 2, R + 4, R, R + 2, R + 4); break;
+    default: return -1;
+  }
+  if (!g.check()) return -3;
+  Fe2 consts[PR_CONSTS];
+  pr_consts<E>(consts, true);
+  std::vector<uint32_t> wsv((size_t)PR_SLOTS * PR_FE2_WORDS, 0);
+  const PrWs ws{wsv.data(), 1, 0};
+  auto load = [&](uint16_t base, const uint8_t* img) {
+    for (uint32_t t = 0; t < 12; t++) {
+      const uint32_t e = t >> 1, slot = 2 * (e % 3) + e / 3;
+      uint32_t w[12];
+      memcpy(w, img + 48 * t, 48);
+      Fe x, pp;
+      FpEl<F>::from_plain(x, w, md);
+      if (top) {   // the residue plus 2p: the top of class W
+        fe_reduce<F>(x);
+        fe_set(pp, F::P);
+        fe_add(x, x, pp);
+        fe_add(x, x, pp);
+        fe_normalize(x);
+      }
+      pr_store_fe(ws, base + slot, t & 1, x);
+    }
+  };
+  load(A, a);
+  if (b) load(B, b);
+  pr_exec<E>(ws, g.ops.data(), (uint32_t)g.ops.size(), consts, false, md);
+  for (uint32_t t = 0; t < 12; t++) {
+    const uint32_t e = t >> 1, slot = 2 * (e % 3) + e / 3;
+    Fe x;
+    pr_load_fe(x, ws, R + slot, t & 1);
+    uint32_t w[12];
+    FpEl<F>::to_plain(w, x, md);
+    memcpy(out + 48 * t, w, 48);
+  }
+  return 0;
+}
+
+template <class E>
+static int t_pr_info(uint64_t* v) {
+  PrGen<E> gm, ga, gf;
+  gm.miller();
+  ga.accumulate();
+  gf.final_exponentiation();
+  v[0] = gm.products - ga.products;   // Fp2 products of one Miller loop (the accumulation into the run's product apart)
+  v[1] = gf.products;
+  v[2] = ga.products;
+  v[3] = gm.ops.size();
+  v[4] = gf.ops.size();
+  v[5] = PR_SLOTS;
+  v[6] = PR_LANES;
+  v[7] = PR_MILLER_SLOTS;
+  v[8] = ga.ops.size();
+  v[9] = PR_MAX_ITEMS;
+  return 0;
+}
+
+#define PR_FAMILY(fn, ...) (family == 0 ? fn<Fp2El<Bls12_377_Fq, 5>>(__VA_ARGS__) : fn<Fp2El<Bls12_381_Fq, 1>>(__VA_ARGS__))
+extern "C" {
+// mi355_msm_pairing_run / _check on the host (family 0: BLS12-377, 1: BLS12-381; flags bit 0: canonical images; check: one byte per group);
+// ht_pairing_op: one tower routine on canonical Gt images (top: the operands stored at the top of their class);  ht_pairing_info: the
+// Fp2 products of a Miller loop, a final exponentiation and a product step, the lengths of these two programs, the slots, the lanes of a
+// block, the slots of a Miller lane, the length of the product step and the lanes of a chunk (ten values).
+int ht_pairing_run(int family, uint8_t* out, const uint8_t* g1, size_t g1_stride, const uint8_t* g2, size_t g2_stride, size_t n, size_t group, unsigned flags,
+                   int check) {
+  if ((family != 0 && family != 1) || (flags & ~1u) || group == 0 || n % group || g1_stride < 104 || g2_stride < 200 || (g1_stride & 3) || (g2_stride & 3) ||
+      n > (1u << 16) || (n && (!out || !g1 || !g2)))
+    return -1;
+  if (n == 0) return 0;
+  return PR_FAMILY(t_pr_run, out, g1, g1_stride, g2, g2_stride, n, group, flags, check);
+}
+int ht_pairing_op(int family, int op, uint8_t* out, const uint8_t* a, const uint8_t* b, unsigned top) {
+  if ((family != 0 && family != 1) || !out || !a) return -1;
+  return PR_FAMILY(t_pr_op, op, out, a, b, top);
+}
+int ht_pairing_info(int family, uint64_t* v) {
+  if ((family != 0 && family != 1) || !v) return -1;
+  return PR_FAMILY(t_pr_info, v);
+}
+}
+
 // ---- transforms of vectors of points (group_fft.hpp) with the limb-bound checker armed ------------------------------------------
 // The SAME MSM_HD functions the kernels of kernels_gfft.hip wrap: the index maps, the twiddle exponent, the twiddle and the factor as
 // canonical words, the table of a butterfly's B, the walk and the butterfly; records by fb_host_records, the vector between two

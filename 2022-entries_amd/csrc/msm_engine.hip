@@ -2977,4 +2977,5 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 #include "msm_sparse.hpp"
 #include "msm_mle.hpp"
 #include "msm_poseidon.hpp"
+#include "msm_pairing.hpp"
 #include "msm_gfft.hpp"

@@ -169,6 +169,11 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_poseidon_set_option": [vp, ctypes.c_char_p, ctypes.c_long],
         "mi355_msm_poseidon_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_poseidon_destroy": [vp],
+        "mi355_msm_pairing_create": [ctypes.POINTER(vp), ci, ci],
+        "mi355_msm_pairing_run": [vp, vp, vp, sz, vp, sz, sz, sz, ctypes.c_uint, vp],
+        "mi355_msm_pairing_check": [vp, vp, vp, sz, vp, sz, sz, sz, ctypes.c_uint, vp],
+        "mi355_msm_pairing_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_pairing_destroy": [vp],
         "mi355_msm_domain_mle_fix": [vp, vp, vp, ctypes.c_uint, vp, ctypes.c_uint, ctypes.c_uint, vp],
         "mi355_msm_domain_mle_eq": [vp, vp, vp, ctypes.c_uint, ctypes.c_uint, vp],
         "mi355_msm_domain_sumcheck_round": [vp, vp, vp, sz, ctypes.c_uint, vp, sz, vp, vp, ctypes.c_uint, vp],
@@ -2069,6 +2074,115 @@ class PoseidonMerkleTree:
             out.append(self._node(idx + 1 if idx & 1 else idx - 1))
             idx = (idx - 1) // 2
         return out
+
+
+class Pairing:
+    """Batch pairings and pairing products on one GPU (mi355_msm_pairing_*): arkworks' / snarkVM's ``Bls12::pairing`` and
+    ``product_of_pairings`` for the family of ``curve`` (any of the four names selects it).  ``p`` holds n arkworks ``Affine<G1>`` images
+    (104 bytes each, or ``p_stride``), ``q`` n ``Affine<G2>`` images (200 bytes, or ``q_stride``) -- bytes, a NumPy array or a torch
+    tensor; the points must be of order r or flagged infinity, nothing is tested.  A Gt value is 576 bytes: arkworks' in-memory ``Fq12``
+    (Montgomery), or with ``canonical=True`` its ``CanonicalSerialize``.  Torch GPU tensors are read in place on the current stream and
+    give GPU tensors (``out=``: one to write into)."""
+
+    GT_BYTES = 576
+
+    def __init__(self, curve="bls12_377_g1", device: Optional[int] = None):
+        self.curve = _curve_id(curve)
+        self.handle = ctypes.c_void_p()
+        self._lib = load_library()
+        _check(self._lib.mi355_msm_pairing_create(ctypes.byref(self.handle), self.curve, -1 if device is None else device))
+        self.device = self.query("device")
+
+    def _inputs(self, p, q, p_stride, q_stride):
+        if not self.handle:
+            raise MsmError(-1, "the pairing handle is closed")
+        a, b = _Buf(p), _Buf(q)
+        s1, s2 = int(p_stride or 104), int(q_stride or 200)
+        if s1 <= 0 or s2 <= 0 or a.nbytes % s1 or b.nbytes % s2 or a.nbytes // s1 != b.nbytes // s2:
+            raise ValueError(f"p: n images of {s1} bytes, q: n images of {s2} bytes ({a.nbytes} and {b.nbytes} bytes given)")
+        if a.is_device != b.is_device:
+            raise ValueError("p and q must both be GPU tensors or both live on the host")
+        if a.is_device:
+            for t in (a, b):
+                if t.device_index != self.device:
+                    raise MsmError(-1, f"an input lives on cuda:{t.device_index} but this handle is bound to device {self.device}")
+        return a, b, s1, s2, a.nbytes // s1
+
+    def _call(self, name, p, q, group, unit, flags, out, p_stride, q_stride):
+        a, b, s1, s2, n = self._inputs(p, q, p_stride, q_stride)
+        fn = getattr(self._lib, name)
+        group = int(group)
+        if group < 1 or n % group:
+            raise ValueError(f"{n} pairs are not whole groups of {group}")
+        m = n // group
+        shape = (m, unit) if unit > 1 else (m,)
+        if a.is_device:
+            import torch
+
+            if out is None:
+                out = torch.empty(shape, dtype=torch.uint8, device=a.keep.device)
+            ob = _Buf(out)
+            if not ob.is_device or ob.keep is not out or ob.nbytes != m * unit:
+                raise ValueError(f"out: a contiguous uint8 GPU tensor of {m} x {unit} bytes")
+            _check(fn(self.handle, ob.ptr if n else None, a.ptr if n else None, s1, b.ptr if n else None, s2, n, group, flags | 2, a.stream))
+            return out
+        if out is not None:
+            raise ValueError("out= goes with GPU tensors")
+        import numpy as np
+
+        res = np.zeros(shape, dtype=np.uint8)
+        _check(fn(self.handle, res.ctypes.data if n else None, a.ptr if n else None, s1, b.ptr if n else None, s2, n, group, flags, None))
+        return res
+
+    def pairing(self, p, q, group: int = 1, canonical: bool = False, out=None, p_stride=None, q_stride=None):
+        """``out[j] = prod_{i < group} e(p[j group + i], q[j group + i])``: shape ``(n / group, 576)`` uint8"""
+        return self._call("mi355_msm_pairing_run", p, q, group, self.GT_BYTES, 1 if canonical else 0, out, p_stride, q_stride)
+
+    def product_of_pairings(self, p, q, canonical: bool = False, p_stride=None, q_stride=None):
+        """``product_of_pairings``: the 576 bytes of ``prod_i e(p[i], q[i])`` (the empty product is one)"""
+        n = self._inputs(p, q, p_stride, q_stride)[4]
+        if n == 0:
+            raise ValueError("product_of_pairings needs at least one pair")
+        res = self.pairing(p, q, group=n, canonical=canonical, p_stride=p_stride, q_stride=q_stride)
+        return res.reshape(-1) if hasattr(res, "is_cuda") else res.tobytes()
+
+    def check(self, p, q, group=None, out=None, p_stride=None, q_stride=None):
+        """Whether the product over each group of ``group`` pairs is one: a bool array of n / group entries, or -- ``group=None``, the
+        whole input -- one bool.  No Gt image leaves the device."""
+        n = self._inputs(p, q, p_stride, q_stride)[4]
+        whole = group is None
+        if whole and n == 0:
+            return True
+        res = self._call("mi355_msm_pairing_check", p, q, n if whole else group, 1, 0, out, p_stride, q_stride)
+        if hasattr(res, "is_cuda"):
+            res = res != 0
+            return bool(res[0].item()) if whole else res
+        res = res.astype(bool)
+        return bool(res[0]) if whole else res
+
+    def query(self, key: str) -> int:
+        """ "workspace_bytes", "work_bytes", "last_launches", "products_miller", "products_product_step", "products_final_exponentiation",
+        "program_ops", "device", "curve", "block_lanes", "lane_bytes", "max_lanes", "serial_group" """
+        v = ctypes.c_uint64(0)
+        _check(self._lib.mi355_msm_pairing_query(self.handle, key.encode(), ctypes.byref(v)))
+        return int(v.value)
+
+    def close(self) -> None:
+        if self.handle:
+            _check(self._lib.mi355_msm_pairing_destroy(self.handle))
+            self.handle = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class FixedBase:

@@ -782,6 +782,50 @@ RustError mi355_msm_poseidon_set_option(mi355_msm_poseidon* p, const char* key, 
 RustError mi355_msm_poseidon_query(mi355_msm_poseidon* p, const char* key, uint64_t* value);
 RustError mi355_msm_poseidon_destroy(mi355_msm_poseidon* p);
 
+/* ---- batch pairings and pairing products (arkworks / snarkVM Bls12::pairing and product_of_pairings, BLS12-377 and BLS12-381) ---------
+ * What KZG openings, Groth16 proofs, BLS signatures and an SRS validation end in.  out[j] = prod_{i < group} e(P[j group + i], Q[j group + i]):
+ * group = 1 gives batch pairings, group = n gives product_of_pairings.  The value is byte for byte the reference's
+ * (curves/src/templates/bls12/bls12.rs): f_{|x|,Q}(P), conjugated for BLS12-381's negative x, raised to 3 (p^12 - 1) / r -- eprint 2016/130
+ * Table 1 computes the cube of the reduced Tate power.  A pair whose P or Q is flagged infinity contributes 1; the flag byte is
+ * authoritative.  P and Q must be of order r or flagged infinity: NOTHING is tested (mi355_msm_check_bases exists for that); for other
+ * inputs the value is unspecified but the call is harmless, every loop has a fixed trip count and no access is indexed by data.  If the
+ * Miller value is 0 -- impossible for points of order r; arkworks returns None -- the image is all zero and the check byte is 0.
+ *   create  any of the four curve ids selects its family, as mi355_msm_domain_create does; device < 0: the current one.
+ *   run     g1: n arkworks Affine<G1> images g1_stride bytes apart (at least 104), g2: n Affine<G2> images g2_stride apart (at least
+ *           200), strides a multiple of 4, read exactly as mi355_msm_set_bases reads them.  n must be a multiple of group >= 1.  out
+ *           receives n / group Gt images of 576 bytes: twelve 48-byte Fp elements in arkworks' order c0.c0.c0, c0.c0.c1, c0.c1.c0,
+ *           c0.c1.c1, c0.c2.c0, c0.c2.c1, then the six of c1 (Fp12 = Fp6[w]/(w^2 - v), Fp6 = Fp2[v]/(v^3 - xi)); in-memory Montgomery
+ *           images (R = 2^384, little-endian) like the coordinates of a point image, or with flag bit 0 canonical integers -- that is
+ *           CanonicalSerialize of Fq12.  n == 0 writes nothing.
+ *   check   the same inputs; ok receives one byte per group, 1 exactly when the product is one, and no Gt image leaves the device.
+ *           Flag bit 0 has no meaning here and is refused.
+ *   Flag bit 1 (value 2): every vector is a DEVICE pointer (4-byte aligned; ok needs none) and `stream` is the hipStream_t on which the
+ *           inputs become ready (NULL = the default stream): the work is enqueued there and the call returns when the output is
+ *           written.  Without bit 1 they are host pointers, staged through a buffer the handle keeps, and a non-null stream is an error.
+ *   query   "workspace_bytes" (the two lane-interleaved workspaces), "work_bytes" (everything the handle holds on the device),
+ *           "last_launches", "products_miller", "products_product_step", "products_final_exponentiation" (Fp products a lane
+ *           executes), "program_ops", "device", "curve"; "block_lanes", "lane_bytes", "max_lanes" and "serial_group", constants of the kernels, are answered
+ *           without a handle too.
+ * One call each with a flag bit, and no twin whose name ends in _device: this is the route mi355_msm_sparse_apply and
+ * mi355_msm_poseidon_hash took, for the reason given there; the stream-ordering promise of flag bit 1 is pinned by late-producer tests in
+ * tests/test_gpu_pairing.py.  The handle belongs to one device; a sharded context plays no part.
+ * Scheme (csrc/pairing.hpp).  Nothing above Fp2 is code: create writes the Miller loop, the product step and the final exponentiation
+ * as lists of operations on Fp2 slots, and one rolled interpreter with a single Fp2 product runs them, one lane per pair (or run of
+ * pairs) and per group; tower values live in a lane-interleaved workspace in device memory sized by the lanes in flight, not by n.
+ * Groups of up to "serial_group" pairs are walked by one lane; larger ones are split over lanes and multiplied as a tree of fan-in 8
+ * across lanes and blocks, without atomics and in an order fixed by the indices.  No prepared G2 tables.  There is no CPU fallback.
+ * Errors: -1 with a message, decided before any device call, in this order: unknown flag bits; group == 0 or n not a multiple of
+ * group; a stride too small or not a multiple of 4; null pointers (with n > 0); alignment; a stream without flag bit 1; an output that
+ * overlaps an input; and last the null handle (create: a null out-pointer, then an unknown curve id). */
+typedef struct mi355_msm_pairing mi355_msm_pairing;
+RustError mi355_msm_pairing_create(mi355_msm_pairing** out, int curve, int device);
+RustError mi355_msm_pairing_run(mi355_msm_pairing* h, void* out, const void* g1, size_t g1_stride, const void* g2, size_t g2_stride,
+                                size_t n, size_t group, unsigned flags, void* stream);
+RustError mi355_msm_pairing_check(mi355_msm_pairing* h, uint8_t* ok, const void* g1, size_t g1_stride, const void* g2, size_t g2_stride,
+                                  size_t n, size_t group, unsigned flags, void* stream);
+RustError mi355_msm_pairing_query(mi355_msm_pairing* h, const char* key, uint64_t* value);
+RustError mi355_msm_pairing_destroy(mi355_msm_pairing* h);
+
 /* ---- transforms of vectors of curve points over a domain (ARK poly/src/domain/mod.rs:99-170 on DomainCoeff = G1Projective / G2Projective) ----
  * domain.fft / ifft / coset_fft / coset_ifft on GROUP elements: what turns a monomial SRS [tau^j] G into the Lagrange SRS
  * [L_i(tau)] G (kind 1), and the transform behind FK20, cq and Caulk tables.  With in[j] a point and the products scalar multiples:

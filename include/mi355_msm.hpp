@@ -506,6 +506,49 @@ struct Poseidon {
   }
 };
 
+// Bls12::pairing and product_of_pairings for batches on the GPU (mi355_msm_pairing_*): g1 holds n arkworks Affine<G1> images of 104
+// bytes, g2 n Affine<G2> images of 200; a Gt value is 576 bytes, arkworks' in-memory Fq12 or -- canonical -- its CanonicalSerialize.
+// The points must be of order r or flagged infinity; nothing is tested.
+struct Pairing {
+  mi355_msm_pairing* handle = nullptr;
+  static constexpr size_t GT_BYTES = 576;
+  explicit Pairing(int curve = MI355_BLS12_377_G1, int device = -1) { check(mi355_msm_pairing_create(&handle, curve, device)); }
+  Pairing(const Pairing&) = delete;
+  Pairing& operator=(const Pairing&) = delete;
+  Pairing(Pairing&& o) noexcept : handle(o.handle) { o.handle = nullptr; }
+  uint64_t query(const char* key) const {
+    uint64_t v = 0;
+    check(mi355_msm_pairing_query(handle, key, &v));
+    return v;
+  }
+  // out[j] = prod_{i < group} e(P[j group + i], Q[j group + i]): n / group images
+  std::vector<uint8_t> pairing(const std::vector<uint8_t>& g1, const std::vector<uint8_t>& g2, size_t group = 1, bool canonical = false) const {
+    const size_t n = g1.size() / 104;
+    if (g1.size() % 104 || g2.size() != n * 200 || !group || n % group) throw std::invalid_argument("n images of 104 and of 200 bytes, whole groups");
+    std::vector<uint8_t> out(n / group * GT_BYTES);
+    check(mi355_msm_pairing_run(handle, out.data(), g1.data(), 104, g2.data(), 200, n, group, canonical ? 1u : 0u, nullptr));
+    return out;
+  }
+  std::vector<uint8_t> product_of_pairings(const std::vector<uint8_t>& g1, const std::vector<uint8_t>& g2, bool canonical = false) const {
+    if (g1.empty()) throw std::invalid_argument("at least one pair");
+    return pairing(g1, g2, g1.size() / 104, canonical);
+  }
+  // one byte per group: 1 exactly when the product over the group is one
+  std::vector<uint8_t> check_groups(const std::vector<uint8_t>& g1, const std::vector<uint8_t>& g2, size_t group) const {
+    const size_t n = g1.size() / 104;
+    if (g1.size() % 104 || g2.size() != n * 200 || !group || n % group) throw std::invalid_argument("n images of 104 and of 200 bytes, whole groups");
+    std::vector<uint8_t> ok(n / group);
+    check(mi355_msm_pairing_check(handle, ok.data(), g1.data(), 104, g2.data(), 200, n, group, 0, nullptr));
+    return ok;
+  }
+  ~Pairing() {
+    if (handle) {
+      RustError e = mi355_msm_pairing_destroy(handle);
+      if (e.message) std::free(e.message);
+    }
+  }
+};
+
 // ark-poly's DenseMultilinearExtension and the prover of ark-linear-sumcheck's ListOfProductsOfPolynomials on host vectors
 // (mi355_msm_domain_mle_fix, _mle_eq, _sumcheck_round): a table holds 2^nv evaluations, index b the point (b_0, .., b_{nv-1}) with b_0 the
 // lowest bit, and variables are fixed from the lowest bit upward.  The domain lends its field and its device; its size plays no part.

@@ -272,6 +272,17 @@ pub mod sys {
         pub fn mi355_msm_poseidon_set_option(p: *mut c_void, key: *const c_char, value: c_long) -> Error;
         pub fn mi355_msm_poseidon_query(p: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
         pub fn mi355_msm_poseidon_destroy(p: *mut c_void) -> Error;
+
+        // Batch pairings and pairing products (arkworks' Bls12::pairing / product_of_pairings): out[j] is the product over the j-th group of
+        // `group` consecutive pairs, a 576-byte Fq12 image (flag bit 0: CanonicalSerialize / the canonical integers); check writes one
+        // byte per group, 1 exactly when the product is one.  Flag bit 1: device pointers on `stream`.
+        pub fn mi355_msm_pairing_create(out: *mut *mut c_void, curve: c_int, device: c_int) -> Error;
+        pub fn mi355_msm_pairing_run(h: *mut c_void, out: *mut c_void, g1: *const c_void, g1_stride: usize, g2: *const c_void, g2_stride: usize,
+                                     n: usize, group: usize, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_pairing_check(h: *mut c_void, ok: *mut u8, g1: *const c_void, g1_stride: usize, g2: *const c_void, g2_stride: usize,
+                                       n: usize, group: usize, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_pairing_query(h: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
+        pub fn mi355_msm_pairing_destroy(h: *mut c_void) -> Error;
         // dense multilinear extensions and sumcheck prover rounds on a domain handle (ark-poly's DenseMultilinearExtension, the prover of
         // ark-linear-sumcheck): flags bit 0: plain integers, bit 1 (value 2): the vectors are device pointers and `stream` is where they
         // become ready, else host pointers and a null stream; points, challenges, coefficients and round results are host elements
@@ -809,6 +820,83 @@ pub mod poseidon {
                                                &domain as *const Fr as *const c_void, 0, std::ptr::null_mut())
             });
             out
+        }
+    }
+}
+
+/// `Bls12::pairing` and `product_of_pairings` for batches on the GPU (`mi355_msm_pairing_*`).  The points must be of order r or the
+/// point at infinity; nothing is tested.  Values come back as arkworks `Fq12` through the canonical form.
+pub mod pairing {
+    use super::sys;
+    use ark_ff::FromBytes;
+    use std::os::raw::c_void;
+
+    #[cfg(not(feature = "bls12_381"))]
+    use ark_bls12_377::{Fq12, G1Affine, G2Affine};
+    #[cfg(feature = "bls12_381")]
+    use ark_bls12_381::{Fq12, G1Affine, G2Affine};
+
+    const GT_BYTES: usize = 576;
+    #[cfg(not(feature = "bls12_381"))]
+    const CURVE: i32 = 0;
+    #[cfg(feature = "bls12_381")]
+    const CURVE: i32 = 1;
+
+    fn check(err: super::Error) {
+        if err.code != 0 {
+            panic!("{}", String::from(err));
+        }
+    }
+
+    pub struct Pairing {
+        handle: *mut c_void,
+    }
+
+    impl Drop for Pairing {
+        fn drop(&mut self) {
+            if !self.handle.is_null() {
+                let _ = unsafe { sys::mi355_msm_pairing_destroy(self.handle) };
+            }
+        }
+    }
+
+    impl Pairing {
+        /// `device < 0`: the current device
+        pub fn new(device: i32) -> Self {
+            let mut handle: *mut c_void = std::ptr::null_mut();
+            check(unsafe { sys::mi355_msm_pairing_create(&mut handle, CURVE, device) });
+            Pairing { handle }
+        }
+
+        /// `out[j] = prod_{i < group} e(p[j group + i], q[j group + i])`
+        pub fn pairing(&self, p: &[G1Affine], q: &[G2Affine], group: usize) -> Vec<Fq12> {
+            assert_eq!(p.len(), q.len(), "as many G1 as G2 points");
+            assert!(group > 0 && p.len() % group == 0, "whole groups");
+            let m = p.len() / group;
+            let mut raw = vec![0u8; m * GT_BYTES];
+            check(unsafe {
+                sys::mi355_msm_pairing_run(self.handle, raw.as_mut_ptr() as *mut c_void, p.as_ptr() as *const c_void, std::mem::size_of::<G1Affine>(),
+                                           q.as_ptr() as *const c_void, std::mem::size_of::<G2Affine>(), p.len(), group, 1, std::ptr::null_mut())
+            });
+            raw.chunks(GT_BYTES).map(|c| Fq12::read(c).expect("a canonical Fq12")).collect()
+        }
+
+        /// `Bls12::product_of_pairings`
+        pub fn product_of_pairings(&self, p: &[G1Affine], q: &[G2Affine]) -> Fq12 {
+            assert!(!p.is_empty(), "at least one pair");
+            self.pairing(p, q, p.len())[0]
+        }
+
+        /// one flag per group: the product over the group is one
+        pub fn check(&self, p: &[G1Affine], q: &[G2Affine], group: usize) -> Vec<bool> {
+            assert_eq!(p.len(), q.len(), "as many G1 as G2 points");
+            assert!(group > 0 && p.len() % group == 0, "whole groups");
+            let mut ok = vec![0u8; p.len() / group];
+            check(unsafe {
+                sys::mi355_msm_pairing_check(self.handle, ok.as_mut_ptr(), p.as_ptr() as *const c_void, std::mem::size_of::<G1Affine>(),
+                                             q.as_ptr() as *const c_void, std::mem::size_of::<G2Affine>(), p.len(), group, 0, std::ptr::null_mut())
+            });
+            ok.iter().map(|&b| b != 0).collect()
         }
     }
 }
