@@ -234,30 +234,24 @@ RustError mi355_msm_set_bases_compressed(mi355_msm_ctx* ctx, const void* records
     codec_check_ctx(ctx, "set_bases_compressed");
     if (npoints && !records) bad_arg("null records pointer");
     const size_t stride = 2 * coord_bytes(ctx->curve) + 8;
-    DevBuf raw;
-    try {
-      if (npoints) {
-        ensure_device(ctx);
-        raw.reserve(npoints * stride);
-      }
-      uint64_t o[8];
-      uint8_t st1 = 0;
-      // decode through the staged-input branch straight into `raw`: chunk by chunk, the images never visit the host
-      decompress_impl(ctx, records, npoints, raw.p, stride, 0, nullptr, o, false, true, &st1);
-      if (o[5] != npoints) {
-        static const char* const kWhy[4] = {"valid", "malformed: x is not below p or both flag bits are set", "no point has this x", ""};
-        bad_arg("set_bases_compressed: record %llu does not decode (status %u: %s); %llu of %zu records fail; the previous bases are kept",
-                (unsigned long long)o[5], (unsigned)st1, kWhy[st1 & 3], (unsigned long long)(o[2] + o[3]), npoints);
-      }
-      validate_new_bases(ctx, raw.p, npoints, stride, false, true);
-      ctx->bases_validated = false;
-      set_bases_device(ctx, raw.p, npoints, stride);
-      ctx->bases_validated = ctx->opt_validate_bases != 0;
-    } catch (...) {
-      raw.release();
-      throw;
+    ScratchBuf raw(ctx->own_stream);
+    if (npoints) {
+      ensure_device(ctx);
+      raw.reserve(npoints * stride);
     }
-    raw.release();
+    uint64_t o[8];
+    uint8_t st1 = 0;
+    // decode through the staged-input branch straight into `raw`: chunk by chunk, the images never visit the host
+    decompress_impl(ctx, records, npoints, raw.p, stride, 0, nullptr, o, false, true, &st1);
+    if (o[5] != npoints) {
+      static const char* const kWhy[4] = {"valid", "malformed: x is not below p or both flag bits are set", "no point has this x", ""};
+      bad_arg("set_bases_compressed: record %llu does not decode (status %u: %s); %llu of %zu records fail; the previous bases are kept",
+              (unsigned long long)o[5], (unsigned)st1, kWhy[st1 & 3], (unsigned long long)(o[2] + o[3]), npoints);
+    }
+    validate_new_bases(ctx, raw.p, npoints, stride, false, true);
+    ctx->bases_validated = false;
+    set_bases_device(ctx, raw.p, npoints, stride);
+    ctx->bases_validated = ctx->opt_validate_bases != 0;
   });
 }
 

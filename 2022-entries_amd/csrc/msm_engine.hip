@@ -217,6 +217,37 @@ struct DevBuf {
   T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// The temporary device buffer of one function: released on every path out of it.  Given the stream its launches and asynchronous copies
+// are enqueued on, it synchronises that stream first, so that no path -- an exception least of all -- unmaps a buffer in flight
+// (MI355_MSM_GUARD_TAIL; hipFree would wait by itself).  Members of contexts and handles stay plain DevBufs, released by their owners.
+struct ScratchBuf : private DevBuf {
+  using DevBuf::as;
+  using DevBuf::bytes;
+  using DevBuf::p;
+  using DevBuf::reserve;
+  ScratchBuf() = default;
+  explicit ScratchBuf(hipStream_t st) : stream(st), in_flight(true) {}
+  ScratchBuf(const ScratchBuf&) = delete;
+  ScratchBuf& operator=(const ScratchBuf&) = delete;
+  ~ScratchBuf() {
+    if (!p) return;
+    if (in_flight) (void)hipStreamSynchronize(stream);
+    release();
+  }
+  // the allocation, for an owner that outlives the function; this buffer is empty afterwards
+  DevBuf detach() {
+    const DevBuf b = *this;
+    p = nullptr;
+    bytes = 0;
+    guard = nullptr;
+    return b;
+  }
+
+ private:
+  hipStream_t stream = nullptr;
+  bool in_flight = false;
+};
+
 inline uint32_t ceil_div(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 inline uint32_t ilog2_floor(uint64_t v) { uint32_t r = 0; while (v >>= 1) r++; return r; }
 
@@ -786,27 +817,19 @@ void build_tables(mi355_msm_ctx* ctx, const uint8_t* d_raw, size_t n, size_t str
   ctx->bases.reserve(table_bytes);
   ctx->inf.reserve((size_t)windows * n);
   HIP_OK(Launch<E>::convert_bases(d_raw, stride, (uint32_t)n, ctx->bases_serialized, ctx->bases.as<AD>(), ctx->inf.as<uint8_t>(), st));
-  DevBuf xyzz, prefix;
-  try {
-    xyzz.reserve(n * sizeof(XD));
-    prefix.reserve(n * sizeof(El));
-    const uint32_t J = 64;
-    for (uint32_t w = 1; w < windows; w++) {
-      AD* prev = ctx->bases.as<AD>() + (size_t)(w - 1) * n;
-      AD* next = ctx->bases.as<AD>() + (size_t)w * n;
-      uint8_t* inf_prev = ctx->inf.as<uint8_t>() + (size_t)(w - 1) * n;
-      uint8_t* inf_next = ctx->inf.as<uint8_t>() + (size_t)w * n;
-      HIP_OK(Launch<E>::pre_double(prev, inf_prev, (uint32_t)n, level_shift, xyzz.as<XD>(), st));
-      HIP_OK(Launch<E>::pre_normalize(xyzz.as<XD>(), (uint32_t)n, J, prefix.as<El>(), next, inf_next, st));
-    }
-    HIP_OK(hipStreamSynchronize(st));
-  } catch (...) {
-    xyzz.release();
-    prefix.release();
-    throw;
+  ScratchBuf xyzz(st), prefix(st);
+  xyzz.reserve(n * sizeof(XD));
+  prefix.reserve(n * sizeof(El));
+  const uint32_t J = 64;
+  for (uint32_t w = 1; w < windows; w++) {
+    AD* prev = ctx->bases.as<AD>() + (size_t)(w - 1) * n;
+    AD* next = ctx->bases.as<AD>() + (size_t)w * n;
+    uint8_t* inf_prev = ctx->inf.as<uint8_t>() + (size_t)(w - 1) * n;
+    uint8_t* inf_next = ctx->inf.as<uint8_t>() + (size_t)w * n;
+    HIP_OK(Launch<E>::pre_double(prev, inf_prev, (uint32_t)n, level_shift, xyzz.as<XD>(), st));
+    HIP_OK(Launch<E>::pre_normalize(xyzz.as<XD>(), (uint32_t)n, J, prefix.as<El>(), next, inf_next, st));
   }
-  xyzz.release();
-  prefix.release();
+  HIP_OK(hipStreamSynchronize(st));
   ctx->pre_c = c;
   ctx->pre_windows = windows;
 }
@@ -824,19 +847,15 @@ void build_te(mi355_msm_ctx* ctx, size_t n, hipStream_t st) {
   ctx->flags.reserve(2 * sizeof(uint32_t));
   if (!ctx->h_flags) HIP_OK(hipHostMalloc((void**)&ctx->h_flags, 2 * sizeof(uint32_t), hipHostMallocDefault));
   HIP_OK(hipMemsetAsync(ctx->flags.p, 0, 2 * sizeof(uint32_t), st));
-  DevBuf prefix;
-  try {
+  {
+    ScratchBuf prefix(st);
     prefix.reserve(n * sizeof(Fe));
     for (size_t w = 0; w < levels; w++)
       HIP_OK(LaunchTe::convert(ctx->bases.as<AffineDev>() + w * n, ctx->inf.as<uint8_t>() + w * n, (uint32_t)n, 64, prefix.as<Fe>(),
                                ctx->te_bases.as<TeAffineDev>() + w * n, ctx->flags.as<uint32_t>(), st));
     HIP_OK(hipMemcpyAsync(ctx->h_flags, ctx->flags.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-  } catch (...) {
-    prefix.release();
-    throw;
   }
-  prefix.release();
   if (ctx->h_flags[0] != 0) {   // a 2-torsion point or one of the two u = -1 points among the bases
     ctx->te_bases.release();
     return;
@@ -844,12 +863,12 @@ void build_te(mi355_msm_ctx* ctx, size_t n, hipStream_t st) {
   ctx->te_active = true;
   if (levels > 1) {
     // keep level 0 of the short-Weierstrass tables only: it serves the (rare) XYZZ fallback, without tables
-    DevBuf level0;
+    ScratchBuf level0(st);
     level0.reserve(n * sizeof(AffineDev));
     HIP_OK(hipMemcpyAsync(level0.p, ctx->bases.p, n * sizeof(AffineDev), hipMemcpyDeviceToDevice, st));
     HIP_OK(hipStreamSynchronize(st));
     ctx->bases.release();
-    ctx->bases = level0;
+    ctx->bases = level0.detach();
     ctx->sw_level0_only = true;
   }
 }
@@ -940,9 +959,9 @@ bool build_tables_te_streamed(mi355_msm_ctx* ctx, const uint8_t* d_raw, size_t n
   HIP_OK(hipMemGetInfo(&free_b, &total_b));
   if (need > free_b + ctx->bases.bytes + ctx->te_bases.bytes + ctx->inf.bytes)
     bad_arg("precompute: %u table levels of %zu points need %zu MiB, only %zu MiB free", levels, n, need >> 20, free_b >> 20);
-  DevBuf xyzz, prefix, level0;   // (all three released on every path out: DevBuf has no destructor)
   bool ok = false;
   try {
+    ScratchBuf xyzz(st), prefix(st), level0(st);   // (inside the frame: they wait for the stream before the handler releases te_bases)
     ctx->te_bases.reserve((size_t)levels * n * sizeof(TeAffineDev));
     ctx->bases.reserve(3 * n * sizeof(AffineDev));       // slot 0 = level 0 (kept), slots 1 / 2 = the two most recent levels
     ctx->inf.reserve((size_t)levels * n);
@@ -972,18 +991,12 @@ bool build_tables_te_streamed(mi355_msm_ctx* ctx, const uint8_t* d_raw, size_t n
       HIP_OK(hipMemcpyAsync(level0.p, ctx->bases.p, n * sizeof(AffineDev), hipMemcpyDeviceToDevice, st));
       HIP_OK(hipStreamSynchronize(st));   // (a device-to-device hipMemcpy is not host-synchronous: the source is freed next)
       ctx->bases.release();
-      ctx->bases = level0;
-      level0 = DevBuf{};   // (ownership moved)
+      ctx->bases = level0.detach();
     }
   } catch (...) {
-    xyzz.release();
-    prefix.release();
-    level0.release();
     ctx->te_bases.release();
     throw;
   }
-  xyzz.release();
-  prefix.release();
   if (!ok) {
     ctx->te_bases.release();
     return false;
@@ -1895,7 +1908,7 @@ void fold_t(uint8_t* out, const uint8_t* in, size_t count) {
 
 void set_bases_host(mi355_msm_ctx* ctx, const void* affine, size_t npoints, size_t stride, bool serialized) {
   ensure_device(ctx);
-  DevBuf raw;
+  ScratchBuf raw(ctx->own_stream);
   ctx->bases_serialized = serialized;
   try {
     if (npoints) {
@@ -1907,11 +1920,9 @@ void set_bases_host(mi355_msm_ctx* ctx, const void* affine, size_t npoints, size
     set_bases_device(ctx, raw.p, npoints, stride);
   } catch (...) {
     ctx->bases_serialized = false;
-    raw.release();
     throw;
   }
   ctx->bases_serialized = false;
-  raw.release();
 }
 
 // Scalars in host memory: `batches` vectors of n scalars, `host_batch_pairs` scalars apart in the caller's buffer.
@@ -1965,7 +1976,7 @@ void check_bases_impl(mi355_msm_ctx* ctx, const void* pts, size_t n, size_t stri
     ensure_device(ctx);
     hipStream_t st = ctx->own_stream;
     const size_t piece = n < kCheckPiece ? n : kCheckPiece;
-    DevBuf raw, dstat;
+    ScratchBuf raw(st), dstat(st);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<uint8_t> hstat(piece);
     try {
@@ -2005,14 +2016,10 @@ void check_bases_impl(mi355_msm_ctx* ctx, const void* pts, size_t n, size_t stri
       (void)hipStreamSynchronize(st);
       if (ev0) (void)hipEventDestroy(ev0);
       if (ev1) (void)hipEventDestroy(ev1);
-      raw.release();
-      dstat.release();
       throw;
     }
     (void)hipEventDestroy(ev0);
     (void)hipEventDestroy(ev1);
-    raw.release();
-    dstat.release();
   }
   out[0] = cnt[0];
   out[1] = flagged;

@@ -78,31 +78,24 @@ void fixed_build_table(mi355_msm_fixed* fb, const uint8_t* base_affine) {
   const hipStream_t st = fb->own_stream;
   const uint32_t w = fb->w, levels = fb->levels;
   const size_t entries = (size_t)levels << w, img_bytes = 2 * coord_bytes(fb->curve) + 8;
-  DevBuf img, lb_x, lb_prefix, lb_a, lb_inf, t_x, t_prefix;
-  auto drop = [&] { for (DevBuf* b : {&img, &lb_x, &lb_prefix, &lb_a, &lb_inf, &t_x, &t_prefix}) b->release(); };
-  try {
-    img.reserve(img_bytes);
-    lb_x.reserve(levels * sizeof(XD));
-    lb_prefix.reserve(levels * sizeof(El));
-    lb_a.reserve(levels * sizeof(AD));
-    lb_inf.reserve(levels);
-    t_x.reserve(entries * sizeof(XD));
-    t_prefix.reserve(entries * sizeof(El));
-    fb->table.reserve(entries * sizeof(AD));
-    fb->table_inf.reserve(entries);
-    uint8_t packed[208] = {0};
-    memcpy(packed, base_affine, 2 * coord_bytes(fb->curve) + 1);   // (the caller's image may end at its flag byte)
-    HIP_OK(hipMemcpyAsync(img.p, packed, img_bytes, hipMemcpyHostToDevice, st));
-    HIP_OK(LaunchFixed<E>::level_bases(img.as<uint8_t>(), w, levels, lb_x.as<XD>(), st));
-    HIP_OK(Launch<E>::pre_normalize(lb_x.as<XD>(), levels, 1, lb_prefix.as<El>(), lb_a.as<AD>(), lb_inf.as<uint8_t>(), st));
-    HIP_OK(LaunchFixed<E>::table(lb_a.as<AD>(), lb_inf.as<uint8_t>(), w, levels, t_x.as<XD>(), st));
-    HIP_OK(Launch<E>::pre_normalize(t_x.as<XD>(), (uint32_t)entries, FB_NORM_RUN, t_prefix.as<El>(), fb->table.as<AD>(), fb->table_inf.as<uint8_t>(), st));
-    HIP_OK(hipStreamSynchronize(st));
-  } catch (...) {
-    drop();
-    throw;
-  }
-  drop();
+  ScratchBuf img(st), lb_x(st), lb_prefix(st), lb_a(st), lb_inf(st), t_x(st), t_prefix(st);
+  img.reserve(img_bytes);
+  lb_x.reserve(levels * sizeof(XD));
+  lb_prefix.reserve(levels * sizeof(El));
+  lb_a.reserve(levels * sizeof(AD));
+  lb_inf.reserve(levels);
+  t_x.reserve(entries * sizeof(XD));
+  t_prefix.reserve(entries * sizeof(El));
+  fb->table.reserve(entries * sizeof(AD));
+  fb->table_inf.reserve(entries);
+  uint8_t packed[208] = {0};
+  memcpy(packed, base_affine, 2 * coord_bytes(fb->curve) + 1);   // (the caller's image may end at its flag byte)
+  HIP_OK(hipMemcpyAsync(img.p, packed, img_bytes, hipMemcpyHostToDevice, st));
+  HIP_OK(LaunchFixed<E>::level_bases(img.as<uint8_t>(), w, levels, lb_x.as<XD>(), st));
+  HIP_OK(Launch<E>::pre_normalize(lb_x.as<XD>(), levels, 1, lb_prefix.as<El>(), lb_a.as<AD>(), lb_inf.as<uint8_t>(), st));
+  HIP_OK(LaunchFixed<E>::table(lb_a.as<AD>(), lb_inf.as<uint8_t>(), w, levels, t_x.as<XD>(), st));
+  HIP_OK(Launch<E>::pre_normalize(t_x.as<XD>(), (uint32_t)entries, FB_NORM_RUN, t_prefix.as<El>(), fb->table.as<AD>(), fb->table_inf.as<uint8_t>(), st));
+  HIP_OK(hipStreamSynchronize(st));
 }
 
 // one chunk, everything in device memory, enqueued on st

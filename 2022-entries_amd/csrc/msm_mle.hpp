@@ -7,7 +7,7 @@
 // mi355_msm_sparse_apply, and no twin whose name ends in _device.  Every call judges its arguments first (the handle last), derives its
 // constants in host arithmetic (1 - r, the half tables of eq, the coefficients) and enqueues separate launches on one stream.  The
 // passes of fix_variables, the half tables and the partial rows of a round live in `mle` (allocated on the first such call, kept by
-// the handle: query "mle_work_bytes"); host-pointer calls stage whole vectors through `mstage`.
+// the handle: query "mle_work_bytes"); host-pointer calls stage whole vectors through `mstage` (with the FrStage of fr_stage.hpp).
 #pragma once
 
 #include "launch_mle.hpp"
@@ -28,30 +28,6 @@ void mle_check_flags(unsigned flags) {
   if (flags & ~(kMleNormal | kMleDevice)) bad_arg("unknown flag bits 0x%x (bit 0: normal-form elements, bit 1: device pointers)", flags);
 }
 
-void mle_check_stream(bool device_ptrs, hipStream_t st) {
-  if (!device_ptrs && st) bad_arg("a stream goes with device pointers (flag bit 1) only");
-}
-
-// the vectors of a host-pointer call inside the staging buffer of the handle
-struct MleStage {
-  mi355_msm_domain* d;
-  size_t used = 0;
-  MleStage(mi355_msm_domain* d_, size_t elems) : d(d_) {
-    if (elems) d->mstage.reserve(elems * 32);
-  }
-  uint32_t* take(size_t elems) {
-    uint8_t* p = (uint8_t*)d->mstage.p + used;
-    used += elems * 32;
-    return (uint32_t*)p;
-  }
-  uint32_t* put(const void* host, size_t elems) {
-    uint32_t* p = take(elems);
-    HIP_OK(hipMemcpyAsync(p, host, elems * 32, hipMemcpyHostToDevice, d->own_stream));
-    return p;
-  }
-  void get(void* host, const uint32_t* dev, size_t elems) { HIP_OK(hipMemcpyAsync(host, dev, elems * 32, hipMemcpyDeviceToHost, d->own_stream)); }
-};
-
 void mle_fix(mi355_msm_domain* d, void* out, const void* in, unsigned num_vars, const void* point, unsigned k, unsigned flags, hipStream_t st) {
   mle_check_flags(flags);
   const bool device_ptrs = (flags & kMleDevice) != 0, normal = (flags & kMleNormal) != 0;
@@ -59,15 +35,15 @@ void mle_fix(mi355_msm_domain* d, void* out, const void* in, unsigned num_vars, 
   if (k > num_vars) bad_arg("%u variables to fix exceed the %u of the table", k, num_vars);
   if (!out || !in || (k && !point)) bad_arg("null input, output or point pointer");
   poly_check_aligned(device_ptrs, {out, in});
-  mle_check_stream(device_ptrs, st);
+  poly_check_stream(device_ptrs, st);
   const size_t n_in = (size_t)1 << num_vars, n_out = (size_t)1 << (num_vars - k);
   if (poly_overlap(out, n_out, in, n_in)) bad_arg("the output overlaps the input (a lane's pair is another block's output: the fold is not done in place)");
   poly_check_handle(d);
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   poly_timed(d, on, [&] {
-    MleStage g(d, device_ptrs ? 0 : n_in + n_out);
-    const uint32_t* src = device_ptrs ? (const uint32_t*)in : g.put(in, n_in);
-    uint32_t* dst = device_ptrs ? (uint32_t*)out : g.take(n_out);
+    FrStage g(d->mstage, device_ptrs, on, n_in + n_out);
+    const uint32_t* src = g.in(in, n_in);
+    uint32_t* dst = g.out(out, n_out);
     d->mle.reserve((size_t)mle_fix_work_elems(num_vars, k, d->poly_tile_log) * sizeof(Fr) + 64);
     with_fr(d->curve, [&]<class FR>() {
       Fr pt[MLE_MAX_VARS];
@@ -75,7 +51,7 @@ void mle_fix(mi355_msm_domain* d, void* out, const void* in, unsigned num_vars, 
       MleRun<FR> run{on};
       mle_chain_fix<FR>(run, dst, src, num_vars, pt, k, normal, d->poly_tile_log, d->mle.as<Fr>());
     });
-    if (!device_ptrs) g.get(out, dst, n_out);
+    g.back(out, dst, n_out);
   });
 }
 
@@ -85,7 +61,7 @@ void mle_eq(mi355_msm_domain* d, void* out, const void* point, unsigned k, unsig
   if (k > MLE_MAX_VARS) bad_arg("%u variables exceed %u", k, MLE_MAX_VARS);
   if (!out || (k && !point)) bad_arg("null output or point pointer");
   poly_check_aligned(device_ptrs, {out});
-  mle_check_stream(device_ptrs, st);
+  poly_check_stream(device_ptrs, st);
   poly_check_handle(d);
   const size_t n = (size_t)1 << k;
   const uint32_t lo_log = (k + 1) / 2, hi_log = k - lo_log;
@@ -100,8 +76,8 @@ void mle_eq(mi355_msm_domain* d, void* out, const void* point, unsigned k, unsig
   });
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   poly_timed(d, on, [&] {
-    MleStage g(d, device_ptrs ? 0 : n);
-    uint32_t* dst = device_ptrs ? (uint32_t*)out : g.take(n);
+    FrStage g(d->mstage, device_ptrs, on, n);
+    uint32_t* dst = g.out(out, n);
     d->mle.reserve((lo.size() + hi.size()) * sizeof(Fr) + 64);
     Fr* dlo = d->mle.as<Fr>();
     Fr* dhi = dlo + lo.size();
@@ -111,7 +87,7 @@ void mle_eq(mi355_msm_domain* d, void* out, const void* point, unsigned k, unsig
       MleRun<FR> run{on};
       mle_chain_eq<FR>(run, dst, dlo, dhi, k);
     });
-    if (!device_ptrs) g.get(out, dst, n);
+    g.back(out, dst, n);
   });
 }
 
@@ -127,7 +103,7 @@ void mle_round(mi355_msm_domain* d, void* evals_out, const void* const* tables, 
   for (size_t i = 0; i < m; i++)
     if (!tables[i] || (fused && !folded[i])) bad_arg("null table pointer");
   for (size_t i = 0; i < m; i++) poly_check_aligned(device_ptrs, {tables[i], fused ? folded[i] : nullptr});
-  mle_check_stream(device_ptrs, st);
+  poly_check_stream(device_ptrs, st);
   const size_t n_in = (size_t)1 << num_vars, n_half = n_in / 2;
   if (fused)
     for (size_t i = 0; i < m; i++) {
@@ -149,7 +125,7 @@ void mle_round(mi355_msm_domain* d, void* evals_out, const void* const* tables, 
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   const Fr* res = nullptr;
   poly_timed(d, on, [&] {
-    MleStage g(d, device_ptrs ? 0 : m * n_in + (fused ? m * n_half : 0));
+    FrStage g(d->mstage, device_ptrs, on, m * n_in + (fused ? m * n_half : 0));
     MleRound p{};
     p.npts = n_round / 2;
     p.m = (uint32_t)m;
@@ -157,10 +133,10 @@ void mle_round(mi355_msm_domain* d, void* evals_out, const void* const* tables, 
     p.tile_log = d->poly_tile_log;
     p.fused = fused ? 1u : 0u;
     for (size_t i = 0; i < m; i++) {
-      const uint32_t* src = device_ptrs ? (const uint32_t*)tables[i] : g.put(tables[i], n_in);
+      const uint32_t* src = g.in(tables[i], n_in);
       if (fused) {
         p.src[i] = src;
-        p.folded[i] = device_ptrs ? (uint32_t*)folded[i] : g.take(n_half);
+        p.folded[i] = g.out(folded[i], n_half);
         p.tab[i] = p.folded[i];
       } else {
         p.tab[i] = src;
@@ -186,8 +162,8 @@ void mle_round(mi355_msm_domain* d, void* evals_out, const void* const* tables, 
       MleRun<FR> run{on};
       res = mle_chain_round<FR>(run, p, D, d->mle.as<Fr>());
     });
-    if (fused && !device_ptrs)
-      for (size_t i = 0; i < m; i++) g.get(folded[i], p.folded[i], n_half);
+    if (fused)
+      for (size_t i = 0; i < m; i++) g.back(folded[i], p.folded[i], n_half);
   });
   Fr row[MLE_EVALS];
   HIP_OK(hipMemcpy(row, res, (D + 1) * sizeof(Fr), hipMemcpyDeviceToHost));

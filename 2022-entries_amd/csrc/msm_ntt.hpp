@@ -8,6 +8,7 @@
 // vector in flight and, for host-pointer calls, one staged vector.  A handle serves one call at a time.
 #pragma once
 
+#include "fr_stage.hpp"
 #include "launch_ntt.hpp"
 #include "launch_poly.hpp"
 #include "mle.hpp"      // (the limits of a sumcheck round, for the queries)

@@ -108,7 +108,7 @@ void pairing_call(mi355_msm_pairing* h, void* out, const void* g1, size_t g1_str
   if (n && (!out || !g1 || !g2)) bad_arg("null output, G1 or G2 pointer");
   const bool device_ptrs = (flags & kPrDevice) != 0;
   if (device_ptrs && (((uintptr_t)out & (check ? 0 : 3)) || ((uintptr_t)g1 & 3) || ((uintptr_t)g2 & 3))) bad_arg("device pointers must be 4-byte aligned");
-  if (!device_ptrs && st) bad_arg("a stream goes with device pointers (flag bit 1) only");
+  poly_check_stream(device_ptrs, st);
   const size_t unit = check ? 1 : PR_GT_BYTES, groups = n / group;
   if (pr_overlap(out, groups * unit, g1, n * g1_stride) || pr_overlap(out, groups * unit, g2, n * g2_stride)) bad_arg("the output overlaps an input");
   if (!h) bad_arg("null pairing handle");

@@ -6,7 +6,8 @@
 // poly/src/domain/radix2/mod.rs:141-216, poly/src/domain/mod.rs:190-197.  Every call judges its arguments first (the handle last, so the
 // other errors read the same with and without one), derives its constants in host arithmetic (the powers z^(2^i), n / Z(tau),
 // 1 / Z(g)) and enqueues separate launches on one stream.  The partial vectors of the scans live in `poly` (allocated on the first such
-// call, kept by the handle: query "poly_work_bytes"); host-pointer calls stage whole vectors through `pstage`.
+// call, kept by the handle: query "poly_work_bytes"); host-pointer calls stage whole vectors through `pstage`, with the FrStage of
+// fr_stage.hpp, which every call body below uses to name each of its vectors once, whichever kind of pointer the caller brought.
 #pragma once
 
 #include "launch_poly.hpp"
@@ -46,6 +47,11 @@ void poly_check_aligned(bool device_ptrs, std::initializer_list<const void*> ptr
     if ((uintptr_t)p & 3) bad_arg("device pointers must be 4-byte aligned");
 }
 
+// the calls that take the pointer kind as a flag bit (msm_mle.hpp, msm_sparse.hpp, msm_poseidon.hpp) take a stream with it
+void poly_check_stream(bool device_ptrs, hipStream_t st) {
+  if (!device_ptrs && st) bad_arg("a stream goes with device pointers (flag bit 1) only");
+}
+
 void poly_check_handle(mi355_msm_domain* d) {
   if (!d) bad_arg("null domain handle");
 }
@@ -79,28 +85,6 @@ void poly_fetch(mi355_msm_domain* d, void* out32, const Fr* dev, unsigned flags)
   with_fr(d->curve, [&]<class FR>() { poly_scalar_out<FR>(out32, x, (flags & kPolyNormal) != 0); });
 }
 
-// the vectors of a host-pointer call inside the staging buffer
-struct PolyStage {
-  mi355_msm_domain* d;
-  size_t used = 0;
-  PolyStage(mi355_msm_domain* d_, size_t elems) : d(d_) {   // (elems == 0: a device-pointer call, which stages nothing)
-    if (elems) d->pstage.reserve(elems * 32);
-  }
-  uint32_t* take(size_t elems) {
-    uint8_t* p = (uint8_t*)d->pstage.p + used;
-    used += elems * 32;
-    return (uint32_t*)p;
-  }
-  uint32_t* put(const void* host, size_t elems) {
-    uint32_t* p = take(elems);
-    if (elems) HIP_OK(hipMemcpyAsync(p, host, elems * 32, hipMemcpyHostToDevice, d->own_stream));
-    return p;
-  }
-  void get(void* host, const uint32_t* dev, size_t elems) {
-    if (elems) HIP_OK(hipMemcpyAsync(host, dev, elems * 32, hipMemcpyDeviceToHost, d->own_stream));
-  }
-};
-
 // ---- batch inversion --------------------------------------------------------------------------------------------------------------
 
 void poly_inverse_check(mi355_msm_domain* d, const void* out, const void* in, size_t n, unsigned flags, bool device_ptrs) {
@@ -125,15 +109,13 @@ void poly_inverse_enqueue(mi355_msm_domain* d, uint32_t* out, const uint32_t* in
 void poly_inverse(mi355_msm_domain* d, void* out, const void* in, size_t n, const void* coeff, unsigned flags, bool device_ptrs, hipStream_t st) {
   poly_inverse_check(d, out, in, n, flags, device_ptrs);
   if (n == 0) return;
-  if (device_ptrs) {
-    poly_timed(d, st, [&] { poly_inverse_enqueue(d, (uint32_t*)out, (const uint32_t*)in, n, coeff, flags, st); });
-    return;
-  }
-  poly_timed(d, d->own_stream, [&] {
-    PolyStage s(d, n);
-    uint32_t* v = s.put(in, n);
-    poly_inverse_enqueue(d, v, v, n, coeff, flags, d->own_stream);
-    s.get(out, v, n);
+  const hipStream_t on = device_ptrs ? st : d->own_stream;
+  poly_timed(d, on, [&] {
+    FrStage g(d->pstage, device_ptrs, on, n);
+    const uint32_t* src = g.in(in, n);
+    uint32_t* dst = g.out_over(out, src);
+    poly_inverse_enqueue(d, dst, src, n, coeff, flags, on);
+    g.back(out, dst, n);
   });
 }
 
@@ -168,20 +150,15 @@ void poly_vec(mi355_msm_domain* d, void* out, const void* a, const void* b, cons
   fr_zero(s);
   if (op == kPolyScale) with_fr(d->curve, [&]<class FR>() { poly_scalar<FR>(s, b, (flags & kPolyNormal) != 0); });
   if (n == 0) return;
-  const bool vb = op != kPolyScale, vc = op == kPolyMulSub;
-  if (device_ptrs) {
-    poly_timed(d, st, [&] {
-      poly_vec_enqueue(d, (uint32_t*)out, (const uint32_t*)a, vb ? (const uint32_t*)b : nullptr, vc ? (const uint32_t*)c : nullptr, n, op, s, flags, st);
-    });
-    return;
-  }
-  poly_timed(d, d->own_stream, [&] {
-    PolyStage g(d, 3 * n);
-    uint32_t* da = g.put(a, n);
-    const uint32_t* db = vb ? g.put(b, n) : nullptr;
-    const uint32_t* dc = vc ? g.put(c, n) : nullptr;
-    poly_vec_enqueue(d, da, da, db, dc, n, op, s, flags, d->own_stream);
-    g.get(out, da, n);
+  const hipStream_t on = device_ptrs ? st : d->own_stream;
+  poly_timed(d, on, [&] {
+    FrStage g(d->pstage, device_ptrs, on, 3 * n);
+    const uint32_t* da = g.in(a, n);
+    const uint32_t* db = op != kPolyScale ? g.in(b, n) : nullptr;
+    const uint32_t* dc = op == kPolyMulSub ? g.in(c, n) : nullptr;
+    uint32_t* dst = g.out_over(out, da);
+    poly_vec_enqueue(d, dst, da, db, dc, n, op, s, flags, on);
+    g.back(out, dst, n);
   });
 }
 
@@ -204,8 +181,8 @@ void poly_evaluate(mi355_msm_domain* d, void* out32, const void* coeffs, size_t 
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   const Fr* res = nullptr;
   poly_timed(d, on, [&] {
-    PolyStage g(d, device_ptrs ? 0 : n);
-    const uint32_t* src = device_ptrs ? (const uint32_t*)coeffs : g.put(coeffs, n);
+    FrStage g(d->pstage, device_ptrs, on, n);
+    const uint32_t* src = g.in(coeffs, n);
     Fr* work = poly_work(d, n);
     with_fr(d->curve, [&]<class FR>() {
       Fr zz;
@@ -235,9 +212,9 @@ void poly_divide(mi355_msm_domain* d, void* q, void* rem32, const void* coeffs, 
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   const Fr* res = nullptr;
   poly_timed(d, on, [&] {
-    PolyStage g(d, device_ptrs ? 0 : 2 * n);
-    const uint32_t* src = device_ptrs ? (const uint32_t*)coeffs : g.put(coeffs, n);
-    uint32_t* dst = device_ptrs ? (uint32_t*)q : g.take(n);
+    FrStage g(d->pstage, device_ptrs, on, 2 * n);
+    const uint32_t* src = g.in(coeffs, n);
+    uint32_t* dst = g.out(q, n);
     Fr* work = poly_work(d, n);
     with_fr(d->curve, [&]<class FR>() {
       Fr zz;
@@ -245,7 +222,7 @@ void poly_divide(mi355_msm_domain* d, void* q, void* rem32, const void* coeffs, 
       PolyRun<FR> run{on};
       res = poly_chain_divide<FR>(run, dst, src, n, normal, d->poly_tile_log, zz, work);
     });
-    if (!device_ptrs) g.get(q, dst, n - 1);
+    g.back(q, dst, n - 1);
   });
   if (rem32) poly_fetch(d, rem32, res, flags);
 }
@@ -281,11 +258,11 @@ void poly_lagrange(mi355_msm_domain* d, void* out, const void* tau, unsigned fla
   });
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   poly_timed(d, on, [&] {
-    PolyStage g(d, device_ptrs ? 0 : n);
-    p.dst = device_ptrs ? (uint32_t*)out : g.take(n);
+    FrStage g(d->pstage, device_ptrs, on, n);
+    p.dst = g.out(out, n);
     with_fr(d->curve, [&]<class FR>() { HIP_OK(LaunchPoly<FR>::lagrange(p, on)); });
     if (!p.in_domain) poly_inverse_enqueue(d, p.dst, p.dst, n, nullptr, flags, on);
-    if (!device_ptrs) g.get(out, p.dst, n);
+    g.back(out, p.dst, n);
   });
 }
 
@@ -318,15 +295,13 @@ void poly_divide_vanishing(mi355_msm_domain* d, void* out, const void* in, size_
     fr_inv<FR>(s, zg);
   });
   if (n == 0) return;
-  if (device_ptrs) {
-    poly_timed(d, st, [&] { poly_vec_enqueue(d, (uint32_t*)out, (const uint32_t*)in, nullptr, nullptr, n, kPolyScale, s, flags, st); });
-    return;
-  }
-  poly_timed(d, d->own_stream, [&] {
-    PolyStage g(d, n);
-    uint32_t* v = g.put(in, n);
-    poly_vec_enqueue(d, v, v, nullptr, nullptr, n, kPolyScale, s, flags, d->own_stream);
-    g.get(out, v, n);
+  const hipStream_t on = device_ptrs ? st : d->own_stream;
+  poly_timed(d, on, [&] {
+    FrStage g(d->pstage, device_ptrs, on, n);
+    const uint32_t* src = g.in(in, n);
+    uint32_t* dst = g.out_over(out, src);
+    poly_vec_enqueue(d, dst, src, nullptr, nullptr, n, kPolyScale, s, flags, on);
+    g.back(out, dst, n);
   });
 }
 

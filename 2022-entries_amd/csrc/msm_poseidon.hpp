@@ -4,8 +4,9 @@
 //
 // A parameter handle belongs to a domain handle: the field, the device, the stream of its host-pointer calls and the events of a
 // call are the domain's.  The table (the caller's constants and matrix, the sparse form of the partial rounds, the reductions of each
-// round) and the staged vectors of a host-pointer call are the handle's own (query "work_bytes").  create derives the sparse form in
-// host arithmetic; every call judges its arguments first, the handle last.
+// round) and the staged vectors of a host-pointer call are the handle's own (query "work_bytes"); hash and merkle stage through
+// `stage` with the FrStage of fr_stage.hpp.  create derives the sparse form in host arithmetic; every call judges its arguments
+// first, the handle last.
 #pragma once
 
 #include "launch_poseidon.hpp"
@@ -92,22 +93,16 @@ void pos_hash(mi355_msm_poseidon* p, void* out, const void* in, size_t n, size_t
   if (n_out > POS_MAX_LEN) bad_arg("%zu output elements per sponge exceed 2^16", n_out);
   if ((n && n_out && !out) || (n && in_len && !in)) bad_arg("null input or output pointer");
   poly_check_aligned(device_ptrs, {out, in});
-  if (!device_ptrs && st) bad_arg("a stream goes with device pointers (flag bit 1) only");
+  poly_check_stream(device_ptrs, st);
   if (poly_overlap(out, n * n_out, in, n * in_len)) bad_arg("the output overlaps the input");
   if (!p) bad_arg("null parameter handle");
   if (n == 0 || n_out == 0) return;
   mi355_msm_domain* d = p->d;
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   poly_timed(d, on, [&] {
-    const uint32_t* src = (const uint32_t*)in;
-    uint32_t* dst = (uint32_t*)out;
-    if (!device_ptrs) {
-      p->stage.reserve((n * in_len + n * n_out) * 32);
-      uint32_t* s = p->stage.as<uint32_t>();
-      if (in_len) HIP_OK(hipMemcpyAsync(s, in, n * in_len * 32, hipMemcpyHostToDevice, on));
-      src = s;
-      dst = s + n * in_len * 8;
-    }
+    FrStage g(p->stage, device_ptrs, on, n * in_len + n * n_out);
+    const uint32_t* src = g.in(in, n * in_len);
+    uint32_t* dst = g.out(out, n * n_out);
     with_fr(d->curve, [&]<class FR>() {
       PosRun r = pos_base<FR>(p, normal);
       r.in = src;
@@ -122,7 +117,7 @@ void pos_hash(mi355_msm_poseidon* p, void* out, const void* in, size_t n, size_t
         for (uint32_t e = 0; e < p->tab.rate; e++) poly_scalar<FR>(r.hdr[e], (const uint8_t*)header + 32 * e, normal);
       HIP_OK(LaunchPoseidon<FR>::hash(r, on));
     });
-    if (!device_ptrs) HIP_OK(hipMemcpyAsync(out, dst, n * n_out * 32, hipMemcpyDeviceToHost, on));
+    g.back(out, dst, n * n_out);
   });
 }
 
@@ -134,7 +129,7 @@ void pos_merkle(mi355_msm_poseidon* p, void* tree_out, const void* leaves, size_
   if (leaf_len >= POS_MAX_LEN) bad_arg("%zu elements per leaf exceed 2^16 - 1", leaf_len);
   if (!tree_out || !domain_sep || (leaf_len && !leaves)) bad_arg("null tree, leaves or domain separator pointer");
   poly_check_aligned(device_ptrs, {tree_out, leaves});
-  if (!device_ptrs && st) bad_arg("a stream goes with device pointers (flag bit 1) only");
+  poly_check_stream(device_ptrs, st);
   size_t P = 1;
   while (P < n_leaves) P *= 2;
   if (poly_overlap(tree_out, 2 * P - 1, leaves, n_leaves * leaf_len)) bad_arg("the tree overlaps the leaves");
@@ -143,15 +138,9 @@ void pos_merkle(mi355_msm_poseidon* p, void* tree_out, const void* leaves, size_
   mi355_msm_domain* d = p->d;
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   poly_timed(d, on, [&] {
-    const uint32_t* src = (const uint32_t*)leaves;
-    uint32_t* dst = (uint32_t*)tree_out;
-    if (!device_ptrs) {
-      p->stage.reserve((n_leaves * leaf_len + 2 * P - 1) * 32);
-      uint32_t* s = p->stage.as<uint32_t>();
-      if (leaf_len) HIP_OK(hipMemcpyAsync(s, leaves, n_leaves * leaf_len * 32, hipMemcpyHostToDevice, on));
-      src = s;
-      dst = s + n_leaves * leaf_len * 8;
-    }
+    FrStage g(p->stage, device_ptrs, on, n_leaves * leaf_len + 2 * P - 1);
+    const uint32_t* src = g.in(leaves, n_leaves * leaf_len);
+    uint32_t* dst = g.out(tree_out, 2 * P - 1);
     with_fr(d->curve, [&]<class FR>() {
       const PosRun base = pos_base<FR>(p, normal);
       Fr hl[POS_MAX_RATE], hn[POS_MAX_RATE];
@@ -170,7 +159,7 @@ void pos_merkle(mi355_msm_poseidon* p, void* tree_out, const void* leaves, size_
       PosEngineRun<FR> run{on};
       pos_merkle_chain(run, base, dst, src, n_leaves, (uint32_t)leaf_len, hl, hn, p->zeros);
     });
-    if (!device_ptrs) HIP_OK(hipMemcpyAsync(tree_out, dst, (2 * P - 1) * 32, hipMemcpyDeviceToHost, on));
+    g.back(tree_out, dst, 2 * P - 1);
   });
 }
 

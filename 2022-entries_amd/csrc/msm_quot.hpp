@@ -5,8 +5,8 @@
 // Every call judges its arguments first (the handle last, so the other errors read the same with and without one; what depends on
 // the size or the field of the domain can only be judged with one), derives its constants in host arithmetic and enqueues separate
 // launches on one stream.  The values x_i - 1, their inverses and the tile products of that inversion live in `quot` (allocated on the
-// first such call, kept by the handle: query "quotient_work_bytes"); host-pointer calls stage whole vectors through `qstage`.  The
-// other buffers of the handle are not touched.
+// first such call, kept by the handle: query "quotient_work_bytes"); host-pointer calls stage whole vectors through `qstage` (with
+// the FrStage of fr_stage.hpp).  The other buffers of the handle are not touched.
 #pragma once
 
 #include "launch_quot.hpp"
@@ -17,28 +17,6 @@ template <class FR>
 struct QuotRun : PolyRun<FR> {
   void xm1(const QuotXm1& p) { HIP_OK(LaunchQuot<FR>::xm1(p, this->st)); }
   void rows(const QuotRows& p) { HIP_OK(LaunchQuot<FR>::rows(p, this->st)); }
-};
-
-// the vectors of a host-pointer call inside the staging buffer
-struct QuotStage {
-  mi355_msm_domain* d;
-  size_t used = 0;
-  QuotStage(mi355_msm_domain* d_, size_t elems) : d(d_) {   // (elems == 0: a device-pointer call, which stages nothing)
-    if (elems) d->qstage.reserve(elems * 32);
-  }
-  uint32_t* take(size_t elems) {
-    uint8_t* p = (uint8_t*)d->qstage.p + used;
-    used += elems * 32;
-    return (uint32_t*)p;
-  }
-  uint32_t* put(const void* host, size_t elems) {
-    uint32_t* p = take(elems);
-    if (elems) HIP_OK(hipMemcpyAsync(p, host, elems * 32, hipMemcpyHostToDevice, d->own_stream));
-    return p;
-  }
-  void get(void* host, const uint32_t* dev, size_t elems) {
-    if (elems) HIP_OK(hipMemcpyAsync(host, dev, elems * 32, hipMemcpyDeviceToHost, d->own_stream));
-  }
 };
 
 bool quot_all_zero(const void* bytes32) {
@@ -121,19 +99,19 @@ void quot_call(mi355_msm_domain* d, const QuotArgs& a, bool device_ptrs, hipStre
   });
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   poly_timed(d, on, [&] {
-    QuotStage g(d, device_ptrs ? 0 : 2 * span + (a.selectors ? sel_span : 0) + (a.pi ? 3 : 2) * M);
-    p.wires = device_ptrs ? (const uint32_t*)a.wires : g.put(a.wires, span);
-    p.sigmas = device_ptrs ? (const uint32_t*)a.sigmas : g.put(a.sigmas, span);
-    p.selectors = !a.selectors ? nullptr : device_ptrs ? (const uint32_t*)a.selectors : g.put(a.selectors, sel_span);
-    p.z = device_ptrs ? (const uint32_t*)a.z : g.put(a.z, M);
-    p.pi = !a.pi ? nullptr : device_ptrs ? (const uint32_t*)a.pi : g.put(a.pi, M);
-    p.dst = device_ptrs ? (uint32_t*)a.out : g.take(M);
+    FrStage g(d->qstage, device_ptrs, on, 2 * span + (a.selectors ? sel_span : 0) + (a.pi ? 3 : 2) * M);
+    p.wires = g.in(a.wires, span);
+    p.sigmas = g.in(a.sigmas, span);
+    p.selectors = a.selectors ? g.in(a.selectors, sel_span) : nullptr;
+    p.z = g.in(a.z, M);
+    p.pi = a.pi ? g.in(a.pi, M) : nullptr;
+    p.dst = g.out(a.out, M);
     d->quot.reserve((size_t)quot_work_elems(M, d->poly_tile_log) * sizeof(Fr));
     with_fr(d->curve, [&]<class FR>() {
       QuotRun<FR> run{{on}};
       quot_chain<FR>(run, p, a2n, d->poly_tile_log, d->quot.as<Fr>());
     });
-    if (!device_ptrs) g.get(a.out, p.dst, M);
+    g.back(a.out, p.dst, M);
   });
 }
 
@@ -180,11 +158,11 @@ void lincomb_call(mi355_msm_domain* d, void* out, const void* const* cols, const
   });
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   poly_timed(d, on, [&] {
-    QuotStage g(d, device_ptrs ? 0 : total + n);
-    for (size_t j = 0; j < m; j++) p.cols[j] = device_ptrs ? (const uint32_t*)cols[j] : g.put(cols[j], lens[j]);
-    p.dst = device_ptrs ? (uint32_t*)out : g.take(n);
+    FrStage g(d->qstage, device_ptrs, on, total + n);
+    for (size_t j = 0; j < m; j++) p.cols[j] = g.in(cols[j], lens[j]);
+    p.dst = g.out(out, n);
     with_fr(d->curve, [&]<class FR>() { HIP_OK(LaunchQuot<FR>::lincomb(p, on)); });
-    if (!device_ptrs) g.get(out, p.dst, n);
+    g.back(out, p.dst, n);
   });
 }
 

@@ -4,7 +4,8 @@
 // Every call judges its arguments first (the handle last, so the other errors read the same with and without one) and enqueues
 // separate launches on one stream.  The totals and carries of the levels, and the numerators and denominators of the permutation
 // product with the work memory of their batch inversion, live in `scan` (allocated on the first such call, kept by the handle: query
-// "scan_work_bytes"); host-pointer calls stage whole vectors through `sstage`.  `work`, `stage`, `poly` and `pstage` are not touched.
+// "scan_work_bytes"); host-pointer calls stage whole vectors through `sstage` (with the FrStage of fr_stage.hpp).  `work`, `stage`,
+// `poly` and `pstage` are not touched.
 #pragma once
 
 #include "launch_scan.hpp"
@@ -18,28 +19,6 @@ struct ScanRun {
   void up(const ScanUp& p) { HIP_OK(LaunchScan<FR>::up(OP, p, st)); }
   template <unsigned OP>
   void down(const ScanDown& p) { HIP_OK(LaunchScan<FR>::down(OP, p, st)); }
-};
-
-// the vectors of a host-pointer call inside the scans' staging buffer
-struct ScanStage {
-  mi355_msm_domain* d;
-  size_t used = 0;
-  ScanStage(mi355_msm_domain* d_, size_t elems) : d(d_) {   // (elems == 0: a device-pointer call, which stages nothing)
-    if (elems) d->sstage.reserve(elems * 32);
-  }
-  uint32_t* take(size_t elems) {
-    uint8_t* p = (uint8_t*)d->sstage.p + used;
-    used += elems * 32;
-    return (uint32_t*)p;
-  }
-  uint32_t* put(const void* host, size_t elems) {
-    uint32_t* p = take(elems);
-    if (elems) HIP_OK(hipMemcpyAsync(p, host, elems * 32, hipMemcpyHostToDevice, d->own_stream));
-    return p;
-  }
-  void get(void* host, const uint32_t* dev, size_t elems) {
-    if (elems) HIP_OK(hipMemcpyAsync(host, dev, elems * 32, hipMemcpyDeviceToHost, d->own_stream));
-  }
 };
 
 void scan_identity_out(mi355_msm_domain* d, void* total32, unsigned op, unsigned flags) {
@@ -83,11 +62,12 @@ void scan_call(mi355_msm_domain* d, void* out, void* total32, const void* in, si
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   const Fr* res = nullptr;
   poly_timed(d, on, [&] {
-    ScanStage g(d, device_ptrs ? 0 : n);
-    uint32_t* v = device_ptrs ? nullptr : g.put(in, n);
+    FrStage g(d->sstage, device_ptrs, on, n);
+    const uint32_t* src = g.in(in, n);
+    uint32_t* dst = g.out_over(out, src);
     d->scan.reserve((size_t)scan_work_elems(n, d->poly_tile_log) * sizeof(Fr));
-    res = scan_enqueue(d, device_ptrs ? (uint32_t*)out : v, device_ptrs ? (const uint32_t*)in : v, nullptr, n, op, flags, d->scan.as<Fr>(), on);
-    if (!device_ptrs) g.get(out, v, n);
+    res = scan_enqueue(d, dst, src, nullptr, n, op, flags, d->scan.as<Fr>(), on);
+    g.back(out, dst, n);
   });
   if (total32) poly_fetch(d, total32, res, flags & kScanNormal);
 }
@@ -118,11 +98,11 @@ void perm_call(mi355_msm_domain* d, void* out, void* total32, const void* wires,
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   const Fr* res = nullptr;
   poly_timed(d, on, [&] {
-    ScanStage g(d, device_ptrs ? 0 : 2 * span + n);
+    FrStage g(d->sstage, device_ptrs, on, 2 * span + n);
     ScanPerm p{};
-    p.wires = device_ptrs ? (const uint32_t*)wires : g.put(wires, span);
-    p.sigmas = device_ptrs ? (const uint32_t*)sigmas : g.put(sigmas, span);
-    uint32_t* dst = device_ptrs ? (uint32_t*)out : g.take(n);
+    p.wires = g.in(wires, span);
+    p.sigmas = g.in(sigmas, span);
+    uint32_t* dst = g.out(out, n);
     // work memory: the scan's levels, the inversion's tile products, the numerators, the denominators
     const size_t scan_elems = (size_t)scan_work_elems(n, d->poly_tile_log), inv_elems = (size_t)poly_work_elems(n, d->poly_tile_log);
     d->scan.reserve((scan_elems + inv_elems) * sizeof(Fr) + 2 * n * 32);
@@ -146,7 +126,7 @@ void perm_call(mi355_msm_domain* d, void* out, void* total32, const void* wires,
       poly_chain_inverse<FR>(inv, p.den, p.den, n, normal, d->poly_tile_log, one, work + scan_elems);
     });
     res = scan_enqueue(d, dst, p.num, p.den, n, kScanProduct, flags, work, on);
-    if (!device_ptrs) g.get(out, dst, n);
+    g.back(out, dst, n);
   });
   if (total32) poly_fetch(d, total32, res, flags);
 }

@@ -224,20 +224,14 @@ static void sharded_set_bases(mi355_msm_ctx* ctx, const void* data, size_t n, si
       return;
     }
     __atomic_fetch_add(&ctx->peer_stagings, 1, __ATOMIC_RELAXED);
-    DevBuf stage;
-    try {
-      stage.reserve(cnt * stride);
-      // ON THE SHARD'S STREAM: a device-to-device hipMemcpy is not synchronous with the host and lives on the null stream, which the
-      // shard's non-blocking stream does not wait for -- the conversion kernel read the staging buffer before the copy had landed
-      // (found by tests/test_gpu_sharded.py::test_peer_staging_branches_on_logical_shards in round 5, on the first box where the
-      // timing exposed it: this branch had never executed before the "force_peer_staging" hook existed)
-      HIP_OK(hipMemcpyAsync(stage.p, src, cnt * stride, hipMemcpyDefault, sh->own_stream));
-      set_bases_device(sh, stage.p, cnt, stride);
-    } catch (...) {
-      stage.release();
-      throw;
-    }
-    stage.release();
+    ScratchBuf stage(sh->own_stream);
+    stage.reserve(cnt * stride);
+    // ON THE SHARD'S STREAM: a device-to-device hipMemcpy is not synchronous with the host and lives on the null stream, which the
+    // shard's non-blocking stream does not wait for -- the conversion kernel read the staging buffer before the copy had landed
+    // (found by tests/test_gpu_sharded.py::test_peer_staging_branches_on_logical_shards in round 5, on the first box where the
+    // timing exposed it: this branch had never executed before the "force_peer_staging" hook existed)
+    HIP_OK(hipMemcpyAsync(stage.p, src, cnt * stride, hipMemcpyDefault, sh->own_stream));
+    set_bases_device(sh, stage.p, cnt, stride);
   });
   ctx->nbases = n;
   if (ctx->opt_combine == 2) (void)rccl_ready(ctx, 3 * coord_bytes(ctx->curve));   // communicator + buffers now, not inside the first run

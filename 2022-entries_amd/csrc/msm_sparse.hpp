@@ -4,7 +4,8 @@
 // A matrix belongs to a domain handle: the field, the device, the stream of its host-pointer calls and the work memory of the sum scan
 // (`scan`) are the domain's.  Everything else -- the coefficients, the column indices, the row lists, the class-M copy of z, the lane
 // totals and the sums at the lane boundaries, the staged vectors of a host-pointer call -- is the matrix's own (query "work_bytes"), so
-// two matrices on one domain do not disturb each other.  Every call judges its arguments first, the handle last.
+// two matrices on one domain do not disturb each other; apply stages through `stage` with the FrStage of fr_stage.hpp.  Every call
+// judges its arguments first, the handle last.
 #pragma once
 
 #include "launch_sparse.hpp"
@@ -73,22 +74,16 @@ void sparse_create(mi355_msm_sparse** out, mi355_msm_domain* d, size_t rows, siz
       off += counts[i];
     }
     m->m = SparseMat{m->vals.as<uint32_t>(), at[0], at[1], at[2], at[3], at[4], (uint32_t)rows, (uint32_t)cols, pl.nnz, pl.nne, pl.nlanes, pl.slots};
-    DevBuf raw;
-    try {
-      if (pl.nnz) {
-        raw.reserve((size_t)pl.nnz * 32);
-        HIP_OK(hipMemcpyAsync(raw.p, values, (size_t)pl.nnz * 32, hipMemcpyHostToDevice, st));
-        const SparseVals p{raw.as<uint32_t>(), m->vals.as<uint32_t>(), pl.nnz, pl.slots, (flags & kSparseNormal) ? 1u : 0u};
-        with_fr(d->curve, [&]<class FR>() { HIP_OK(LaunchSparse<FR>::vals(p, st)); });
-      }
-      HIP_OK(hipStreamSynchronize(st));
-    } catch (...) {
-      (void)hipStreamSynchronize(st);
-      raw.release();
-      throw;
+    ScratchBuf raw(st);
+    if (pl.nnz) {
+      raw.reserve((size_t)pl.nnz * 32);
+      HIP_OK(hipMemcpyAsync(raw.p, values, (size_t)pl.nnz * 32, hipMemcpyHostToDevice, st));
+      const SparseVals p{raw.as<uint32_t>(), m->vals.as<uint32_t>(), pl.nnz, pl.slots, (flags & kSparseNormal) ? 1u : 0u};
+      with_fr(d->curve, [&]<class FR>() { HIP_OK(LaunchSparse<FR>::vals(p, st)); });
     }
-    raw.release();
+    HIP_OK(hipStreamSynchronize(st));
   } catch (...) {
+    (void)hipStreamSynchronize(st);   // (the copies of the index lists may be in flight)
     for (DevBuf* b : {&m->vals, &m->idx, &m->work, &m->stage}) b->release();
     throw;
   }
@@ -100,7 +95,7 @@ void sparse_apply(mi355_msm_sparse* m, void* out, const void* z, unsigned flags,
   const bool device_ptrs = (flags & kSparseDevice) != 0, normal = (flags & kSparseNormal) != 0;
   if (m ? ((m->m.rows && !out) || (m->m.cols && !z)) : (!out || !z)) bad_arg("null input or output pointer");
   poly_check_aligned(device_ptrs, {out, z});
-  if (!device_ptrs && st) bad_arg("a stream goes with device pointers (flag bit 1) only");
+  poly_check_stream(device_ptrs, st);
   if (out && out == z) bad_arg("the output overlaps z");
   if (!m) bad_arg("null matrix handle");
   if (poly_overlap(out, m->m.rows, z, m->m.cols)) bad_arg("the output overlaps z");
@@ -108,20 +103,14 @@ void sparse_apply(mi355_msm_sparse* m, void* out, const void* z, unsigned flags,
   if (m->m.rows == 0) return;
   const hipStream_t on = device_ptrs ? st : d->own_stream;
   poly_timed(d, on, [&] {
-    const uint32_t* src = (const uint32_t*)z;
-    uint32_t* dst = (uint32_t*)out;
-    if (!device_ptrs) {
-      m->stage.reserve(((size_t)m->m.cols + m->m.rows) * 32);
-      uint32_t* zs = m->stage.as<uint32_t>();
-      if (m->m.cols) HIP_OK(hipMemcpyAsync(zs, z, (size_t)m->m.cols * 32, hipMemcpyHostToDevice, on));
-      src = zs;
-      dst = zs + (size_t)m->m.cols * 8;
-    }
+    FrStage g(m->stage, device_ptrs, on, (size_t)m->m.cols + m->m.rows);
+    const uint32_t* src = g.in(z, m->m.cols);
+    uint32_t* dst = g.out(out, m->m.rows);
     with_fr(d->curve, [&]<class FR>() {
       SparseEngineRun<FR> run{d, on};
       sparse_chain<FR>(run, m->m, dst, src, normal, m->work.p);
     });
-    if (!device_ptrs) HIP_OK(hipMemcpyAsync(out, dst, (size_t)m->m.rows * 32, hipMemcpyDeviceToHost, on));
+    g.back(out, dst, m->m.rows);
   });
 }
 
