@@ -40,6 +40,7 @@ from .msm import (  # noqa: F401
     PoseidonMerkleTree,
     poseidon_parameters,
     Pairing,
+    HashToCurve,
 )
 from .dist import all_gather_partials, shard_bounds, sharded_msm  # noqa: F401,E402
 from . import formats  # noqa: F401,E402

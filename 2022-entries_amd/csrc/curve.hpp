@@ -358,6 +358,8 @@ MSM_HD void xyzz_dbl_affine(XyzzT<typename E::T>& acc, const typename E::T& x2, 
 }
 
 // acc = 2 * acc (dbl-2008-s-1).
+// (h2c.hpp holds a second statement of this law, h2c_slot_dbl, with every value in work memory between products: a change here must
+// be made there as well.)
 template <class E>
 MSM_HD void xyzz_dbl(XyzzT<typename E::T>& acc, const typename E::Md& md) {
   typename E::T u, v, w, s, xx, m, mm, t, d, y1 = acc.y;
@@ -457,6 +459,7 @@ MSM_HD void xyzz_madd(XyzzT<typename E::T>& acc, const AffineT<typename E::T>& p
 }
 
 // acc += b   (add-2008-s; 12M + 2S).
+// (h2c.hpp holds a second statement of this law and of add_tail, h2c_slot_add: a change here must be made there as well.)
 template <class E>
 MSM_HD void xyzz_add(XyzzT<typename E::T>& acc, const XyzzT<typename E::T>& b, const typename E::Md& md) {
   if (xyzz_is_inf<E>(b)) return;

@@ -2315,3 +2315,202 @@ int ht_gf_check(int ctx_curve, int ctx_sharded, int ctx_device, int dom_curve, i
   return m ? -1 : 0;
 }
 }
+
+// ---- hash-to-curve (h2c.hpp) with the limb-bound checker armed --------------------------------------------------------------------
+// The SAME MSM_HD functions the kernels of kernels_h2c.hip wrap: SHA-256, expand_message_xmd with the reduction, sqrt_ratio, the
+// simplified SWU map, the isogeny, the pair sum and the cofactor clearing; output by fb_normalize_run.  group 0: G1, 1: G2.
+#include "h2c.hpp"
+
+struct H2cHostDst {
+  uint8_t prime[256];
+  H2cDst d;
+  H2cHostDst(const uint8_t* dst, size_t len) {
+    h2c_make_dst(prime, d.prime_len, d.z_pad, dst, len);
+    d.prime = prime;
+  }
+};
+
+template <class E>
+static void t_h2c_field(const H2cDst& d, const uint8_t* data, const uint64_t* off, size_t n, uint32_t count, uint8_t* out) {
+  const typename E::Md md;
+  const uint32_t elems = count * (E::WORDS / 12);
+  for (size_t i = 0; i < n; i++)
+    h2c_expand<typename E::Fld>((uint32_t*)out + i * elems * 12, data + off[i], (uint32_t)(off[i + 1] - off[i]), elems, d, md);
+}
+
+// flags: bit 2 pairs (n even, n / 2 outputs, cleared), bit 3 Projective images; bit 0 set with bit 2 clear: n outputs, each cleared
+template <class E>
+static void t_h2c_map(const uint8_t* u, size_t n, unsigned flags, uint8_t* out, size_t stride) {
+  using El = typename E::T;
+  const typename E::Md md;
+  std::vector<XyzzDevT<El>> pts(n);
+  std::vector<uint8_t> ws(h2c_map_ws_bytes<E>() + h2c_clear_ws_bytes<E>() + 16);
+  for (size_t i = 0; i < n; i++) {
+    uint32_t w[E::WORDS];
+    memcpy(w, u + i * 4 * E::WORDS, 4 * E::WORDS);
+    El x;
+    E::from_abi(x, w, md);
+    h2c_map_at<E>(&pts[i].p, x, ws.data(), 1, md);
+  }
+  std::vector<XyzzDevT<El>> res;
+  if (flags & 4) {
+    res.resize(n / 2);
+    for (size_t j = 0; j < n / 2; j++) h2c_clear_at<E>(&res[j].p, &pts[2 * j].p, &pts[2 * j + 1].p, ws.data(), 1, md);
+  } else {
+    res = pts;
+    if (flags & 1)
+      for (size_t j = 0; j < n; j++) h2c_clear_at<E>(&res[j].p, &pts[j].p, nullptr, ws.data(), 1, md);
+  }
+  pm_host_output<E>(res, (flags & 8) ? 2u : 0u, out, stride, md);
+}
+
+// mode 0: h2c_clear; mode 1: plain double-and-add by the little-endian integer k of nbytes bytes, on Affine images of any curve points
+template <class E>
+static void t_h2c_clear(int mode, const uint8_t* points, size_t stride, size_t n, const uint8_t* k, size_t nbytes, uint8_t* out, size_t out_stride) {
+  using El = typename E::T;
+  const typename E::Md md;
+  std::vector<XyzzDevT<El>> res(n);
+  std::vector<uint8_t> ws(h2c_clear_ws_bytes<E>() + 16);
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t* img = points + i * stride;
+    uint32_t rec[2 * E::WORDS];
+    memcpy(rec, img, 8 * E::WORDS);
+    XyzzT<El> q;
+    if (img[8 * E::WORDS]) {
+      xyzz_set_inf<E>(q);
+    } else {
+      AffineT<El> a;
+      pm_load_point<E>(a, rec, md);
+      xyzz_from_affine<E>(q, a, false);
+    }
+    if (mode == 0) {
+      h2c_clear_at<E>(&res[i].p, &q, nullptr, ws.data(), 1, md);
+    } else {
+      XyzzT<El> acc;
+      xyzz_set_inf<E>(acc);
+      for (int bit = (int)(8 * nbytes) - 1; bit >= 0; bit--) {
+        xyzz_dbl<E>(acc, md);
+        if ((k[bit >> 3] >> (bit & 7)) & 1) xyzz_add<E>(acc, q, md);
+      }
+      res[i].p = acc;
+    }
+  }
+  pm_host_output<E>(res, 0, out, out_stride, md);
+}
+
+template <class E>
+static int t_h2c_sqrt_ratio(const uint8_t* u, const uint8_t* v, uint8_t* y) {
+  const typename E::Md md;
+  uint32_t w[E::WORDS];
+  typename E::T a, b, r;
+  memcpy(w, u, 4 * E::WORDS);
+  E::from_abi(a, w, md);
+  memcpy(w, v, 4 * E::WORDS);
+  E::from_abi(b, w, md);
+  bool sq;
+  if constexpr (E::WORDS == 12) {
+    sq = h2c_sqrt_ratio<E>(r, a, b, md);
+  } else {
+    Fe2 ws[H2C_MAP_SLOTS];
+    const H2cMem s{ws, 1};
+    s.put(HS_GXN, a);
+    s.put(HS_TV6, b);
+    sq = h2c_sqrt_ratio_slots<E>(s, md);
+    r = s.get(HS_Y);
+  }
+  E::to_abi(w, r, md);
+  memcpy(y, w, 4 * E::WORDS);
+  return sq ? 1 : 0;
+}
+
+template <class E>
+static void t_h2c_iso(const uint8_t* xn, const uint8_t* xd, const uint8_t* y, uint8_t* out, size_t stride) {
+  const typename E::Md md;
+  uint32_t w[E::WORDS];
+  typename E::T a, b, c;
+  memcpy(w, xn, 4 * E::WORDS);
+  E::from_abi(a, w, md);
+  memcpy(w, xd, 4 * E::WORDS);
+  E::from_abi(b, w, md);
+  memcpy(w, y, 4 * E::WORDS);
+  E::from_abi(c, w, md);
+  std::vector<XyzzDevT<typename E::T>> res(1);
+  if constexpr (E::WORDS == 12) {
+    h2c_iso<E>(res[0].p, a, b, c, md);
+  } else {
+    Fe2 ws[H2C_MAP_SLOTS];
+    const H2cMem s{ws, 1};
+    s.put(HS_XN, a);
+    s.put(HS_XD, b);
+    s.put(HS_Y, c);
+    h2c_iso_slots<E>(&res[0].p, s, md);
+  }
+  pm_host_output<E>(res, 0, out, stride, md);
+}
+
+#define H2C_GROUP(fn, ...) (group == 0 ? fn<Bls12_381_G1::E>(__VA_ARGS__) : fn<Bls12_381_G2::E>(__VA_ARGS__))
+extern "C" {
+int ht_h2c_sha256(const uint8_t* data, size_t len, uint8_t* out) {
+  if ((len && !data) || !out || len >= (1u << 28)) return -1;
+  uint32_t h[8];
+  h2c_sha256(h, data, (uint32_t)len);
+  for (int i = 0; i < 32; i++) out[i] = (uint8_t)(h[i >> 2] >> (24 - 8 * (i & 3)));
+  return 0;
+}
+// DST_prime (at most 256 bytes) and the state after 64 zero bytes; returns the length of DST_prime
+int ht_h2c_dst(const uint8_t* dst, size_t len, uint8_t* prime, uint32_t* z_pad) {
+  if (!dst || !len || !prime || !z_pad) return -1;
+  H2cHostDst d(dst, len);
+  memcpy(prime, d.prime, d.d.prime_len);
+  memcpy(z_pad, d.d.z_pad, 32);
+  return (int)d.d.prime_len;
+}
+// the reduction of hash_to_field on a raw 64-byte big-endian string: m = 1 or 2 strings in, m images of 48 bytes out
+int ht_h2c_reduce(const uint8_t* in, size_t count, uint8_t* out) {
+  if (!in || !out) return -1;
+  const Modulus<Bls12_381_Fq> md;
+  for (size_t j = 0; j < count; j++) {
+    uint32_t hi[8], lo[8], w[12];
+    for (int k = 0; k < 8; k++) {
+      const uint8_t* a = in + 64 * j + 4 * k;
+      hi[k] = ((uint32_t)a[0] << 24) | ((uint32_t)a[1] << 16) | ((uint32_t)a[2] << 8) | a[3];
+      lo[k] = ((uint32_t)a[32] << 24) | ((uint32_t)a[33] << 16) | ((uint32_t)a[34] << 8) | a[35];
+    }
+    h2c_reduce<Bls12_381_Fq>(w, hi, lo, md);
+    memcpy(out + 48 * j, w, 48);
+  }
+  return 0;
+}
+int ht_h2c_check_offsets(const uint64_t* off, size_t n, size_t data_bytes, char* msg, size_t msg_len) {
+  if (!msg || msg_len < 1) return -2;
+  const char* m = h2c_check_offsets(off, n, data_bytes);
+  snprintf(msg, msg_len, "%s", m ? m : "");
+  return m ? -1 : 0;
+}
+int ht_h2c_field(int group, const uint8_t* dst, size_t dst_len, const uint8_t* data, size_t data_bytes, const uint64_t* off, size_t n, unsigned count,
+                 uint8_t* out) {
+  if (group < 0 || group > 1 || !dst || !dst_len || count < 1 || count > 2 || (n && !out) || h2c_check_offsets(off, n, data_bytes)) return -1;
+  H2cHostDst d(dst, dst_len);
+  H2C_GROUP(t_h2c_field, d.d, data, off, n, count, out);
+  return 0;
+}
+int ht_h2c_map(int group, const uint8_t* u, size_t n, unsigned flags, uint8_t* out, size_t stride) {
+  if (group < 0 || group > 1 || (n && (!u || !out)) || (flags & ~13u) || ((flags & 4) && (n & 1)) || stride % 4) return -1;
+  H2C_GROUP(t_h2c_map, u, n, flags, out, stride);
+  return 0;
+}
+int ht_h2c_clear(int group, int mode, const uint8_t* points, size_t stride, size_t n, const uint8_t* k, size_t nbytes, uint8_t* out, size_t out_stride) {
+  if (group < 0 || group > 1 || (n && (!points || !out)) || (mode && !k) || mode < 0 || mode > 1) return -1;
+  H2C_GROUP(t_h2c_clear, mode, points, stride, n, k, nbytes, out, out_stride);
+  return 0;
+}
+int ht_h2c_sqrt_ratio(int group, const uint8_t* u, const uint8_t* v, uint8_t* y) {
+  if (group < 0 || group > 1 || !u || !v || !y) return -1;
+  return H2C_GROUP(t_h2c_sqrt_ratio, u, v, y);
+}
+int ht_h2c_iso(int group, const uint8_t* xn, const uint8_t* xd, const uint8_t* y, uint8_t* out, size_t stride) {
+  if (group < 0 || group > 1 || !xn || !xd || !y || !out) return -1;
+  H2C_GROUP(t_h2c_iso, xn, xd, y, out, stride);
+  return 0;
+}
+}

@@ -2985,4 +2985,5 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 #include "msm_mle.hpp"
 #include "msm_poseidon.hpp"
 #include "msm_pairing.hpp"
+#include "msm_h2c.hpp"
 #include "msm_gfft.hpp"

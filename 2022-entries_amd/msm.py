@@ -174,6 +174,12 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_pairing_check": [vp, vp, vp, sz, vp, sz, sz, sz, ctypes.c_uint, vp],
         "mi355_msm_pairing_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_pairing_destroy": [vp],
+        "mi355_msm_h2c_create": [ctypes.POINTER(vp), ci, vp, sz, ci],
+        "mi355_msm_h2c_field": [vp, vp, vp, sz, vp, sz, ctypes.c_uint, ctypes.c_uint, vp],
+        "mi355_msm_h2c_map": [vp, vp, sz, vp, sz, ctypes.c_uint, vp],
+        "mi355_msm_h2c_hash": [vp, vp, sz, vp, sz, vp, sz, ctypes.c_uint, vp],
+        "mi355_msm_h2c_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_h2c_destroy": [vp],
         "mi355_msm_domain_mle_fix": [vp, vp, vp, ctypes.c_uint, vp, ctypes.c_uint, ctypes.c_uint, vp],
         "mi355_msm_domain_mle_eq": [vp, vp, vp, ctypes.c_uint, ctypes.c_uint, vp],
         "mi355_msm_domain_sumcheck_round": [vp, vp, vp, sz, ctypes.c_uint, vp, sz, vp, vp, ctypes.c_uint, vp],
@@ -2170,6 +2176,158 @@ class Pairing:
     def close(self) -> None:
         if self.handle:
             _check(self._lib.mi355_msm_pairing_destroy(self.handle))
+            self.handle = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HashToCurve:
+    """Batch hash-to-curve on one GPU (mi355_msm_h2c_*): RFC 9380 for ``bls12_381_g1`` or ``bls12_381_g2`` with one domain separation
+    tag -- arkworks' ``MapToCurveBasedHasher<_, DefaultFieldHasher<Sha256, 128>, WBMap<_>>``.  ``msgs`` is a list of ``bytes``, an
+    ``(n, len)`` uint8 array or torch tensor (CPU or GPU), or a ``(data, offsets)`` pair (bytes and n + 1 offsets; on the GPU a uint8
+    tensor and an int64 tensor).  GPU tensors in give a GPU tensor out on the current stream (``out=``: one to write into).  The points
+    are arkworks ``Affine`` images (104 / 200 bytes a row; ``projective=True``: 144 / 288), ready for ``mul_points``, ``compress_points``
+    and ``Pairing.check``.  Meant for short messages; both BLS12-377 curves are refused (no standard suite exists)."""
+
+    def __init__(self, curve="bls12_381_g2", dst=b"", device: Optional[int] = None):
+        self.curve = _curve_id(curve)
+        self.handle = ctypes.c_void_p()
+        self._lib = load_library()
+        tag = dst.encode() if isinstance(dst, str) else bytes(dst)
+        keep = ctypes.create_string_buffer(tag, len(tag)) if tag else None
+        _check(self._lib.mi355_msm_h2c_create(ctypes.byref(self.handle), self.curve, ctypes.addressof(keep) if tag else None, len(tag),
+                                              -1 if device is None else device))
+        self.device = self.query("device")
+        self.m = 2 if self.curve >= 2 else 1
+
+    def _messages(self, msgs):
+        """-> (data _Buf or None, offsets pointer, keep-alive, n, data bytes, on the GPU?, stream, torch device)"""
+        if not self.handle:
+            raise MsmError(-1, "the hash-to-curve handle is closed")
+        import numpy as np
+
+        if isinstance(msgs, tuple) and len(msgs) == 2:
+            data, off = msgs
+            if hasattr(off, "is_cuda") and off.is_cuda:
+                import torch
+
+                if off.dtype != torch.int64 or off.dim() != 1 or off.numel() < 1 or not off.is_contiguous():
+                    raise ValueError("offsets on the GPU: a contiguous 1-D int64 tensor of n + 1 entries")
+                d = _Buf(data)
+                if not d.is_device or d.device_index != self.device or off.device.index != self.device:
+                    raise MsmError(-1, f"data and offsets must both live on device {self.device}")
+                return d, off.data_ptr(), off, off.numel() - 1, d.nbytes, True, d.stream, d.keep.device
+            off = np.ascontiguousarray(np.asarray(off.cpu() if hasattr(off, "cpu") else off), dtype=np.uint64)
+            if off.ndim != 1 or off.size < 1:
+                raise ValueError("offsets: n + 1 entries")
+            d = _Buf(data.cpu() if hasattr(data, "cpu") else data)
+            return d, off.ctypes.data, off, off.size - 1, d.nbytes, False, None, None
+        if hasattr(msgs, "is_cuda") or hasattr(msgs, "__array_interface__"):
+            if len(msgs.shape) != 2:
+                raise ValueError("an array of messages has the shape (n, len)")
+            n, ln = int(msgs.shape[0]), int(msgs.shape[1])
+            d = _Buf(msgs)
+            if d.is_device:
+                import torch
+
+                if d.device_index != self.device:
+                    raise MsmError(-1, f"an input lives on cuda:{d.device_index} but this handle is bound to device {self.device}")
+                off = torch.arange(n + 1, dtype=torch.int64, device=d.keep.device) * ln
+                return d, off.data_ptr(), off, n, d.nbytes, True, d.stream, d.keep.device
+            off = np.arange(n + 1, dtype=np.uint64) * np.uint64(ln)
+            return d, off.ctypes.data, off, n, d.nbytes, False, None, None
+        msgs = [bytes(x) for x in msgs]
+        off = np.zeros(len(msgs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in msgs], dtype=np.uint64)
+        d = _Buf(b"".join(msgs))
+        return d, off.ctypes.data, off, len(msgs), d.nbytes, False, None, None
+
+    def _output(self, rows, width, on_gpu, out, tdev):
+        if on_gpu:
+            import torch
+
+            if out is None:
+                out = torch.empty((rows, width), dtype=torch.uint8, device=tdev)
+            ob = _Buf(out)
+            if not ob.is_device or ob.keep is not out or ob.nbytes != rows * width:
+                raise ValueError(f"out: a contiguous uint8 GPU tensor of {rows} x {width} bytes")
+            return out, ob.ptr
+        if out is not None:
+            raise ValueError("out= goes with GPU tensors")
+        import numpy as np
+
+        res = np.zeros((rows, width), dtype=np.uint8)
+        return res, res.ctypes.data
+
+    def _image(self, projective):
+        return 144 * self.m if projective else 96 * self.m + 8
+
+    def _hash(self, msgs, flags, projective, out):
+        d, off, keep, n, nbytes, gpu, stream, tdev = self._messages(msgs)
+        width = self._image(projective)
+        res, ptr = self._output(n, width, gpu, out, tdev)
+        _check(self._lib.mi355_msm_h2c_hash(self.handle, ptr if n else None, width, d.ptr if nbytes else None, nbytes, off, n,
+                                            flags | (8 if projective else 0) | (2 if gpu else 0), stream))
+        del keep
+        return res
+
+    def hash(self, msgs, projective: bool = False, out=None):
+        """``hash_to_curve``: one point of the order-r subgroup per message, shape ``(n, image bytes)`` uint8"""
+        return self._hash(msgs, 0, projective, out)
+
+    def encode(self, msgs, projective: bool = False, out=None):
+        """``encode_to_curve`` (the non-uniform ``_NU_`` suite): one u per message"""
+        return self._hash(msgs, 1, projective, out)
+
+    def hash_to_field(self, msgs, count: int = 2, out=None):
+        """``count`` (1 or 2) elements of the base field per message: shape ``(n * count, 48 m)`` uint8, Montgomery images"""
+        if count not in (1, 2):
+            raise ValueError("count is 1 or 2")
+        d, off, keep, n, nbytes, gpu, stream, tdev = self._messages(msgs)
+        res, ptr = self._output(n * count, 48 * self.m, gpu, out, tdev)
+        _check(self._lib.mi355_msm_h2c_field(self.handle, ptr if n else None, d.ptr if nbytes else None, nbytes, off, n, count, 2 if gpu else 0, stream))
+        del keep
+        return res
+
+    def map_to_curve(self, u, pairs: bool = False, projective: bool = False, out=None):
+        """``WBMap::map_to_curve`` of n field images (no cofactor clearing); ``pairs=True``: n / 2 points
+        ``clear_cofactor(map(u[2j]) + map(u[2j + 1]))``"""
+        if not self.handle:
+            raise MsmError(-1, "the hash-to-curve handle is closed")
+        b = _Buf(u)
+        unit = 48 * self.m
+        if b.nbytes % unit:
+            raise ValueError(f"u: n images of {unit} bytes ({b.nbytes} bytes given)")
+        n = b.nbytes // unit
+        if pairs and n % 2:
+            raise ValueError(f"{n} field images are not whole pairs")
+        if b.is_device and b.device_index != self.device:
+            raise MsmError(-1, f"an input lives on cuda:{b.device_index} but this handle is bound to device {self.device}")
+        width = self._image(projective)
+        res, ptr = self._output(n // 2 if pairs else n, width, b.is_device, out, b.keep.device if b.is_device else None)
+        _check(self._lib.mi355_msm_h2c_map(self.handle, ptr if n else None, width, b.ptr if n else None, n,
+                                           (4 if pairs else 0) | (8 if projective else 0) | (2 if b.is_device else 0), b.stream))
+        return res
+
+    def query(self, key: str) -> int:
+        """ "work_bytes", "lanes_in_flight", "last_launches", "device", "curve", "dst_bytes", "dst_oversize", "block_lanes", "max_lanes" """
+        v = ctypes.c_uint64(0)
+        _check(self._lib.mi355_msm_h2c_query(self.handle, key.encode(), ctypes.byref(v)))
+        return int(v.value)
+
+    def close(self) -> None:
+        if self.handle:
+            _check(self._lib.mi355_msm_h2c_destroy(self.handle))
             self.handle = ctypes.c_void_p()
 
     def __enter__(self):

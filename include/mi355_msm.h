@@ -826,6 +826,55 @@ RustError mi355_msm_pairing_check(mi355_msm_pairing* h, uint8_t* ok, const void*
 RustError mi355_msm_pairing_query(mi355_msm_pairing* h, const char* key, uint64_t* value);
 RustError mi355_msm_pairing_destroy(mi355_msm_pairing* h);
 
+/* ---- batch hash-to-curve (RFC 9380; arkworks MapToCurveBasedHasher over WBMap with DefaultFieldHasher<Sha256, 128>; BLS12-381 G1 and G2) ----
+ * What a BLS verification starts with: H(m).  The suites are BLS12381G1_XMD:SHA-256_SSWU_RO_ and BLS12381G2_XMD:SHA-256_SSWU_RO_ (hash) and
+ * their _NU_ forms (encode), byte for byte RFC 9380's vectors as the arkworks tests read them.  A handle is made for one curve
+ * (MI355_BLS12_381_G1 or MI355_BLS12_381_G2) and one domain separation tag; both BLS12-377 curves are refused at create: no standard
+ * suite exists for them.
+ *   create  dst: 1 .. 255 bytes are used as they are; a longer tag is replaced by SHA-256("H2C-OVERSIZE-DST-" || dst) (RFC 9380 5.3.3).
+ *           device < 0: the current one.
+ *   field   hash_to_field: n messages as one byte buffer `data` of data_bytes bytes and n + 1 64-bit offsets (message i is
+ *           data[offsets[i] .. offsets[i + 1])); count 1 or 2; out receives count * m base-field images per message (m = 1 for G1, 2 for
+ *           G2), 48 bytes each, in the form the coordinates of an Affine image have (Montgomery, R = 2^384, little-endian), c0 before c1.
+ *           Host pointers: the offsets must be non-decreasing and end inside the buffer, which is checked before anything is
+ *           launched.  Device pointers: the offsets are not read on the host; the kernel clamps every message to the buffer, so a bad
+ *           offset cannot read outside it.  A message is shorter than 2^28 bytes.
+ *   map     n field images (48 m bytes each, packed) -> n points: simplified SWU on the isogenous curve, then the isogeny (WBMap::
+ *           map_to_curve; NO cofactor clearing: the points are on the curve, not in the subgroup).  With flag bit 2 (pairs) n must be
+ *           even and out receives n / 2 points clear_cofactor(map(u[2j]) + map(u[2j + 1])).
+ *   hash    messages as for field -> n points: hash_to_curve (two u per message, add, clear the cofactor); with flag bit 0
+ *           encode_to_curve (one u, clear).
+ *   Output: arkworks Affine images out_stride bytes apart (a multiple of 4, at least the image: 104 / 200 bytes), infinity as zeros
+ *           with the flag byte set; flag bit 3: normalised Projective images (144 / 288 bytes), as mi355_msm_mul_points writes them.
+ *   Flag bit 1 (value 2): every vector is a DEVICE pointer (4-byte aligned, offsets 8-byte) and `stream` is the hipStream_t on which
+ *           the inputs become ready (NULL = the default stream): the work is enqueued there and the call returns when the output is
+ *           written.  Without bit 1 they are host pointers, staged through a buffer the handle keeps, and a non-null stream is an error.
+ *   query   "work_bytes" (everything the handle holds on the device), "lanes_in_flight" (the widest launch of the last call),
+ *           "last_launches", "device", "curve", "dst_bytes", "dst_oversize"; "block_lanes" and "max_lanes", constants of the
+ *           kernels, are answered without a handle too.
+ * One call each with a flag bit, and no twin whose name ends in _device, as the pairing handle has it; the stream-ordering promise of
+ * flag bit 1 is pinned by a late-producer test in tests/test_gpu_h2c.py.  The handle belongs to one device.
+ * Scheme (csrc/h2c.hpp).  expand_message_xmd and the reduction run one lane per message with SHA-256 in registers: meant for short
+ * messages (32 .. 200 bytes); a lane per message is a poor shape for kilobyte messages, which work but serialise a wave on its
+ * longest.  The map runs one lane per u, division-free, sqrt_ratio as one exponentiation, the isogeny by Horner on the projective x;
+ * G1 clears the cofactor by h_eff = 1 - z, G2 by psi (Budroni-Pintore), which equals h_eff Q on every point of the curve.  Work
+ * buffers are sized by the lanes in flight ("max_lanes"), never by n -- but for the staging buffer of a host-pointer call, which holds
+ * that call's whole input, offsets and packed output.  Every constant is derived from the suite parameters by
+ * tools/gen_h2c_consts.py.  There is no CPU fallback.
+ * Errors: -1 with a message, decided before any device call, in this order: unknown flag bits; count / an odd n with pairs; the
+ * stride; null pointers (with n > 0); alignment; a stream without flag bit 1; bad offsets (host pointers); and last the null handle
+ * (then the stride against the handle's image, and overlap).  create: a null out-pointer, an unknown curve id, an empty tag, a
+ * BLS12-377 curve, then the device. */
+typedef struct mi355_msm_h2c mi355_msm_h2c;
+RustError mi355_msm_h2c_create(mi355_msm_h2c** out, int curve, const void* dst, size_t dst_len, int device);
+RustError mi355_msm_h2c_field(mi355_msm_h2c* h, void* out, const void* data, size_t data_bytes, const uint64_t* offsets, size_t n,
+                              unsigned count, unsigned flags, void* stream);
+RustError mi355_msm_h2c_map(mi355_msm_h2c* h, void* out, size_t out_stride, const void* u, size_t n, unsigned flags, void* stream);
+RustError mi355_msm_h2c_hash(mi355_msm_h2c* h, void* out, size_t out_stride, const void* data, size_t data_bytes, const uint64_t* offsets,
+                             size_t n, unsigned flags, void* stream);
+RustError mi355_msm_h2c_query(mi355_msm_h2c* h, const char* key, uint64_t* value);
+RustError mi355_msm_h2c_destroy(mi355_msm_h2c* h);
+
 /* ---- transforms of vectors of curve points over a domain (ARK poly/src/domain/mod.rs:99-170 on DomainCoeff = G1Projective / G2Projective) ----
  * domain.fft / ifft / coset_fft / coset_ifft on GROUP elements: what turns a monomial SRS [tau^j] G into the Lagrange SRS
  * [L_i(tau)] G (kind 1), and the transform behind FK20, cq and Caulk tables.  With in[j] a point and the products scalar multiples:

@@ -549,6 +549,64 @@ struct Pairing {
   }
 };
 
+// RFC 9380 hash-to-curve for batches on the GPU (mi355_msm_h2c_*): hash_to_curve / encode_to_curve / hash_to_field / map_to_curve for
+// MI355_BLS12_381_G1 or MI355_BLS12_381_G2 and one domain separation tag.  Messages are host byte strings; points come back as arkworks
+// Affine images (104 / 200 bytes), field elements as 48-byte Montgomery images.
+struct HashToCurve {
+  mi355_msm_h2c* handle = nullptr;
+  int curve;
+  HashToCurve(int curve_, const std::string& dst, int device = -1) : curve(curve_) {
+    check(mi355_msm_h2c_create(&handle, curve, dst.data(), dst.size(), device));
+  }
+  HashToCurve(const HashToCurve&) = delete;
+  HashToCurve& operator=(const HashToCurve&) = delete;
+  HashToCurve(HashToCurve&& o) noexcept : handle(o.handle), curve(o.curve) { o.handle = nullptr; }
+  size_t m() const { return curve >= 2 ? 2 : 1; }
+  size_t image_bytes() const { return 96 * m() + 8; }
+  uint64_t query(const char* key) const {
+    uint64_t v = 0;
+    check(mi355_msm_h2c_query(handle, key, &v));
+    return v;
+  }
+  static void pack(const std::vector<std::string>& msgs, std::vector<uint8_t>& data, std::vector<uint64_t>& off) {
+    off.assign(1, 0);
+    for (const std::string& s : msgs) {
+      data.insert(data.end(), s.begin(), s.end());
+      off.push_back(data.size());
+    }
+  }
+  // hash_to_curve (encode = false) or encode_to_curve: one Affine image per message
+  std::vector<uint8_t> hash(const std::vector<std::string>& msgs, bool encode = false) const {
+    std::vector<uint8_t> data, out(msgs.size() * image_bytes());
+    std::vector<uint64_t> off;
+    pack(msgs, data, off);
+    check(mi355_msm_h2c_hash(handle, out.data(), image_bytes(), data.data(), data.size(), off.data(), msgs.size(), encode ? 1u : 0u, nullptr));
+    return out;
+  }
+  // hash_to_field: count * m images of 48 bytes per message
+  std::vector<uint8_t> hash_to_field(const std::vector<std::string>& msgs, unsigned count = 2) const {
+    std::vector<uint8_t> data, out(msgs.size() * count * m() * 48);
+    std::vector<uint64_t> off;
+    pack(msgs, data, off);
+    check(mi355_msm_h2c_field(handle, out.data(), data.data(), data.size(), off.data(), msgs.size(), count, 0, nullptr));
+    return out;
+  }
+  // map_to_curve of n field images; pairs: n / 2 points clear_cofactor(map(u[2j]) + map(u[2j + 1]))
+  std::vector<uint8_t> map_to_curve(const std::vector<uint8_t>& u, bool pairs = false) const {
+    const size_t n = u.size() / (48 * m());
+    if (u.size() % (48 * m()) || (pairs && (n & 1))) throw std::invalid_argument("n field images of 48 m bytes, whole pairs");
+    std::vector<uint8_t> out((pairs ? n / 2 : n) * image_bytes());
+    check(mi355_msm_h2c_map(handle, out.data(), image_bytes(), u.data(), n, pairs ? 4u : 0u, nullptr));
+    return out;
+  }
+  ~HashToCurve() {
+    if (handle) {
+      RustError e = mi355_msm_h2c_destroy(handle);
+      if (e.message) std::free(e.message);
+    }
+  }
+};
+
 // ark-poly's DenseMultilinearExtension and the prover of ark-linear-sumcheck's ListOfProductsOfPolynomials on host vectors
 // (mi355_msm_domain_mle_fix, _mle_eq, _sumcheck_round): a table holds 2^nv evaluations, index b the point (b_0, .., b_{nv-1}) with b_0 the
 // lowest bit, and variables are fixed from the lowest bit upward.  The domain lends its field and its device; its size plays no part.

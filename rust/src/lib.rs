@@ -283,6 +283,16 @@ pub mod sys {
                                        n: usize, group: usize, flags: c_uint, stream: *mut c_void) -> Error;
         pub fn mi355_msm_pairing_query(h: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
         pub fn mi355_msm_pairing_destroy(h: *mut c_void) -> Error;
+        // Batch hash-to-curve (RFC 9380, BLS12-381 G1 / G2): messages as one byte buffer and n + 1 offsets; flag bit 0 encode_to_curve,
+        // bit 1 device pointers on `stream`, bit 2 pairs (map), bit 3 Projective images.
+        pub fn mi355_msm_h2c_create(out: *mut *mut c_void, curve: c_int, dst: *const c_void, dst_len: usize, device: c_int) -> Error;
+        pub fn mi355_msm_h2c_field(h: *mut c_void, out: *mut c_void, data: *const c_void, data_bytes: usize, offsets: *const u64, n: usize,
+                                   count: c_uint, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_h2c_map(h: *mut c_void, out: *mut c_void, out_stride: usize, u: *const c_void, n: usize, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_h2c_hash(h: *mut c_void, out: *mut c_void, out_stride: usize, data: *const c_void, data_bytes: usize, offsets: *const u64,
+                                  n: usize, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_h2c_query(h: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
+        pub fn mi355_msm_h2c_destroy(h: *mut c_void) -> Error;
         // dense multilinear extensions and sumcheck prover rounds on a domain handle (ark-poly's DenseMultilinearExtension, the prover of
         // ark-linear-sumcheck): flags bit 0: plain integers, bit 1 (value 2): the vectors are device pointers and `stream` is where they
         // become ready, else host pointers and a null stream; points, challenges, coefficients and round results are host elements
@@ -897,6 +907,87 @@ pub mod pairing {
                                              q.as_ptr() as *const c_void, std::mem::size_of::<G2Affine>(), p.len(), group, 0, std::ptr::null_mut())
             });
             ok.iter().map(|&b| b != 0).collect()
+        }
+    }
+}
+
+/// RFC 9380 hash-to-curve for batches on the GPU (`mi355_msm_h2c_*`): arkworks' `MapToCurveBasedHasher` over `WBMap` with
+/// `DefaultFieldHasher<Sha256, 128>`, BLS12-381 only (no standard suite exists for BLS12-377).
+#[cfg(feature = "bls12_381")]
+pub mod h2c {
+    use super::sys;
+    use ark_bls12_381::{G1Affine, G2Affine};
+    use std::os::raw::c_void;
+
+    fn check(err: super::Error) {
+        if err.code != 0 {
+            panic!("{}", String::from(err));
+        }
+    }
+
+    pub struct HashToCurve {
+        handle: *mut c_void,
+        g2: bool,
+    }
+
+    impl Drop for HashToCurve {
+        fn drop(&mut self) {
+            if !self.handle.is_null() {
+                let _ = unsafe { sys::mi355_msm_h2c_destroy(self.handle) };
+            }
+        }
+    }
+
+    impl HashToCurve {
+        /// `g2`: hash to G2 (curve id 3) instead of G1 (curve id 1); `device < 0`: the current device
+        pub fn new(g2: bool, dst: &[u8], device: i32) -> Self {
+            let mut handle: *mut c_void = std::ptr::null_mut();
+            check(unsafe { sys::mi355_msm_h2c_create(&mut handle, if g2 { 3 } else { 1 }, dst.as_ptr() as *const c_void, dst.len(), device) });
+            HashToCurve { handle, g2 }
+        }
+
+        fn pack(msgs: &[&[u8]]) -> (Vec<u8>, Vec<u64>) {
+            let mut data = Vec::new();
+            let mut off = vec![0u64];
+            for m in msgs {
+                data.extend_from_slice(m);
+                off.push(data.len() as u64);
+            }
+            (data, off)
+        }
+
+        fn run<T: Copy + Default>(&self, msgs: &[&[u8]], flags: u32) -> Vec<T> {
+            let (data, off) = Self::pack(msgs);
+            let mut out = vec![T::default(); msgs.len()];
+            check(unsafe {
+                sys::mi355_msm_h2c_hash(self.handle, out.as_mut_ptr() as *mut c_void, std::mem::size_of::<T>(), data.as_ptr() as *const c_void, data.len(),
+                                        off.as_ptr(), msgs.len(), flags, std::ptr::null_mut())
+            });
+            out
+        }
+
+        /// `hash_to_curve` into G1 (a handle made with `g2 = false`)
+        pub fn hash_g1(&self, msgs: &[&[u8]]) -> Vec<G1Affine> {
+            assert!(!self.g2, "this handle hashes to G2");
+            self.run(msgs, 0)
+        }
+
+        /// `hash_to_curve` into G2 (a handle made with `g2 = true`)
+        pub fn hash_g2(&self, msgs: &[&[u8]]) -> Vec<G2Affine> {
+            assert!(self.g2, "this handle hashes to G1");
+            self.run(msgs, 0)
+        }
+
+        /// `encode_to_curve` into G1
+        pub fn encode_g1(&self, msgs: &[&[u8]]) -> Vec<G1Affine> {
+            assert!(!self.g2, "this handle hashes to G2");
+            self.run(msgs, 1)
+        }
+
+        /// `encode_to_curve` into G2
+        pub fn encode_g2(&self, msgs: &[&[u8]]) -> Vec<G2Affine> {
+            assert!(self.g2, "this handle hashes to G1");
+            self.run(msgs, 1)
         }
     }
 }
