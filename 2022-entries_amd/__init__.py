@@ -36,6 +36,7 @@ from .msm import (  # noqa: F401
     mul_by_cofactor,
     Radix2EvaluationDomain,
     SparseMatrix,
+    LookupTable,
     Poseidon,
     PoseidonMerkleTree,
     poseidon_parameters,

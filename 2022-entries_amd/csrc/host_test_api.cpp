@@ -2514,3 +2514,146 @@ int ht_h2c_iso(int group, const uint8_t* xn, const uint8_t* xd, const uint8_t* y
   return 0;
 }
 }
+
+// ---- lookup tables and the logUp sum (lookup.hpp): the build, the probe, the counters as elements, the u32 scan, the expansion and the
+// rows of the logUp sum lane by lane in order -- the atomics are plain sequential operations here -- and the chains the engine runs ------
+#include "lookup.hpp"
+
+struct HostLookupRun {
+  // a tile of the u32 scan in order: what the block's lanes do through LDS
+  void scan_up(const LookupScan& p) {
+    const uint64_t T = (uint64_t)1 << LOOKUP_SCAN_TILE_LOG;
+    for (uint64_t tile = 0; tile * T < p.n; tile++) {
+      uint32_t acc = 0;
+      for (uint64_t i = 0; i < T; i++) acc += lookup_scan_elem(p, tile * T + i);
+      p.totals[tile] = acc;
+    }
+  }
+  void scan_down(const LookupScan& p) {
+    const uint64_t T = (uint64_t)1 << LOOKUP_SCAN_TILE_LOG;
+    for (uint64_t tile = 0; tile * T < p.n; tile++) {
+      uint32_t acc = p.carry ? p.carry[tile] : 0u;
+      for (uint64_t i = 0; i < T && tile * T + i < p.n; i++) {
+        const uint32_t e = lookup_scan_elem(p, tile * T + i);
+        p.dst[tile * T + i] = acc;
+        acc += e;
+      }
+    }
+  }
+};
+
+// create + count + sorted: every output may be NULL; info = {slots, distinct, max_probe}
+template <class FR>
+static int t_lookup(unsigned flags, const uint8_t* table, uint64_t n_t, const uint8_t* values, uint64_t n_f, uint8_t* mult_out, uint32_t* index_out,
+                    uint64_t* stats, uint8_t* s_out, uint64_t* info) {
+  std::vector<uint32_t> raw(n_t * 8), keys(n_t * 8), vals(n_f * 8), count(n_t, 0u), index(n_f);
+  memcpy(raw.data(), table, n_t * 32);
+  if (n_f) memcpy(vals.data(), values, n_f * 32);
+  uint32_t nslots = 2;
+  while (nslots < 2 * n_t) nslots <<= 1;
+  std::vector<uint32_t> slots(nslots, LOOKUP_EMPTY);
+  LookupHead head{};
+  head.first = ~0ull;
+  const LookupCanon cp{raw.data(), keys.data(), n_t};
+  for (uint64_t i = 0; i < n_t; i++) lookup_canon_elem<FR>(cp, i);
+  const LookupTab tab{keys.data(), slots.data(), (uint32_t)n_t, nslots - 1};
+  const LookupBuild bp{tab, &head};
+  for (uint32_t i = 0; i < n_t; i++) {
+    uint32_t steps;
+    if (lookup_insert(bp, i, steps)) head.distinct++;
+    lookup_note_walk(bp, steps);
+  }
+  if (head.err) return -2;
+  const LookupProbe pp{tab, vals.data(), n_f, n_f ? index.data() : nullptr, count.data(), &head, 1u};
+  for (uint64_t j = 0; j < n_f; j++) lookup_credit(pp, lookup_find<FR>(pp, j), j, 1u);
+  if (head.err) return -2;
+  if (info) {
+    info[0] = nslots;
+    info[1] = head.distinct;
+    info[2] = head.max_probe;
+  }
+  if (stats) {
+    stats[0] = head.missing;
+    stats[1] = head.missing ? head.first : n_f;
+  }
+  if (index_out && n_f) memcpy(index_out, index.data(), n_f * 4);
+  if (mult_out) {
+    std::vector<uint32_t> dst(n_t * 8);
+    LookupMult mp{count.data(), dst.data(), (uint32_t)n_t, (flags & kLookupNormal) ? 1u : 0u, Fr{}};
+    lookup_image_const<FR>(mp.image);
+    for (uint32_t i = 0; i < n_t; i++) lookup_mult_elem<FR>(mp, i);
+    memcpy(mult_out, dst.data(), n_t * 32);
+  }
+  if (s_out && !head.missing) {
+    std::vector<uint32_t> off(n_t), levels(lookup_scan_work_words(n_t)), dst((n_t + n_f) * 8);
+    HostLookupRun run;
+    lookup_scan_chain(run, off.data(), count.data(), n_t, levels.data());
+    const LookupExpand ep{keys.data(), off.data(), dst.data(), (uint32_t)n_t, n_t + n_f};
+    for (uint64_t g = 0; g < n_t + n_f; g++) lookup_expand_elem(ep, g);
+    memcpy(s_out, dst.data(), (n_t + n_f) * 32);
+  }
+  return 0;
+}
+
+template <class FR>
+static int t_logup_sum(uint32_t tile_log, unsigned flags, const uint8_t* table, const uint8_t* mult, const uint8_t* values, uint32_t m, uint64_t stride,
+                       uint64_t n, const uint8_t* beta, uint8_t* out, uint8_t* total32, uint8_t* helpers) {
+  const bool normal = (flags & kLookupNormal) != 0;
+  if (n == 0) {
+    if (total32) memset(total32, 0, 32);
+    return 0;
+  }
+  const uint64_t span = (m - 1) * stride + n, hn = (uint64_t)(m + 1) * n;
+  std::vector<uint32_t> v(span * 8), t(n * 8), mu(n * 8), h(hn * 8), term(n * 8), dst(n * 8);
+  memcpy(v.data(), values, span * 32);
+  memcpy(t.data(), table, n * 32);
+  memcpy(mu.data(), mult, n * 32);
+  LogupRows p{};
+  p.values = v.data();
+  p.table = t.data();
+  p.mult = mu.data();
+  p.helpers = h.data();
+  p.term = term.data();
+  p.n = n;
+  p.stride = stride;
+  p.m = m;
+  p.normal = normal ? 1u : 0u;
+  poly_scalar<FR>(p.beta, beta, normal);
+  for (uint64_t j = 0; j < n; j++) logup_den_row<FR>(p, j);
+  std::vector<Fr> iwork(poly_work_elems(hn, tile_log)), work(scan_work_elems(n, tile_log));
+  Fr one;
+  fr_set<FR>(one, FR::ONE);
+  HostPolyRun<FR> inv;
+  poly_chain_inverse<FR>(inv, h.data(), h.data(), hn, normal, tile_log, one, iwork.data());
+  for (uint64_t j = 0; j < n; j++) logup_term_row<FR>(p, j);
+  HostScanRun<FR> run;
+  const Fr* res = scan_chain<FR, kScanSum>(run, dst.data(), term.data(), nullptr, n, normal, false, tile_log, work.data());
+  if (total32) poly_scalar_out<FR>(total32, *res, normal);
+  memcpy(out, dst.data(), n * 32);
+  if (helpers) memcpy(helpers, h.data(), hn * 32);
+  return 0;
+}
+
+extern "C" {
+// mi355_msm_lookup_create + _count + _sorted on the host: flags bit 0, plain integers; mult_out (n_t elements), index_out (n_f u32), stats
+// (2), s_out (n_t + n_f elements; untouched when a value is missing) and info (slots, distinct, max_probe) may each be NULL
+int ht_lookup(int field, unsigned flags, const uint8_t* table, uint64_t n_t, const uint8_t* values, uint64_t n_f, uint8_t* mult_out, uint32_t* index_out,
+              uint64_t* stats, uint8_t* s_out, uint64_t* info) {
+  if ((flags & ~kLookupNormal) || n_t < 1 || n_t > ((uint64_t)1 << 22) || n_f > ((uint64_t)1 << 22) || !table || (n_f && !values)) return -1;
+  return POLY_FIELD(t_lookup, flags, table, n_t, values, n_f, mult_out, index_out, stats, s_out, info);
+}
+// the hash of one canonical key, for the tests of its mixing
+unsigned ht_lookup_hash(const uint8_t* key32) {
+  uint32_t w[8];
+  memcpy(w, key32, 32);
+  return lookup_hash(w);
+}
+// mi355_msm_domain_logup_sum on the host; total32 and helpers ((m + 1) n elements) may be NULL
+int ht_logup_sum(int field, unsigned tile_log, unsigned flags, const uint8_t* table, const uint8_t* mult, const uint8_t* values, unsigned m, uint64_t stride,
+                 uint64_t n, const uint8_t* beta, uint8_t* out, uint8_t* total32, uint8_t* helpers) {
+  if (tile_log < POLY_TILE_LOG_MIN || tile_log > POLY_TILE_LOG_MAX || (flags & ~kLookupNormal) || m < 1 || m > LOGUP_MAX_COLUMNS || stride < n ||
+      n > ((uint64_t)1 << 20) || stride > ((uint64_t)1 << 22) || !beta || (n && (!table || !mult || !values || !out)))
+    return -1;
+  return POLY_FIELD(t_logup_sum, tile_log, flags, table, mult, values, m, stride, n, beta, out, total32, helpers);
+}
+}

@@ -2987,3 +2987,4 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 #include "msm_pairing.hpp"
 #include "msm_h2c.hpp"
 #include "msm_gfft.hpp"
+#include "msm_lookup.hpp"

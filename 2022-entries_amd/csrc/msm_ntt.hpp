@@ -25,6 +25,7 @@ struct mi355_msm_domain {
   DevBuf scan, sstage;    // msm_scan.hpp: the levels of the scans and the rows of the permutation product; the staged vectors of its host-pointer calls
   DevBuf quot, qstage;    // msm_quot.hpp: x - 1 per row, its inverses and their tile products; the staged vectors of its host-pointer calls
   DevBuf mle, mstage;     // msm_mle.hpp: the passes of fix_variables, the half tables of eq, the partial rows of a round; the staged vectors of its host-pointer calls
+  DevBuf logup, lstage;   // msm_lookup.hpp: the denominators, the terms and the levels of the logUp sum; the staged vectors of its host-pointer calls
   uint32_t mle_levels = 0;   // launches of the most recent sumcheck round: the round and its further sums
   Fr size_inv{};
   Fr g_have{};            // the (inverted, for the inverse kinds) offset the offset tables hold
@@ -66,7 +67,7 @@ void with_fr(int curve, Fn&& fn) {
 }
 
 void domain_release(mi355_msm_domain* d) {
-  for (DevBuf* b : {&d->tables, &d->work, &d->stage, &d->poly, &d->pstage, &d->scan, &d->sstage, &d->quot, &d->qstage, &d->mle, &d->mstage}) b->release();
+  for (DevBuf* b : {&d->tables, &d->work, &d->stage, &d->poly, &d->pstage, &d->scan, &d->sstage, &d->quot, &d->qstage, &d->mle, &d->mstage, &d->logup, &d->lstage}) b->release();
   for (hipEvent_t& e : d->ev)
     if (e) { (void)hipEventDestroy(e); e = nullptr; }
   if (d->own_stream) { (void)hipStreamDestroy(d->own_stream); d->own_stream = nullptr; }
@@ -387,6 +388,7 @@ RustError mi355_msm_domain_query(mi355_msm_domain* d, const char* key, uint64_t*
     else if (k == "scan_work_bytes") *value = d->scan.bytes + d->sstage.bytes;
     else if (k == "quotient_work_bytes") *value = d->quot.bytes + d->qstage.bytes;
     else if (k == "mle_work_bytes") *value = d->mle.bytes + d->mstage.bytes;
+    else if (k == "logup_work_bytes") *value = d->logup.bytes + d->lstage.bytes;
     else if (k == "sumcheck_levels") *value = d->mle_levels;
     else if (k == "poly_tile_log") *value = d->poly_tile_log;
     else if (k == "device") *value = (uint64_t)d->device;

@@ -163,6 +163,12 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_sparse_apply": [vp, vp, vp, ctypes.c_uint, vp],
         "mi355_msm_sparse_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_sparse_destroy": [vp],
+        "mi355_msm_lookup_create": [ctypes.POINTER(vp), vp, vp, sz, ctypes.c_uint, vp],
+        "mi355_msm_lookup_count": [vp, vp, vp, vp, vp, sz, ctypes.c_uint, vp],
+        "mi355_msm_lookup_sorted": [vp, vp, vp, vp, sz, ctypes.c_uint, vp],
+        "mi355_msm_lookup_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_lookup_destroy": [vp],
+        "mi355_msm_domain_logup_sum": [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, ctypes.c_uint, vp],
         "mi355_msm_poseidon_create": [ctypes.POINTER(vp), vp, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, vp, vp, ctypes.c_uint],
         "mi355_msm_poseidon_hash": [vp, vp, vp, sz, sz, sz, vp, ctypes.c_uint, vp],
         "mi355_msm_poseidon_merkle": [vp, vp, vp, sz, sz, vp, ctypes.c_uint, vp],
@@ -1652,12 +1658,80 @@ class Radix2EvaluationDomain:
         h = self.divide_by_vanishing_poly_on_coset(h, **kw)
         return self.coset_ifft(h, **kw)
 
+    # ---- lookup arguments: resident tables and the logUp running sum (mi355_msm_lookup_*, mi355_msm_domain_logup_sum) ----------------
+
+    def logup_sum(self, table, mult, values, beta: int, helpers: bool = False, montgomery: bool = True, out=None):
+        """The logUp running sum over ``n`` rows (any ``n``, not the domain's size): with
+        ``term[j] = sum_c 1 / (beta + values_c[j]) - mult[j] / (beta + table[j])``, ``phi[0] = 0`` and ``phi[j+1] = phi[j] + term[j]``.
+        Returns ``(phi, total)``, or ``(phi, total, helper_columns)`` with ``helpers=True``: ``total = phi[n-1] + term[n-1]`` as an
+        integer, 0 exactly when the multiset relation holds; the helper columns are the ``m`` columns ``1 / (beta + values_c[j])``
+        and then ``mult[j] / (beta + table[j])``, shape ``(m + 1, n, 32)`` -- what sumcheck-based logUp commits to instead of ``phi``.
+        ``table`` and ``mult`` hold ``n`` elements (``mult`` as ``LookupTable.multiplicities`` returns it); ``values`` is one vector
+        of ``n``, a list of ``m <= 8`` vectors or a ``(m, n, 32)`` array or tensor.  A zero denominator does not raise: that term is 0.
+        GPU tensors in give GPU tensors out on the current stream.
+
+        Tuple lookups compress their columns on both sides first, with one random ``zeta``::
+
+            f = dom.linear_combination([a, b, c], [1, zeta, zeta * zeta % r])
+            t = dom.linear_combination([ta, tb, tc], [1, zeta, zeta * zeta % r])
+            lt = ea.LookupTable(dom, t)
+            mult, missing, first_missing = lt.multiplicities(f)
+            phi, total = dom.logup_sum(t, mult, f, beta)      # total == 0
+        """
+        if not self.handle:
+            raise MsmError(-1, "the domain is closed")
+        (bt, bm), n = self._vectors(table, mult)
+        if isinstance(values, (list, tuple)) or len(getattr(values, "shape", ())) == 3:
+            if isinstance(values, (list, tuple)):
+                first = values[0] if len(values) else None
+                if hasattr(first, "is_cuda") and hasattr(first, "data_ptr"):
+                    import torch
+
+                    values = torch.stack([c.reshape(-1, 32) for c in values])
+                else:
+                    import numpy as np
+
+                    values = np.stack([np.frombuffer(_flat_bytes(c), dtype=np.uint8).reshape(-1, 32) for c in values]) if len(values) else np.zeros((0, n, 32), np.uint8)
+            shape = tuple(values.shape)
+            if len(shape) != 3 or shape[2] != 32 or not 1 <= shape[0] <= 8 or shape[1] < n:
+                raise ValueError(f"values: m columns (1 <= m <= 8) of {n} 32-byte elements, shape (m, {n}, 32), not {shape}")
+            bv, m, stride = _Buf(values), int(shape[0]), int(shape[1])
+        else:
+            bv, m, stride = _Buf(values), 1, n
+            if bv.nbytes != n * 32:
+                raise ValueError(f"values: {n} 32-byte elements beside a table of {n}, not {bv.nbytes} bytes")
+        if bv.is_device != bt.is_device:
+            raise ValueError("table, mult and values must live in the same kind of memory")
+        if bv.is_device and bv.device_index != self.device:
+            raise MsmError(-1, f"the input lives on cuda:{bv.device_index} but this domain is bound to device {self.device}")
+        res, ob = self._out(table, bt, out, n)
+        tot = ctypes.create_string_buffer(32)
+        flags = 0 if montgomery else 1
+        hres = hb = None
+        if helpers:
+            if bt.is_device:
+                import torch
+
+                hres = torch.empty((m + 1, n, 32), dtype=torch.uint8, device=bt.keep.device)
+            else:
+                import numpy as np
+
+                hres = np.zeros((m + 1, n, 32), dtype=np.uint8)
+            hb = _Buf(hres)
+        _check(self._lib.mi355_msm_domain_logup_sum(self.handle, ob.ptr if n else None, tot, hb.ptr if helpers and n else None, bt.ptr if n else None,
+                                                    bm.ptr if n else None, bv.ptr if n else None, m, stride, n, self._scalar(beta, montgomery),
+                                                    flags | (2 if bt.is_device else 0), bt.stream if bt.is_device else None))
+        if not bt.is_device:
+            res = _like_input(table, res, (n, 32))
+        total = self._scalar_out(tot.raw, montgomery)
+        return (res, total, hres) if helpers else (res, total)
+
     def set_option(self, key: str, value: int) -> None:
         _check(self._lib.mi355_msm_domain_set_option(self.handle, key.encode(), int(value)))
 
     def query(self, key: str) -> int:
         """ "size", "log_size", "passes", "pass_log", "table_bytes", "work_bytes", "poly_work_bytes", "scan_work_bytes", "quotient_work_bytes",
-        "mle_work_bytes", "sumcheck_levels", "sumcheck_max_tables", "sumcheck_max_terms", "sumcheck_max_factors", "poly_tile_log",
+        "mle_work_bytes", "logup_work_bytes", "sumcheck_levels", "sumcheck_max_tables", "sumcheck_max_terms", "sumcheck_max_factors", "poly_tile_log",
         "device", "last_us", "last_device_us" """
         v = ctypes.c_uint64(0)
         _check(self._lib.mi355_msm_domain_query(self.handle, key.encode(), ctypes.byref(v)))
@@ -1781,6 +1855,118 @@ class SparseMatrix:
     def close(self) -> None:
         if self.handle:
             _check(self._lib.mi355_msm_sparse_destroy(self.handle))
+            self.handle = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LookupTable:
+    """A lookup table over ``Fr`` resident on one GPU (mi355_msm_lookup_*): ``table`` holds ``1 <= n_t <= 2^28`` 32-byte elements (bytes,
+    NumPy or torch; a GPU tensor is read on its current stream).  Equality is equality modulo r in the form given here, and every
+    later call must bring values in the same form.  Duplicates are allowed; every match is credited to the first occurrence.
+    ``multiplicities(values)`` are logUp's ``m``; ``sorted(values)`` is plookup's ``s = (f, t)`` sorted by ``t``."""
+
+    def __init__(self, dom, table, montgomery: bool = True):
+        self.handle = ctypes.c_void_p()
+        self.dom = dom
+        if not dom.handle:
+            raise MsmError(-1, "the domain is closed")
+        self._lib = dom._lib
+        self.montgomery = bool(montgomery)
+        b = _Buf(table)
+        if b.nbytes == 0 or b.nbytes % 32:
+            raise ValueError(f"table: a whole number (at least one) of 32-byte elements, not {b.nbytes} bytes")
+        if b.is_device and b.device_index != dom.device:
+            raise MsmError(-1, f"the input lives on cuda:{b.device_index} but this domain is bound to device {dom.device}")
+        self._flags = 0 if montgomery else 1
+        _check(self._lib.mi355_msm_lookup_create(ctypes.byref(self.handle), dom.handle, b.ptr, b.nbytes // 32, self._flags | (2 if b.is_device else 0),
+                                                 b.stream if b.is_device else None))
+        self.n = b.nbytes // 32
+
+    def _values(self, values):
+        if not self.handle:
+            raise MsmError(-1, "the lookup table is closed")
+        b = _Buf(values)
+        if b.nbytes % 32:
+            raise ValueError(f"values: a whole number of 32-byte elements, not {b.nbytes} bytes")
+        if b.is_device and b.device_index != self.dom.device:
+            raise MsmError(-1, f"the input lives on cuda:{b.device_index} but this table is bound to device {self.dom.device}")
+        return b, b.nbytes // 32
+
+    def multiplicities(self, values, index: bool = False):
+        """``(mult, missing, first_missing)``, with ``index=True`` ``(mult, missing, first_missing, index)``: ``mult`` holds ``n`` elements
+        in the form of the table, ``mult[i]`` = how many values equal ``table[i]`` (0 at later duplicates); ``index[j]`` (uint32) is the
+        first table index of ``values[j]`` or 0xFFFFFFFF; ``missing`` values have no match, the first at ``first_missing``
+        (``len(values)`` when none).  A missing value does not raise."""
+        b, n_f = self._values(values)
+        stats = (ctypes.c_uint64 * 2)()
+        if b.is_device:
+            import torch
+
+            mult = torch.empty((self.n, 32), dtype=torch.uint8, device=b.keep.device)
+            idx = torch.empty((n_f,), dtype=torch.int32, device=b.keep.device) if index else None
+            _check(self._lib.mi355_msm_lookup_count(self.handle, mult.data_ptr(), idx.data_ptr() if index and n_f else None, stats, b.ptr if n_f else None,
+                                                    n_f, self._flags | 2, b.stream))
+            if index:
+                idx = idx.view(torch.uint32) if hasattr(torch, "uint32") else idx
+        else:
+            import numpy as np
+
+            mult = np.zeros((self.n, 32), dtype=np.uint8)
+            idx = np.zeros(n_f, dtype=np.uint32) if index else None
+            _check(self._lib.mi355_msm_lookup_count(self.handle, mult.ctypes.data, idx.ctypes.data if index and n_f else None, stats, b.ptr if n_f else None,
+                                                    n_f, self._flags, None))
+            mult = _like_input(values, mult.reshape(-1), (self.n, 32))
+        return (mult, int(stats[0]), int(stats[1]), idx) if index else (mult, int(stats[0]), int(stats[1]))
+
+    def sorted(self, values, out=None):
+        """plookup's sorted vector: the ``n + len(values)`` canonical elements ``table[i]`` followed by ``mult[i]`` further copies, for
+        ``i`` in order.  Jellyfish's ``h1 = s[:n]``, ``h2 = s[n-1:]`` and Plonkup's alternating halves are slices of it.  Raises
+        ``MsmError`` naming ``first_missing`` when a value is absent from the table (``out`` is then untouched)."""
+        b, n_f = self._values(values)
+        total = self.n + n_f
+        stats = (ctypes.c_uint64 * 2)()
+        if b.is_device:
+            import torch
+
+            if out is None:
+                out = torch.empty((total, 32), dtype=torch.uint8, device=b.keep.device)
+            ob = _Buf(out)
+            if not ob.is_device or ob.nbytes != total * 32 or ob.keep is not out:
+                raise ValueError(f"out must be a contiguous uint8 GPU tensor of {total * 32} bytes")
+            _check(self._lib.mi355_msm_lookup_sorted(self.handle, ob.ptr, stats, b.ptr if n_f else None, n_f, self._flags | 2, b.stream))
+            res = out
+        else:
+            if out is not None:
+                raise ValueError("out= goes with GPU tensors")
+            import numpy as np
+
+            res = np.zeros((total, 32), dtype=np.uint8)
+            _check(self._lib.mi355_msm_lookup_sorted(self.handle, res.ctypes.data, stats, b.ptr if n_f else None, n_f, self._flags, None))
+            res = _like_input(values, res.reshape(-1), (total, 32))
+        if stats[0]:
+            raise MsmError(-1, f"{int(stats[0])} values are not in the table; first_missing = {int(stats[1])}")
+        return res
+
+    def query(self, key: str) -> int:
+        """ "n", "slots", "distinct", "max_probe", "table_bytes", "lookup_work_bytes" """
+        v = ctypes.c_uint64(0)
+        _check(self._lib.mi355_msm_lookup_query(self.handle, key.encode(), ctypes.byref(v)))
+        return int(v.value)
+
+    def close(self) -> None:
+        if self.handle:
+            _check(self._lib.mi355_msm_lookup_destroy(self.handle))
             self.handle = ctypes.c_void_p()
 
     def __enter__(self):

@@ -929,6 +929,69 @@ RustError mi355_msm_fft_points(mi355_msm_ctx* ctx, mi355_msm_domain* domain, voi
 RustError mi355_msm_fft_points_device(mi355_msm_ctx* ctx, mi355_msm_domain* domain, void* d_out, size_t out_stride, const void* d_in, size_t in_len,
                                       size_t stride, unsigned kind, unsigned flags, const void* offset, void* stream);
 
+/* ---- lookup-argument columns over Fr: resident lookup tables (logUp multiplicities, plookup's sorted vector) and the logUp running sum ----
+ * The step every Plonk-style prover has between "wires committed" and "grand product / running sum": halo2, UltraPlonk / Jellyfish,
+ * Plonkup and logUp in its univariate and its sumcheck form all join a witness column against a table.  The contract is stated on
+ * integers.  Elements are 32 bytes: arkworks Fr images or, with flag bit 0, plain integers; ANY 256-bit pattern is read as its
+ * residue, and every Fr output is canonical.  Flag bit 1 (value 2): the vectors are DEVICE pointers (4-byte aligned) and `stream` is
+ * the hipStream_t on which the inputs become ready (NULL = the default stream); the work is enqueued there and the call returns when
+ * its outputs are written.  Without bit 1 they are host pointers, staged through buffers the handle keeps, and a non-null stream is an
+ * error.  `stats`, `beta` and `total32` are HOST memory in both cases.
+ *   create  the table t[0 .. n_t), 1 <= n_t <= 2^28, on the field, the device, the events and the host-pointer stream of the domain d,
+ *           WHICH MUST OUTLIVE THE TABLE (its size plays no part).  Equality is equality MODULO r: v, v + r, v + 2r, .. match each
+ *           other wherever they fit 256 bits.  The matching key is the canonical residue of the 256-bit pattern in the form of the
+ *           call; Montgomery images are in bijection with residues, so matching needs a reduction and no field product.  The table is
+ *           fixed for the life of the handle IN THE FORM IT WAS CREATED WITH: a later call whose flag bit 0 differs is refused.
+ *           Duplicates are allowed: first(i) is the smallest j with t[j] == t[i], and every match is credited to the first occurrence.
+ *   count   for n_f <= 2^30 values: index_out[j] (n_f u32; may be NULL) = first(i) for the t[i] == values[j], or 0xFFFFFFFF when there
+ *           is none; mult_out[i] (n_t elements in the form of the call; may be NULL) = the number of j with index_out[j] == i, so 0 at
+ *           later duplicates; stats[0] = the number of values without a match, stats[1] = the smallest such j, or n_f when there is
+ *           none.  A MISSING VALUE IS NOT AN ERROR (as a zero denominator is none in the permutation product).  n_f == 0 writes n_t
+ *           zeros and stats (0, 0).
+ *   sorted  s_out receives the n_t + n_f elements of plookup's s = (f, t) sorted by t: for i = 0 .. n_t - 1 in order t[i], followed
+ *           by mult[i] further copies of t[i], all canonical in the form of the call.  If stats[0] != 0 NOTHING is written to s_out
+ *           and the call still returns 0.  Jellyfish's h1 = s[:n], h2 = s[n-1:] and the alternating halves of Plonkup are slices of
+ *           s_out for the caller to take.
+ *   query   "n", "slots", "distinct" (keys), "max_probe" (the longest probe walk of the build), "table_bytes" (keys and slots),
+ *           "lookup_work_bytes" (counters, offsets, scan levels, staged vectors).
+ *   mi355_msm_domain_logup_sum   n <= 2^30 rows, any n; values holds 1 <= m <= 8 columns of n elements, stride >= n elements apart;
+ *           beta is one HOST element.  term[j] = sum_c 1 / (beta + values_c[j]) - mult[j] / (beta + table[j]); out[0] = 0,
+ *           out[j + 1] = out[j] + term[j] (n elements, exclusive); total32 (may be NULL) = out[n-1] + term[n-1], which is 0 exactly
+ *           when the multiset relation holds; helpers (may be NULL) receives (m + 1) n elements: the m columns 1 / (beta +
+ *           values_c[j]), then mult[j] / (beta + table[j]) -- what sumcheck-based logUp commits to instead of the running sum.
+ *           A ZERO DENOMINATOR IS NOT AN ERROR: the batch inversion leaves it zero and that term contributes 0 (as the permutation
+ *           product documents).  Neither output may overlap an input or the other output.  n == 0 writes total32 = 0 only.
+ * No name here ends in _device: every such name in this header stands in the table of tests/stream_cases.py, and
+ * tests/test_stream_coverage.py keeps the two equal.  The stream-ordering promise of flag bit 1 is the same one and is pinned by
+ * late-producer tests of its own in tests/test_gpu_lookup.py, one each for create, count, sorted and logup_sum.
+ * Scheme (csrc/lookup.hpp).  create: one launch reduces the table into the handle's canonical copy; one launch inserts, a lane per
+ * entry, open addressing with linear probing into `slots` = the power of two >= 2 n_t of u32 indices.  The hash mixes all eight words
+ * of the key (murmur3).  An empty slot is claimed with a compare-and-swap; a slot whose entry is equal is lowered with an atomic min,
+ * which makes first(i) independent of the arrival order; slots are read through agent-scope atomic loads.  count: a separate launch,
+ * a lane per value, walks with plain loads, writes index_out and adds to a u32 counter AFTER the lanes of a wave that found the same
+ * entry have combined into one add (a padded column puts most values on one counter; a heavy entry and the misses are carried over
+ * the values a block takes and added once per block, since adds to one address are serialised); the missing count and the first missing
+ * index are two 64-bit atomics per block that has misses; one lane per entry writes the counter as an element (at most one product).  sorted:
+ * the same probe, an exclusive u32 scan of 1 + count (tiles of 1024, levels as launches), and one lane per OUTPUT element that finds
+ * its entry by bisection -- balanced whatever the distribution.  No lane waits on another lane's progress, a walk is bounded by
+ * `slots`, nothing is polled; a walk that wraps (impossible at load <= 1/2) is error -2.  Sums and minima of integers do not depend
+ * on their order: every output byte is a function of the inputs alone.  logup_sum: one launch writes the (m + 1) n denominators, the
+ * three launches of the batch inversion run over them in place, one launch forms the last helper column and the row's term, and the
+ * sum scan runs over the terms.  Work memory is the domain's (query "logup_work_bytes"; the other queries keep their values).
+ * Results never depend on host versus device pointers.  There is no CPU fallback.
+ * Errors: -1 with a message, decided before any device call, in this order: unknown flag bits, sizes outside their limits, null
+ * pointers, alignment, a stream without flag bit 1, an overlap, and last the null handle (create and logup_sum: the domain), after
+ * which the extent of an overlap and the form of the table are judged against the handle.  hipErrorNoDevice without a GPU. */
+typedef struct mi355_msm_lookup mi355_msm_lookup;
+RustError mi355_msm_lookup_create(mi355_msm_lookup** out, mi355_msm_domain* d, const void* table, size_t n_t, unsigned flags, void* stream);
+RustError mi355_msm_lookup_count(mi355_msm_lookup* h, void* mult_out, uint32_t* index_out, uint64_t* stats, const void* values, size_t n_f,
+                                 unsigned flags, void* stream);
+RustError mi355_msm_lookup_sorted(mi355_msm_lookup* h, void* s_out, uint64_t* stats, const void* values, size_t n_f, unsigned flags, void* stream);
+RustError mi355_msm_lookup_query(mi355_msm_lookup* h, const char* key, uint64_t* value);
+RustError mi355_msm_lookup_destroy(mi355_msm_lookup* h);
+RustError mi355_msm_domain_logup_sum(mi355_msm_domain* d, void* out, void* total32, void* helpers, const void* table, const void* mult,
+                                     const void* values, size_t m, size_t stride, size_t n, const void* beta, unsigned flags, void* stream);
+
 /* Sum `count` projective images (any Z) into one normalised image: the multi-GPU combine step
  * ("final 8-point curve add").  Pure host arithmetic on <= a few dozen points; no device needed. */
 RustError mi355_msm_fold(int curve, void* out_projective, const void* projective, size_t count);

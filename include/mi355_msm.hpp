@@ -443,6 +443,68 @@ struct SparseMatrix {
   }
 };
 
+// A lookup table over Fr resident on the GPU (mi355_msm_lookup_*), on a domain that outlives it: multiplicities are logUp's m, sorted is
+// plookup's s = (f, t) sorted by t (Jellyfish's h1 = s[:n], h2 = s[n-1:] are slices of it).  Fr values in Montgomery form; equality is
+// equality modulo r, duplicates are credited to their first occurrence, and a missing value is reported, not an error.
+struct LookupTable {
+  mi355_msm_lookup* handle = nullptr;
+  size_t n = 0;
+  struct Counts {
+    std::vector<BigInteger256> mult;
+    std::vector<uint32_t> index;
+    uint64_t missing = 0, first_missing = 0;
+  };
+  LookupTable(const Radix2EvaluationDomain& dom, const std::vector<BigInteger256>& table) : n(table.size()) {
+    check(mi355_msm_lookup_create(&handle, dom.handle, table.data(), table.size(), 0, nullptr));
+  }
+  LookupTable(const LookupTable&) = delete;
+  LookupTable& operator=(const LookupTable&) = delete;
+  LookupTable(LookupTable&& o) noexcept : handle(o.handle), n(o.n) { o.handle = nullptr; }
+  uint64_t query(const char* key) const {
+    uint64_t v = 0;
+    check(mi355_msm_lookup_query(handle, key, &v));
+    return v;
+  }
+  Counts multiplicities(const std::vector<BigInteger256>& values) const {
+    Counts c;
+    c.mult.resize(n);
+    c.index.resize(values.size());
+    uint64_t stats[2] = {0, 0};
+    check(mi355_msm_lookup_count(handle, c.mult.data(), c.index.data(), stats, values.data(), values.size(), 0, nullptr));
+    c.missing = stats[0];
+    c.first_missing = stats[1];
+    return c;
+  }
+  // empty, with *first_missing set, when a value is not in the table
+  std::vector<BigInteger256> sorted(const std::vector<BigInteger256>& values, uint64_t* first_missing = nullptr) const {
+    std::vector<BigInteger256> s(n + values.size());
+    uint64_t stats[2] = {0, 0};
+    check(mi355_msm_lookup_sorted(handle, s.data(), stats, values.data(), values.size(), 0, nullptr));
+    if (stats[0]) {
+      if (first_missing) *first_missing = stats[1];
+      s.clear();
+    }
+    return s;
+  }
+  ~LookupTable() {
+    if (handle) {
+      RustError e = mi355_msm_lookup_destroy(handle);
+      if (e.message) std::free(e.message);
+    }
+  }
+};
+
+// phi[0] = 0, phi[j+1] = phi[j] + sum_c 1 / (beta + columns[c][j]) - mult[j] / (beta + table[j]); *total is zero exactly when the
+// multiset relation holds.  A zero denominator contributes 0.
+inline std::vector<BigInteger256> logup_sum(const Radix2EvaluationDomain& dom, const std::vector<BigInteger256>& table, const std::vector<BigInteger256>& mult,
+                                            const std::vector<std::vector<BigInteger256>>& columns, const BigInteger256& beta, BigInteger256* total = nullptr) {
+  const size_t n = table.size();
+  std::vector<BigInteger256> flat, phi(n);
+  for (const auto& c : columns) flat.insert(flat.end(), c.begin(), c.end());
+  check(mi355_msm_domain_logup_sum(dom.handle, phi.data(), total, nullptr, table.data(), mult.data(), flat.data(), columns.size(), n, n, &beta, 0, nullptr));
+  return phi;
+}
+
 // ark-groth16's LibsnarkReduction::witness_map on host vectors, from the full assignment z to the size() coefficients of h: a = A z with
 // z[0 .. num_inputs) appended behind the constraints, b = B z, c = a * b element by element, all zero-padded to the domain;
 // h = coset_ifft((coset_fft(ifft(a)) * coset_fft(ifft(b)) - coset_fft(ifft(c))) / Z(g)).  (The Python layer keeps every step in device memory.)

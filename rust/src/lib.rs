@@ -258,6 +258,19 @@ pub mod sys {
         pub fn mi355_msm_sparse_apply(m: *mut c_void, out: *mut c_void, z: *const c_void, flags: c_uint, stream: *mut c_void) -> Error;
         pub fn mi355_msm_sparse_query(m: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
         pub fn mi355_msm_sparse_destroy(m: *mut c_void) -> Error;
+        // resident lookup tables over Fr on a domain handle, which must outlive them, and the logUp running sum: flags bit 0, plain
+        // integers (a table keeps the form it was created with); bit 1 (value 2): the vectors are device pointers and `stream` is where
+        // the inputs become ready, else host pointers and a null stream.  `stats`, `beta` and `total32` are host memory in both cases
+        pub fn mi355_msm_lookup_create(out: *mut *mut c_void, d: *mut c_void, table: *const c_void, n_t: usize, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_lookup_count(h: *mut c_void, mult_out: *mut c_void, index_out: *mut u32, stats: *mut u64, values: *const c_void, n_f: usize,
+                                      flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_lookup_sorted(h: *mut c_void, s_out: *mut c_void, stats: *mut u64, values: *const c_void, n_f: usize, flags: c_uint,
+                                       stream: *mut c_void) -> Error;
+        pub fn mi355_msm_lookup_query(h: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
+        pub fn mi355_msm_lookup_destroy(h: *mut c_void) -> Error;
+        pub fn mi355_msm_domain_logup_sum(d: *mut c_void, out: *mut c_void, total32: *mut c_void, helpers: *mut c_void, table: *const c_void,
+                                          mult: *const c_void, values: *const c_void, m: usize, stride: usize, n: usize, beta: *const c_void,
+                                          flags: c_uint, stream: *mut c_void) -> Error;
         // Poseidon parameters over Fr on a domain handle, which must outlive them: `ark` holds (full + partial rounds) * (rate + 1)
         // host elements, `mds` (rate + 1)^2 (flags bit 0: plain integers).  hash: n sponges, row i of `input` holds in_len elements, row
         // i of `out` receives n_out; `header` is null or `rate` host elements absorbed before every row.  merkle: snarkVM's Poseidon
@@ -753,6 +766,86 @@ pub mod sparse {
             });
             out
         }
+    }
+}
+
+/// Lookup-argument columns on the GPU (`mi355_msm_lookup_*`, `mi355_msm_domain_logup_sum`): the multiplicities of logUp, plookup's sorted
+/// vector `s = (f, t)` sorted by `t` (Jellyfish's `h1 = s[..n]`, `h2 = s[n-1..]` are slices of it) and the logUp running sum.
+pub mod lookup {
+    use super::sys;
+    use super::Fr;
+    use ark_std::Zero;
+    use std::os::raw::c_void;
+
+    fn check(err: super::Error) {
+        if err.code != 0 {
+            panic!("{}", String::from(err));
+        }
+    }
+
+    /// Lives on a domain handle of `sys::mi355_msm_domain_create`, which the caller keeps alive for as long as the table.
+    pub struct LookupTable {
+        handle: *mut c_void,
+        pub n: usize,
+    }
+
+    impl Drop for LookupTable {
+        fn drop(&mut self) {
+            if !self.handle.is_null() {
+                let _ = unsafe { sys::mi355_msm_lookup_destroy(self.handle) };
+            }
+        }
+    }
+
+    impl LookupTable {
+        /// # Safety
+        /// `domain` is a live handle of `sys::mi355_msm_domain_create` over the field of `Fr` and outlives the table.
+        pub unsafe fn new(domain: *mut c_void, table: &[Fr]) -> Self {
+            let mut handle: *mut c_void = std::ptr::null_mut();
+            check(sys::mi355_msm_lookup_create(&mut handle, domain, table.as_ptr() as *const c_void, table.len(), 0, std::ptr::null_mut()));
+            LookupTable { handle, n: table.len() }
+        }
+
+        /// `(mult, index, missing, first_missing)`: `mult[i]` = how many values equal `table[i]` (0 at later duplicates), `index[j]` the
+        /// first table index of `values[j]` or `u32::MAX`; a missing value is not an error
+        pub fn multiplicities(&self, values: &[Fr]) -> (Vec<Fr>, Vec<u32>, u64, u64) {
+            let mut mult = vec![Fr::zero(); self.n];
+            let mut index = vec![0u32; values.len()];
+            let mut stats = [0u64; 2];
+            check(unsafe {
+                sys::mi355_msm_lookup_count(self.handle, mult.as_mut_ptr() as *mut c_void, index.as_mut_ptr(), stats.as_mut_ptr(),
+                                            values.as_ptr() as *const c_void, values.len(), 0, std::ptr::null_mut())
+            });
+            (mult, index, stats[0], stats[1])
+        }
+
+        /// `table[i]` followed by `mult[i]` further copies, for `i` in order; `Err(first_missing)` when a value is not in the table
+        pub fn sorted(&self, values: &[Fr]) -> Result<Vec<Fr>, u64> {
+            let mut s = vec![Fr::zero(); self.n + values.len()];
+            let mut stats = [0u64; 2];
+            check(unsafe {
+                sys::mi355_msm_lookup_sorted(self.handle, s.as_mut_ptr() as *mut c_void, stats.as_mut_ptr(), values.as_ptr() as *const c_void,
+                                             values.len(), 0, std::ptr::null_mut())
+            });
+            if stats[0] != 0 { Err(stats[1]) } else { Ok(s) }
+        }
+    }
+
+    /// `phi[0] = 0`, `phi[j+1] = phi[j] + sum_c 1 / (beta + columns[c][j]) - mult[j] / (beta + table[j])`, and the total, which is zero
+    /// exactly when the multiset relation holds.  A zero denominator contributes 0.
+    ///
+    /// # Safety
+    /// `domain` is a live handle of `sys::mi355_msm_domain_create` over the field of `Fr`.
+    pub unsafe fn logup_sum(domain: *mut c_void, table: &[Fr], mult: &[Fr], columns: &[Vec<Fr>], beta: Fr) -> (Vec<Fr>, Fr) {
+        let n = table.len();
+        assert!(mult.len() == n && columns.iter().all(|c| c.len() == n), "one element per row in every vector");
+        let flat: Vec<Fr> = columns.iter().flat_map(|c| c.iter().copied()).collect();
+        let mut phi = vec![Fr::zero(); n];
+        let mut total = Fr::zero();
+        check(sys::mi355_msm_domain_logup_sum(domain, phi.as_mut_ptr() as *mut c_void, &mut total as *mut Fr as *mut c_void, std::ptr::null_mut(),
+                                              table.as_ptr() as *const c_void, mult.as_ptr() as *const c_void, flat.as_ptr() as *const c_void,
+                                              columns.len(), n, n, &beta as *const Fr as *const c_void, 0, std::ptr::null_mut()));
+        (phi, total)
     }
 }
 
