@@ -37,6 +37,8 @@ from .msm import (  # noqa: F401
     Radix2EvaluationDomain,
     SparseMatrix,
     LookupTable,
+    Expr,
+    GateProgram,
     Poseidon,
     PoseidonMerkleTree,
     poseidon_parameters,

@@ -2657,3 +2657,76 @@ int ht_logup_sum(int field, unsigned tile_log, unsigned flags, const uint8_t* ta
   return POLY_FIELD(t_logup_sum, tile_log, flags, table, mult, values, m, stride, n, beta, out, total32, helpers);
 }
 }
+
+// ---- compiled expressions (expr.hpp): the compiler, and the interpreter row by row with one lane's slots in a plain array -----------
+#include "expr.hpp"
+
+template <class FR>
+static int t_expr(unsigned flags, const uint32_t* nodes, uint64_t n_nodes, const uint8_t* consts, uint64_t n_consts, uint64_t n_chal, uint64_t n_cols,
+                  const uint8_t* const* cols, const uint64_t* lens, uint64_t len, uint64_t rot_step, const uint8_t* challenges, uint8_t* out, uint64_t* info,
+                  char* msg, uint64_t msg_len) {
+  const bool normal = (flags & kExprNormal) != 0;
+  ExprProgram pr;
+  if (!expr_check_dag(nodes, n_nodes, n_consts, n_chal, n_cols, msg, msg_len)) return -1;
+  const bool ok = expr_compile(pr, nodes, n_nodes, n_consts, n_chal, n_cols, expr_store_limit<FR>(), msg, msg_len);
+  if (info) {
+    info[0] = pr.n_nodes;
+    info[1] = pr.ninstr();
+    info[2] = pr.slots;
+    info[3] = pr.products;
+    info[4] = pr.reduces;
+    info[5] = expr_lds_bytes(pr.slots);
+    info[6] = pr.used_cols;
+    info[7] = pr.rot0_only;
+  }
+  if (!ok) return -1;
+  if (!out || len == 0) return 0;
+  for (uint64_t j = 0; j < n_cols; j++)
+    if (lens[j] == 0 || len % lens[j]) return -3;
+  std::vector<uint32_t> cw(n_consts * 8 + 1), hw(n_chal * 8 + 1), dst(len * 8), slots((size_t)pr.slots * 8 + 1);
+  std::vector<std::vector<uint32_t>> colw(n_cols);
+  auto words = [&](uint32_t* w8, const uint8_t* b32) {
+    Fr x;
+    uint32_t w[8];
+    poly_scalar<FR>(x, b32, normal);
+    fr_pack(w, x);
+    memcpy(w8, w, 32);
+  };
+  for (uint64_t k = 0; k < n_consts; k++) words(cw.data() + k * 8, consts + k * 32);
+  for (uint64_t k = 0; k < n_chal; k++) words(hw.data() + k * 8, challenges + k * 32);
+  for (uint64_t j = 0; j < n_cols; j++) {
+    colw[j].resize(lens[j] * 8);
+    memcpy(colw[j].data(), cols[j], lens[j] * 32);
+  }
+  std::vector<ExprColRef> refs(pr.refs.size() + 1);
+  for (size_t k = 0; k < pr.refs.size(); k++)
+    refs[k] = ExprColRef{colw[pr.refs[k].first].data(), (uint32_t)lens[pr.refs[k].first], expr_shift(pr.refs[k].second, rot_step, len)};
+  ExprRun p{};
+  p.prog = pr.code.data();
+  p.refs = refs.data();
+  p.consts = cw.data();
+  p.chals = hw.data();
+  p.out = dst.data();
+  p.ninstr = pr.ninstr();
+  p.len = (uint32_t)len;
+  p.normal = normal ? 1u : 0u;
+  const ExprSlots<1> st{slots.data()};
+  for (uint64_t i = 0; i < len; i++) expr_row<FR>(st, p, (uint32_t)i);
+  memcpy(out, dst.data(), len * 32);
+  return 0;
+}
+
+extern "C" {
+// mi355_msm_expr_create + _run on the host: flags bit 0, plain integers (constants, challenges, columns and output alike).  info (8: nodes,
+// instructions, slots, products, reduces, lds_bytes, the columns read, those read at rotation 0 only) may be NULL; out NULL or len 0: the
+// compiler alone.  -1 with msg set: what create refuses.
+int ht_expr(int field, unsigned flags, const uint32_t* nodes, uint64_t n_nodes, const uint8_t* consts, uint64_t n_consts, uint64_t n_chal, uint64_t n_cols,
+            const uint8_t* const* cols, const uint64_t* lens, uint64_t len, uint64_t rot_step, const uint8_t* challenges, uint8_t* out, uint64_t* info,
+            char* msg, uint64_t msg_len) {
+  if ((flags & ~kExprNormal) || !nodes || !msg || msg_len < 64 || len > ((uint64_t)1 << 22) || (n_consts && !consts)) return -2;
+  if (out && len && ((n_cols && (!cols || !lens)) || (n_chal && !challenges))) return -2;
+  msg[0] = 0;
+  return POLY_FIELD(t_expr, flags, nodes, n_nodes, consts, n_consts, n_chal, n_cols, cols, lens, len, rot_step, challenges, out, info, msg, msg_len);
+}
+unsigned ht_expr_max_slots(void) { return EXPR_MAX_SLOTS; }
+}

@@ -2988,3 +2988,4 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 #include "msm_h2c.hpp"
 #include "msm_gfft.hpp"
 #include "msm_lookup.hpp"
+#include "msm_expr.hpp"

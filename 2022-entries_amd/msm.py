@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 from typing import List, Optional, Sequence
 
 CURVE_IDS = {"bls12_377_g1": 0, "bls12_381_g1": 1, "bls12_377_g2": 2, "bls12_381_g2": 3}
@@ -169,6 +170,10 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_lookup_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
         "mi355_msm_lookup_destroy": [vp],
         "mi355_msm_domain_logup_sum": [vp, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, ctypes.c_uint, vp],
+        "mi355_msm_expr_create": [ctypes.POINTER(vp), vp, vp, sz, vp, sz, sz, sz, ctypes.c_uint],
+        "mi355_msm_expr_run": [vp, vp, vp, vp, sz, sz, sz, vp, sz, ctypes.c_uint, vp],
+        "mi355_msm_expr_query": [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint64)],
+        "mi355_msm_expr_destroy": [vp],
         "mi355_msm_poseidon_create": [ctypes.POINTER(vp), vp, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, vp, vp, ctypes.c_uint],
         "mi355_msm_poseidon_hash": [vp, vp, vp, sz, sz, sz, vp, ctypes.c_uint, vp],
         "mi355_msm_poseidon_merkle": [vp, vp, vp, sz, sz, vp, ctypes.c_uint, vp],
@@ -1477,6 +1482,12 @@ class Radix2EvaluationDomain:
         _check(self._lib.mi355_msm_domain_linear_combination(self.handle, ob.ptr if n else None, ptrs, lv, cb, m, flags))
         return _like_input(cols[lens.index(n)], res, (n, 32))
 
+    def compile_expression(self, expr, ncols: int):
+        """An ``Expr`` over ``ncols`` columns, compiled once for this domain's field and device into a ``GateProgram``: one launch of
+        ``prog.run(cols, ...)`` then evaluates it for every row, reading each column where it lies.  Raises ``MsmError`` when the
+        expression needs more slots than the kernel has (the message names ``S`` and the limit): split the sum over an output column."""
+        return GateProgram(self, expr, ncols)
+
     # ---- dense multilinear extensions and sumcheck prover rounds (mi355_msm_domain_mle_*, _sumcheck_round) --------------------------
 
     def _point(self, point, montgomery):
@@ -1967,6 +1978,230 @@ class LookupTable:
     def close(self) -> None:
         if self.handle:
             _check(self._lib.mi355_msm_lookup_destroy(self.handle))
+            self.handle = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- custom-gate expressions over Fr columns with rotations (mi355_msm_expr_*) ------------------------------------------------------------
+
+class Expr:
+    """A polynomial expression over columns of ``Fr``, built with ``+ - * **`` (a small non-negative integer exponent) and unary minus
+    from the leaves ``Expr.col(j, rot=0)`` (column ``j`` at row ``i + rot * rot_step``), ``Expr.const(v)`` (an integer, fixed when the
+    expression is compiled) and ``Expr.challenge(k)`` (given at every run).  Integers mix in as constants.  Equal sub-expressions are
+    ONE object (hash-consing; ``a + b`` and ``b + a`` alike), so a shared term is evaluated once per row.  ``nodes()`` is the flat
+    DAG ``mi355_msm_expr_create`` takes."""
+
+    COL, CONST, CHAL, ADD, SUB, MUL, NEG, SQR = range(8)
+    __slots__ = ("op", "a", "b", "serial", "__weakref__")
+    _interned = weakref.WeakValueDictionary()
+    _count = 0
+
+    def __init__(self, op, a, b):
+        raise TypeError("build expressions from Expr.col, Expr.const and Expr.challenge")
+
+    @classmethod
+    def _make(cls, op, a, b=None):
+        leaf = op <= cls.CHAL
+        if op in (cls.ADD, cls.MUL) and b.serial < a.serial:
+            a, b = b, a
+        key = (op, a, b) if leaf else (op, a.serial, b.serial if b is not None else -1)
+        e = cls._interned.get(key)
+        if e is None:
+            e = object.__new__(cls)
+            e.op, e.a, e.b = op, a, b
+            Expr._count += 1
+            e.serial = Expr._count
+            cls._interned[key] = e
+        return e
+
+    @classmethod
+    def col(cls, j: int, rot: int = 0):
+        j, rot = int(j), int(rot)
+        if j < 0:
+            raise ValueError("a column index is not negative")
+        return cls._make(cls.COL, j, rot)
+
+    @classmethod
+    def const(cls, v: int):
+        return cls._make(cls.CONST, int(v), None)
+
+    @classmethod
+    def challenge(cls, k: int):
+        k = int(k)
+        if k < 0:
+            raise ValueError("a challenge index is not negative")
+        return cls._make(cls.CHAL, k, None)
+
+    @classmethod
+    def _of(cls, x):
+        if isinstance(x, Expr):
+            return x
+        if isinstance(x, int) and not isinstance(x, bool):
+            return cls.const(x)
+        return None
+
+    def __add__(self, o):
+        o = Expr._of(o)
+        return NotImplemented if o is None else Expr._make(Expr.ADD, self, o)
+
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        o = Expr._of(o)
+        return NotImplemented if o is None else Expr._make(Expr.SUB, self, o)
+
+    def __rsub__(self, o):
+        o = Expr._of(o)
+        return NotImplemented if o is None else Expr._make(Expr.SUB, o, self)
+
+    def __mul__(self, o):
+        o = Expr._of(o)
+        if o is None:
+            return NotImplemented
+        return Expr._make(Expr.SQR, self) if o is self else Expr._make(Expr.MUL, self, o)
+
+    __rmul__ = __mul__
+
+    def __neg__(self):
+        return Expr._make(Expr.NEG, self)
+
+    def __pow__(self, e):
+        if not isinstance(e, int) or isinstance(e, bool) or not 0 <= e <= 1 << 16:
+            raise ValueError("the exponent is an integer 0 .. 65536")
+        if e == 0:
+            return Expr.const(1)
+        acc = self
+        for bit in bin(e)[3:]:            # square and multiply from the top bit
+            acc = acc * acc
+            if bit == "1":
+                acc = acc * self
+        return acc
+
+    def nodes(self, modulus: Optional[int] = None):
+        """``(nodes, consts, n_chal, n_cols_used)``: the sub-expressions this one depends on as ``(op, a, b)`` triples in topological
+        order, this one last; ``consts`` the distinct constants (reduced modulo ``modulus`` when given) that ``CONST`` nodes index."""
+        index, out, consts, const_at = {}, [], [], {}
+        n_chal = n_cols = 0
+        stack = [(self, False)]
+        while stack:
+            e, seen = stack.pop()
+            if e.serial in index:
+                continue
+            if e.op <= Expr.CHAL:
+                if e.op == Expr.COL:
+                    n_cols = max(n_cols, e.a + 1)
+                    node = (Expr.COL, e.a, e.b & 0xFFFFFFFF)
+                elif e.op == Expr.CONST:
+                    v = e.a % modulus if modulus else e.a
+                    if v in const_at:                 # constants that are equal modulo the field are one node
+                        index[e.serial] = const_at[v]
+                        continue
+                    const_at[v] = len(out)
+                    consts.append(v)
+                    node = (Expr.CONST, len(consts) - 1, 0)
+                else:
+                    n_chal = max(n_chal, e.a + 1)
+                    node = (Expr.CHAL, e.a, 0)
+            elif not seen:
+                stack.append((e, True))
+                for c in (e.b, e.a):
+                    if c is not None and c.serial not in index:
+                        stack.append((c, False))
+                continue
+            else:
+                node = (e.op, index[e.a.serial], index[e.b.serial] if e.b is not None else 0)
+            index[e.serial] = len(out)
+            out.append(node)
+        return out, consts, n_chal, n_cols
+
+    def __repr__(self):
+        if self.op == Expr.COL:
+            return f"col({self.a}, {self.b})"
+        if self.op == Expr.CONST:
+            return f"const({self.a})"
+        if self.op == Expr.CHAL:
+            return f"challenge({self.a})"
+        return f"<Expr {('add', 'sub', 'mul', 'neg', 'sqr')[self.op - 3]} #{self.serial}>"
+
+
+class GateProgram:
+    """An ``Expr`` compiled for one domain's field and device (mi355_msm_expr_*; ``dom.compile_expression(expr, ncols)``): a straight-line
+    program whose one launch evaluates the expression for every row.  ``query``: "nodes", "instructions", "slots", "products" (field
+    products per row, conversions included), "reduces", "columns", "lds_bytes", "last_us", "last_device_us"."""
+
+    def __init__(self, dom, expr, ncols: int):
+        self.handle = ctypes.c_void_p()
+        self.dom = dom
+        if not dom.handle:
+            raise MsmError(-1, "the domain is closed")
+        if not isinstance(expr, Expr):
+            raise TypeError("expr: an Expr")
+        self._lib = dom._lib
+        nodes, consts, self.n_chal, used = expr.nodes(dom.modulus)
+        self.ncols = int(ncols)
+        if used > self.ncols:
+            raise ValueError(f"the expression reads column {used - 1}, ncols is {self.ncols}")
+        flat = (ctypes.c_uint32 * (3 * len(nodes)))(*[w for node in nodes for w in node])
+        cb = b"".join(v.to_bytes(32, "little") for v in consts)
+        _check(self._lib.mi355_msm_expr_create(ctypes.byref(self.handle), dom.handle, flat, len(nodes), cb if consts else None, len(consts), self.n_chal,
+                                               self.ncols, 1))
+
+    def run(self, cols, challenges=(), rot_step: int = 1, montgomery: bool = True, out=None):
+        """``out[i]`` = the expression at row ``i`` for ``i < len = max(len(cols[j]))``: ``cols`` is a list of ``ncols`` vectors of 32-byte
+        elements (bytes, NumPy or torch, all in one kind of memory) whose lengths divide ``len``; column ``j`` at rotation ``rot`` is read
+        at row ``((i + rot * rot_step) mod len) mod len(cols[j])``, so a periodic column costs its period and a column of one element is a
+        scalar.  ``challenges``: ``n_chal`` integers.  ``rot_step`` is ``M / n`` on a quotient domain, 1 on the constraint domain.  GPU
+        tensors in give a GPU tensor out, on the current stream; ``out`` may be one of the full-length columns if the expression reads
+        that column at rotation 0 only."""
+        if not self.handle:
+            raise MsmError(-1, "the program is closed")
+        cols = list(cols)
+        challenges = [int(c) for c in challenges]
+        if len(cols) != self.ncols or len(challenges) != self.n_chal:
+            raise ValueError(f"the program takes {self.ncols} columns and {self.n_chal} challenges")
+        bufs = [_Buf(c) for c in cols]
+        for b in bufs:
+            if b.nbytes % 32 or b.is_device != bufs[0].is_device:
+                raise ValueError("the columns must hold 32-byte elements, in the same kind of memory")
+            if b.is_device and b.device_index != self.dom.device:
+                raise MsmError(-1, f"the input lives on cuda:{b.device_index} but this domain is bound to device {self.dom.device}")
+        lens = [b.nbytes // 32 for b in bufs]
+        if not bufs:
+            raise ValueError("a program without columns has no rows")
+        n = max(lens)
+        first = bufs[lens.index(n)]
+        res, ob = self.dom._out(cols[lens.index(n)], first, out, n)
+        m = self.ncols
+        ptrs = (ctypes.c_void_p * m)(*[b.ptr for b in bufs])
+        lv = (ctypes.c_size_t * m)(*lens)
+        cb = b"".join(self.dom._scalar(c, montgomery) for c in challenges)
+        flags = (0 if montgomery else 1) | (2 if first.is_device else 0)
+        _check(self._lib.mi355_msm_expr_run(self.handle, ob.ptr if n else None, ptrs, lv, m, n, int(rot_step), cb if challenges else None, len(challenges),
+                                            flags, first.stream if first.is_device else None))
+        if first.is_device:
+            return res
+        return _like_input(cols[lens.index(n)], res, (n, 32))
+
+    def query(self, key: str) -> int:
+        """ "nodes", "instructions", "slots", "products", "reduces", "columns", "lds_bytes", "last_us", "last_device_us" """
+        v = ctypes.c_uint64(0)
+        _check(self._lib.mi355_msm_expr_query(self.handle, key.encode(), ctypes.byref(v)))
+        return int(v.value)
+
+    def close(self) -> None:
+        if self.handle:
+            _check(self._lib.mi355_msm_expr_destroy(self.handle))
             self.handle = ctypes.c_void_p()
 
     def __enter__(self):

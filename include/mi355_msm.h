@@ -992,6 +992,57 @@ RustError mi355_msm_lookup_destroy(mi355_msm_lookup* h);
 RustError mi355_msm_domain_logup_sum(mi355_msm_domain* d, void* out, void* total32, void* helpers, const void* table, const void* mult,
                                      const void* values, size_t m, size_t stride, size_t n, const void* beta, unsigned flags, void* stream);
 
+/* ---- custom-gate expressions over Fr columns with rotations: a DAG compiled once, evaluated for every row in one launch ----
+ * What a Plonkish (halo2-style) prover computes in its quotient round and halo2 calls evaluate_h: a circuit-specific polynomial
+ * expression in dozens of columns read at several rotations.  mi355_msm_domain_plonk_quotient has Jellyfish's gate wired in; this
+ * handle evaluates any gate.  The contract is stated on integers: out[i] = the DAG evaluated modulo r at row i.
+ *   create  on the field and the device of the domain d, WHICH MUST OUTLIVE THE PROGRAM (its size plays no part).  `nodes` holds
+ *           n_nodes triples (op, a, b) of uint32_t in topological order, the last one the result:
+ *             0 COL    column a at the rotation b (a signed 32-bit value, within +-2^15)
+ *             1 CONST  element a of `consts` (n_consts 32-byte HOST elements; flag bit 0 at create: plain integers)
+ *             2 CHAL   element a of the challenges given at every run
+ *             3 ADD, 4 SUB, 5 MUL of the earlier nodes a and b;  6 NEG, 7 SQR of the earlier node a
+ *           At most 65 535 nodes, 4 096 constants, 64 challenges, 64 columns.  Nodes the result does not depend on cost nothing.
+ *           create FAILS (-1, the message names S and the limit) when the program needs more than 32 slots at once: split the sum
+ *           over an output column (overlap rule below).
+ *   run     out[i], i < len <= 2^30 (any len, not only a power of two; len == 0 succeeds and writes nothing).  `cols` is a HOST array
+ *           of ncols pointers, lens[j] the length of column j, which must divide len: COL(j, rot) is read at row
+ *           ((i + rot * rot_step) mod len) mod lens[j].  A periodic column (the `ratio` inverses of Z_H on a coset) costs its period,
+ *           a column of length 1 is a scalar.  rot_step is M / n on a quotient domain, 1 on the constraint domain.  `challenges`:
+ *           nchal HOST elements.  Flag bit 0: plain integers instead of arkworks images -- columns, challenges and output alike; ANY
+ *           256-bit input is read as its residue and every output is canonical.  Flag bit 1 (value 2): the pointers in `cols` and
+ *           `out` are DEVICE pointers (4-byte aligned), `stream` is the hipStream_t on which the inputs become ready, the work is
+ *           enqueued there and the call returns when the output is written; without it they are host pointers, staged through a buffer
+ *           the program keeps, and a non-null stream is an error.  OVERLAP: `out` may BE one of the full-length columns if the program
+ *           reads that column at rotation 0 only; any other overlap of out with a column is refused.
+ *   query   "nodes", "instructions", "slots" (S), "products" (field products per row, the conversions of the column operands and of
+ *           the result included), "reduces" (reductions the compiler inserted), "columns", "lds_bytes" (per block of 64 rows),
+ *           "last_us", "last_device_us".
+ * No name here ends in _device (the convention of mi355_msm_lookup_count); tests/test_gpu_expr.py pins the stream-ordering promise of
+ * flag bit 1 with a late producer.
+ * Scheme (csrc/expr.hpp).  create orders the evaluation by a post-order walk that takes the operand with the larger Sethi-Ullman label
+ * first, then hands out slots by a linear scan: leaves are never kept (a column operand is loaded at its use and pays its one
+ * conversion there, constants and challenges are read through wave-uniform pointers), a node whose only use is the next instruction
+ * stays in registers, every other interior node keeps a slot until its last use.  A slot is 8 words per lane: every stored value is a
+ * 256-bit integer below 2^256, which is tighter than what a product asks of its operands, so the compiler carries an upper bound in
+ * units of r for every node and inserts a reduction (a conditional subtraction of r, or a product by one when the bound is above 3)
+ * where an ADD, SUB or NEG would otherwise pass 2^256 / r = 13.7 (BLS12-377) or 2.2 (BLS12-381).  run: ONE launch, one lane per row, blocks
+ * of one wave; the slots live in dynamic LDS, lane-interleaved (no lane reads another's, no barrier); the instruction loop is rolled
+ * and its control is wave-uniform; only the column reads are indexed by the lane.
+ * Work memory is the program's own: the instructions and constants, the column references and challenges of the most recent run, the
+ * staged vectors of a host-pointer run.  Results never depend on host versus device pointers.  There is no CPU fallback.
+ * Errors: -1 with a message, decided before any device call: unknown flag bits, len above 2^30, more than 64 columns or challenges,
+ * null pointers, a lens[j] of 0 or one that does not divide len, alignment, a stream without flag bit 1, an overlap in part, and last
+ * the null handle (create: the limits of the DAG, then the domain), after which ncols and nchal are judged against what the program was
+ * created with, and an `out` that is a column against its rotations.  hipErrorNoDevice without a GPU. */
+typedef struct mi355_msm_expr mi355_msm_expr;
+RustError mi355_msm_expr_create(mi355_msm_expr** out, mi355_msm_domain* d, const uint32_t* nodes, size_t n_nodes, const void* consts, size_t n_consts,
+                                size_t n_chal, size_t n_cols, unsigned flags);
+RustError mi355_msm_expr_run(mi355_msm_expr* e, void* out, const void* const* cols, const size_t* lens, size_t ncols, size_t len, size_t rot_step,
+                             const void* challenges, size_t nchal, unsigned flags, void* stream);
+RustError mi355_msm_expr_query(mi355_msm_expr* e, const char* key, uint64_t* value);
+RustError mi355_msm_expr_destroy(mi355_msm_expr* e);
+
 /* Sum `count` projective images (any Z) into one normalised image: the multi-GPU combine step
  * ("final 8-point curve add").  Pure host arithmetic on <= a few dozen points; no device needed. */
 RustError mi355_msm_fold(int curve, void* out_projective, const void* projective, size_t count);

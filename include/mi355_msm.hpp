@@ -494,6 +494,47 @@ struct LookupTable {
   }
 };
 
+// A custom-gate expression compiled for the GPU (mi355_msm_expr_*), on a domain that outlives it: nodes are (op, a, b) triples in
+// topological order, the last one the result (0 COL column a at the signed rotation b, 1 CONST, 2 CHAL, 3 ADD, 4 SUB, 5 MUL, 6 NEG,
+// 7 SQR); one launch of run evaluates it for every row.  Fr values in Montgomery form.
+struct GateProgram {
+  mi355_msm_expr* handle = nullptr;
+  size_t n_cols = 0, n_chal = 0;
+  GateProgram(const Radix2EvaluationDomain& dom, const std::vector<uint32_t>& nodes, const std::vector<BigInteger256>& consts, size_t n_chal_, size_t n_cols_)
+      : n_cols(n_cols_), n_chal(n_chal_) {
+    check(mi355_msm_expr_create(&handle, dom.handle, nodes.data(), nodes.size() / 3, consts.empty() ? nullptr : consts.data(), consts.size(), n_chal, n_cols, 0));
+  }
+  GateProgram(const GateProgram&) = delete;
+  GateProgram& operator=(const GateProgram&) = delete;
+  GateProgram(GateProgram&& o) noexcept : handle(o.handle), n_cols(o.n_cols), n_chal(o.n_chal) { o.handle = nullptr; }
+  uint64_t query(const char* key) const {
+    uint64_t v = 0;
+    check(mi355_msm_expr_query(handle, key, &v));
+    return v;
+  }
+  // out[i] for i < the longest column; column j at rotation rot is read at row ((i + rot * rot_step) mod len) mod cols[j].size()
+  std::vector<BigInteger256> run(const std::vector<std::vector<BigInteger256>>& cols, const std::vector<BigInteger256>& challenges, size_t rot_step = 1) const {
+    std::vector<const void*> ptrs;
+    std::vector<size_t> lens;
+    size_t len = 0;
+    for (const auto& c : cols) {
+      ptrs.push_back(c.data());
+      lens.push_back(c.size());
+      len = c.size() > len ? c.size() : len;
+    }
+    std::vector<BigInteger256> out(len);
+    check(mi355_msm_expr_run(handle, out.data(), ptrs.data(), lens.data(), cols.size(), len, rot_step, challenges.empty() ? nullptr : challenges.data(),
+                             challenges.size(), 0, nullptr));
+    return out;
+  }
+  ~GateProgram() {
+    if (handle) {
+      RustError e = mi355_msm_expr_destroy(handle);
+      if (e.message) std::free(e.message);
+    }
+  }
+};
+
 // phi[0] = 0, phi[j+1] = phi[j] + sum_c 1 / (beta + columns[c][j]) - mult[j] / (beta + table[j]); *total is zero exactly when the
 // multiset relation holds.  A zero denominator contributes 0.
 inline std::vector<BigInteger256> logup_sum(const Radix2EvaluationDomain& dom, const std::vector<BigInteger256>& table, const std::vector<BigInteger256>& mult,

@@ -271,6 +271,16 @@ pub mod sys {
         pub fn mi355_msm_domain_logup_sum(d: *mut c_void, out: *mut c_void, total32: *mut c_void, helpers: *mut c_void, table: *const c_void,
                                           mult: *const c_void, values: *const c_void, m: usize, stride: usize, n: usize, beta: *const c_void,
                                           flags: c_uint, stream: *mut c_void) -> Error;
+        // compiled custom-gate expressions on a domain handle, which must outlive them: `nodes` holds n_nodes triples (op, a, b) in
+        // topological order (0 COL column a at the signed rotation b, 1 CONST, 2 CHAL, 3 ADD, 4 SUB, 5 MUL, 6 NEG, 7 SQR), the last one
+        // the result.  run: `cols` is a HOST array of ncols pointers, lens[j] divides len; flags bit 0: plain integers, bit 1 (value 2):
+        // the columns and `out` are device pointers and `stream` is where the inputs become ready, else host pointers and a null stream
+        pub fn mi355_msm_expr_create(out: *mut *mut c_void, d: *mut c_void, nodes: *const u32, n_nodes: usize, consts: *const c_void, n_consts: usize,
+                                     n_chal: usize, n_cols: usize, flags: c_uint) -> Error;
+        pub fn mi355_msm_expr_run(e: *mut c_void, out: *mut c_void, cols: *const *const c_void, lens: *const usize, ncols: usize, len: usize,
+                                  rot_step: usize, challenges: *const c_void, nchal: usize, flags: c_uint, stream: *mut c_void) -> Error;
+        pub fn mi355_msm_expr_query(e: *mut c_void, key: *const c_char, value: *mut u64) -> Error;
+        pub fn mi355_msm_expr_destroy(e: *mut c_void) -> Error;
         // Poseidon parameters over Fr on a domain handle, which must outlive them: `ark` holds (full + partial rounds) * (rate + 1)
         // host elements, `mds` (rate + 1)^2 (flags bit 0: plain integers).  hash: n sponges, row i of `input` holds in_len elements, row
         // i of `out` receives n_out; `header` is null or `rate` host elements absorbed before every row.  merkle: snarkVM's Poseidon
@@ -846,6 +856,82 @@ pub mod lookup {
                                               table.as_ptr() as *const c_void, mult.as_ptr() as *const c_void, flat.as_ptr() as *const c_void,
                                               columns.len(), n, n, &beta as *const Fr as *const c_void, 0, std::ptr::null_mut()));
         (phi, total)
+    }
+}
+
+/// Custom-gate expressions over columns of `Fr` with rotations (`mi355_msm_expr_*`): a DAG compiled once per circuit, evaluated for
+/// every row in one launch -- the step halo2 calls `evaluate_h`.
+pub mod expr {
+    use super::sys;
+    use super::Fr;
+    use ark_std::Zero;
+    use std::os::raw::c_void;
+
+    fn check(err: super::Error) {
+        if err.code != 0 {
+            panic!("{}", String::from(err));
+        }
+    }
+
+    pub const COL: u32 = 0;
+    pub const CONST: u32 = 1;
+    pub const CHAL: u32 = 2;
+    pub const ADD: u32 = 3;
+    pub const SUB: u32 = 4;
+    pub const MUL: u32 = 5;
+    pub const NEG: u32 = 6;
+    pub const SQR: u32 = 7;
+
+    /// Lives on a domain handle of `sys::mi355_msm_domain_create`, which the caller keeps alive for as long as the program.
+    pub struct GateProgram {
+        handle: *mut c_void,
+        pub n_cols: usize,
+        pub n_chal: usize,
+    }
+
+    impl Drop for GateProgram {
+        fn drop(&mut self) {
+            if !self.handle.is_null() {
+                let _ = unsafe { sys::mi355_msm_expr_destroy(self.handle) };
+            }
+        }
+    }
+
+    impl GateProgram {
+        /// `nodes`: `(op, a, b)` in topological order, the last one the result; a rotation is `b as i32`.  Panics with the library's
+        /// message when the program needs more slots than the kernel has.
+        ///
+        /// # Safety
+        /// `domain` is a live handle of `sys::mi355_msm_domain_create` over the field of `Fr` and outlives the program.
+        pub unsafe fn new(domain: *mut c_void, nodes: &[[u32; 3]], consts: &[Fr], n_chal: usize, n_cols: usize) -> Self {
+            let mut handle: *mut c_void = std::ptr::null_mut();
+            check(sys::mi355_msm_expr_create(&mut handle, domain, nodes.as_ptr() as *const u32, nodes.len(), consts.as_ptr() as *const c_void,
+                                             consts.len(), n_chal, n_cols, 0));
+            GateProgram { handle, n_cols, n_chal }
+        }
+
+        /// `out[i]` for `i < len = the longest column`; column `j` at rotation `rot` is read at row
+        /// `((i + rot * rot_step) mod len) mod cols[j].len()`, so every length must divide `len`
+        pub fn run(&self, cols: &[&[Fr]], challenges: &[Fr], rot_step: usize) -> Vec<Fr> {
+            assert!(cols.len() == self.n_cols && challenges.len() == self.n_chal, "the columns and challenges the program was created with");
+            let len = cols.iter().map(|c| c.len()).max().unwrap_or(0);
+            let ptrs: Vec<*const c_void> = cols.iter().map(|c| c.as_ptr() as *const c_void).collect();
+            let lens: Vec<usize> = cols.iter().map(|c| c.len()).collect();
+            let mut out = vec![Fr::zero(); len];
+            check(unsafe {
+                sys::mi355_msm_expr_run(self.handle, out.as_mut_ptr() as *mut c_void, ptrs.as_ptr(), lens.as_ptr(), cols.len(), len, rot_step,
+                                        challenges.as_ptr() as *const c_void, challenges.len(), 0, std::ptr::null_mut())
+            });
+            out
+        }
+
+        /// "nodes", "instructions", "slots", "products", "reduces", "columns", "lds_bytes", "last_us", "last_device_us"
+        pub fn query(&self, key: &str) -> u64 {
+            let k = std::ffi::CString::new(key).expect("a key without NUL");
+            let mut v = 0u64;
+            check(unsafe { sys::mi355_msm_expr_query(self.handle, k.as_ptr(), &mut v) });
+            v
+        }
     }
 }
 

@@ -23,6 +23,7 @@ All margins must be positive (tests/test_fr_consts.py runs it); the host build c
     python tools/limb_bounds_fr.py --sparse   (the lane sums of the sparse matrix-vector product of csrc/sparse.hpp: analyse_sparse below)
     python tools/limb_bounds_fr.py --mle      (the folds, extrapolations, products and sums of csrc/mle.hpp: analyse_mle below)
     python tools/limb_bounds_fr.py --poseidon (the rounds of csrc/poseidon.hpp with the reductions its schedule sets: analyse_poseidon below)
+    python tools/limb_bounds_fr.py --expr     (the stored form and the bound rule of the expression programs of csrc/expr.hpp: analyse_expr below)
 """
 import sys
 
@@ -650,8 +651,54 @@ def analyse_poseidon(name, r, out):
     return ok
 
 
+def analyse_expr(name, r, out):
+    """The stored form of csrc/expr.hpp (python tools/limb_bounds_fr.py --expr).  Every operand of an instruction is a 256-bit integer
+    unpacked into normalised limbs, so the products need nothing from the compiler: ANY two 256-bit values give a class-M product.  What
+    the compiler has to keep is the 2^256 of the stored form: it carries value <= B r per node, B <= LIM = 2^32 / (top word of r + 1),
+    a little below 2^256 / r.  Printed: LIM, the rule for every instruction, and the reductions it leads to in small cases."""
+    import math
+
+    rl = limbs(r)
+    ok = True
+
+    def margin(what, have, limit):
+        nonlocal ok
+        m = limit - have
+        ok &= m > 0
+        out.append("  %-82s %s (limit 2^%.2f, margin %.3e)" % (what, "ok " if m > 0 else "BAD", math.log2(limit), m))
+
+    lim = float(1 << 32) / ((r >> 224) + 1)
+    K = 32 * lim
+    out.append("%s: r = %.3f * 2^252, 2^256 / r = %.4f, LIM = %.4f, R / r = %.2f, 32 LIM = %.2f  (the programs of expr.hpp)"
+               % (name, r / 2**252, 2.0**256 / r, lim, R / r, K))
+    any256 = [MASK] * (N - 1) + [(1 << (256 - B * (N - 1))) - 1]
+    margin("LIM r against the stored form (2^256)", int(lim * r), 1 << 256)
+    margin("a product of any two stored values: largest column against 2^64", max(columns(any256, any256, rl)), 1 << 64)
+    margin("a product of any two stored values: r + a b / R against 2r", r + (((1 << 256) - 1) ** 2) // R + 1, 2 * r)
+    margin("a column operand: r + 2^256 r / R against 2r (then one conditional subtraction: below r)", r + ((1 << 256) * r) // R + 1, 2 * r)
+    margin("the result: any stored value times the conversion constant, r + a r / R against 2r", r + ((1 << 256) * r) // R + 1, 2 * r)
+    margin("two canonical leaves added: 2r against LIM r", 2 * r, int(lim * r))
+    margin("SUB of canonical operands: r + r - 0 against LIM r", 2 * r, int(lim * r))
+    out.append("  rule: MUL, SQR  B = 1 + B_a B_b / (32 LIM)   (at most 1 + LIM / 32 = %.4f)" % (1 + lim / 32))
+    out.append("        ADD       B = B_a + B_b;   SUB, NEG  B = B_a + ceil(B_b);   each must stay <= LIM = %.4f" % lim)
+    out.append("        else reduce an operand in place: B <= 3: one conditional subtraction, B -> max(1, B - 1); B > 3: a product by one, B -> 1 + B / (32 LIM)")
+    prod = 1 + 1 / K
+    out.append("  a product of canonical operands: %.4f; product + product: %.4f (%s); (product + product) + product: %.4f (%s)"
+               % (prod, 2 * prod, "fits" if 2 * prod <= lim else "one reduction", 3 * prod, "fits" if 3 * prod <= lim else "one reduction"))
+    b, steps = 1.0, 0
+    while 2 * b <= lim:
+        b, steps = 2 * b, steps + 1
+    out.append("  a doubling chain a = a + a from a canonical leaf runs %d steps before its first reduction" % steps)
+    return ok
+
+
 def main():
     out = []
+    if "--expr" in sys.argv[1:]:
+        ok = all([analyse_expr(name, r, out) for name, r in FIELDS.items()])
+        print("\n".join(out))
+        print("all margins positive" if ok else "A MARGIN IS NOT POSITIVE")
+        return 0 if ok else 1
     if "--poseidon" in sys.argv[1:]:
         ok = all([analyse_poseidon(name, r, out) for name, r in FIELDS.items()])
         print("\n".join(out))
