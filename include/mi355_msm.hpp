@@ -266,6 +266,14 @@ struct FixedBase {
   }
 };
 
+namespace detail {
+// Does a vector of `have` elements hold m columns of n elements, `stride` >= n >= 1 elements apart?  Several C entry points take no
+// length for such a vector, so the wrappers look; by division, so that no product of the caller's numbers can wrap.
+inline bool holds_columns(size_t have, size_t m, size_t stride, size_t n) {
+  return m == 0 || (have >= n && (m == 1 || (stride != 0 && (have - n) / stride >= m - 1)));
+}
+}  // namespace detail
+
 // ark-poly's Radix2EvaluationDomain over the curve family's Fr (ARK poly/src/domain/radix2/mod.rs): vectors of Fr values (Montgomery
 // form, what a Vec<Fr> holds), zero-extended to the domain size, transformed on the GPU.
 struct Radix2EvaluationDomain {
@@ -294,10 +302,12 @@ struct Radix2EvaluationDomain {
   std::vector<BigInteger256> ifft(const std::vector<BigInteger256>& evals) const { return transform(evals, 1); }
   std::vector<BigInteger256> coset_fft(const std::vector<BigInteger256>& coeffs) const { return transform(coeffs, 2); }
   std::vector<BigInteger256> coset_ifft(const std::vector<BigInteger256>& evals) const { return transform(evals, 3); }
-  // mul_polynomials_in_evaluation_domain
+  // mul_polynomials_in_evaluation_domain.  Like vec_op below, mul REFUSES operands of unequal length (std::invalid_argument): an
+  // output sized by one operand and computed over the shorter one would hand back elements that were never written.
   std::vector<BigInteger256> mul(const std::vector<BigInteger256>& a, const std::vector<BigInteger256>& b) const {
+    if (a.size() != b.size()) throw std::invalid_argument("mul: a and b differ in length");
     std::vector<BigInteger256> out(a.size());
-    check(mi355_msm_domain_mul(handle, out.data(), a.data(), b.data(), a.size() < b.size() ? a.size() : b.size(), 0));
+    check(mi355_msm_domain_mul(handle, out.data(), a.data(), b.data(), a.size(), 0));
     return out;
   }
   // ark-ff batch_inversion_and_mul: coeff / v[i], zeros stay zero
@@ -307,13 +317,14 @@ struct Radix2EvaluationDomain {
     return out;
   }
   std::vector<BigInteger256> batch_inversion(const std::vector<BigInteger256>& v) const { return batch_inversion_and_mul(v); }
-  // op 0 a + b, 1 a - b, 2 a * b - c
+  // op 0 a + b, 1 a - b, 2 a * b - c; operands of unequal length are refused (std::invalid_argument)
   std::vector<BigInteger256> vec_op(unsigned op, const std::vector<BigInteger256>& a, const std::vector<BigInteger256>& b,
                                     const std::vector<BigInteger256>* c = nullptr) const {
+    if (a.size() != b.size()) throw std::invalid_argument("vec_op: a and b differ in length");
+    if (c && c->size() != a.size()) throw std::invalid_argument("vec_op: c differs in length from a and b");
+    if (op == 2 && !c) throw std::invalid_argument("vec_op: a * b - c needs c");
     std::vector<BigInteger256> out(a.size());
-    size_t n = a.size() < b.size() ? a.size() : b.size();
-    if (c && c->size() < n) n = c->size();
-    check(mi355_msm_domain_vec_op(handle, out.data(), a.data(), b.data(), c ? c->data() : nullptr, n, op, 0));
+    check(mi355_msm_domain_vec_op(handle, out.data(), a.data(), b.data(), c ? c->data() : nullptr, a.size(), op, 0));
     return out;
   }
   std::vector<BigInteger256> add(const std::vector<BigInteger256>& a, const std::vector<BigInteger256>& b) const { return vec_op(0, a, b); }
@@ -371,6 +382,13 @@ struct Radix2EvaluationDomain {
   std::vector<BigInteger256> permutation_product(const std::vector<BigInteger256>& wires, const std::vector<BigInteger256>& sigmas, size_t stride,
                                                  const std::vector<BigInteger256>& ks, const BigInteger256& beta, const BigInteger256& gamma,
                                                  BigInteger256* total = nullptr) const {
+    const size_t n = size();
+    if (ks.empty()) throw std::invalid_argument("permutation_product: ks is empty");
+    if (stride < n) throw std::invalid_argument("permutation_product: stride is below the domain size");
+    if (!detail::holds_columns(wires.size(), ks.size(), stride, n))
+      throw std::invalid_argument("permutation_product: wires holds fewer than ks.size() columns of size() elements");
+    if (!detail::holds_columns(sigmas.size(), ks.size(), stride, n))
+      throw std::invalid_argument("permutation_product: sigmas holds fewer than ks.size() columns of size() elements");
     std::vector<BigInteger256> out(size());
     check(mi355_msm_domain_permutation_product(handle, out.data(), total, wires.data(), sigmas.data(), ks.size(), stride, ks.data(), &beta, &gamma, 0));
     return out;
@@ -383,6 +401,17 @@ struct Radix2EvaluationDomain {
                                             const std::vector<BigInteger256>& pi, size_t stride, size_t n, const std::vector<BigInteger256>& ks,
                                             const BigInteger256& alpha, const BigInteger256& beta, const BigInteger256& gamma,
                                             const BigInteger256* offset = nullptr) const {
+    const size_t M = size();
+    if (ks.empty()) throw std::invalid_argument("plonk_quotient: ks is empty");
+    if (stride < M) throw std::invalid_argument("plonk_quotient: stride is below the domain size");
+    if (!detail::holds_columns(wires.size(), ks.size(), stride, M))
+      throw std::invalid_argument("plonk_quotient: wires holds fewer than ks.size() columns of size() elements");
+    if (!detail::holds_columns(sigmas.size(), ks.size(), stride, M))
+      throw std::invalid_argument("plonk_quotient: sigmas holds fewer than ks.size() columns of size() elements");
+    if (!selectors.empty() && !detail::holds_columns(selectors.size(), 13, stride, M))
+      throw std::invalid_argument("plonk_quotient: selectors holds fewer than 13 columns of size() elements");
+    if (z.size() < M) throw std::invalid_argument("plonk_quotient: z holds fewer than size() elements");
+    if (!pi.empty() && pi.size() < M) throw std::invalid_argument("plonk_quotient: pi holds fewer than size() elements");
     std::vector<BigInteger256> out(size());
     check(mi355_msm_domain_plonk_quotient(handle, out.data(), wires.data(), sigmas.data(), selectors.empty() ? nullptr : selectors.data(), z.data(),
                                           pi.empty() ? nullptr : pi.data(), ks.size(), stride, n, ks.data(), &alpha, &beta, &gamma, offset, 0));
@@ -398,6 +427,7 @@ struct Radix2EvaluationDomain {
       lens.push_back(c.size());
       n = c.size() > n ? c.size() : n;
     }
+    if (coeffs.size() != cols.size()) throw std::invalid_argument("linear_combination: coeffs holds one element per column");
     std::vector<BigInteger256> out(n);
     check(mi355_msm_domain_linear_combination(handle, out.data(), ptrs.data(), lens.data(), coeffs.data(), cols.size(), 0));
     return out;
@@ -417,6 +447,9 @@ struct SparseMatrix {
   mi355_msm_sparse* handle = nullptr;
   SparseMatrix(const Radix2EvaluationDomain& dom, size_t rows, size_t cols, const std::vector<uint64_t>& row_ptr, const std::vector<uint32_t>& col_idx,
                const std::vector<BigInteger256>& values) {
+    if (row_ptr.empty() || row_ptr.size() - 1 != rows) throw std::invalid_argument("SparseMatrix: row_ptr holds rows + 1 offsets");
+    if (col_idx.size() != row_ptr.back()) throw std::invalid_argument("SparseMatrix: col_idx holds row_ptr.back() entries");
+    if (values.size() != row_ptr.back()) throw std::invalid_argument("SparseMatrix: values holds row_ptr.back() entries");
     check(mi355_msm_sparse_create(&handle, dom.handle, rows, cols, row_ptr.data(), col_idx.data(), values.data(), 0));
   }
   SparseMatrix(const SparseMatrix&) = delete;
@@ -431,6 +464,7 @@ struct SparseMatrix {
   size_t cols() const { return (size_t)query("cols"); }
   // y[i] = sum_k values[k] * z[col_idx[k]] over the entries of row i; z holds cols() elements
   std::vector<BigInteger256> apply(const std::vector<BigInteger256>& z) const {
+    if (z.size() != cols()) throw std::invalid_argument("SparseMatrix::apply: z holds cols() elements");
     std::vector<BigInteger256> out(rows());
     check(mi355_msm_sparse_apply(handle, out.data(), z.data(), 0, nullptr));
     return out;
@@ -502,6 +536,7 @@ struct GateProgram {
   size_t n_cols = 0, n_chal = 0;
   GateProgram(const Radix2EvaluationDomain& dom, const std::vector<uint32_t>& nodes, const std::vector<BigInteger256>& consts, size_t n_chal_, size_t n_cols_)
       : n_cols(n_cols_), n_chal(n_chal_) {
+    if (nodes.size() % 3) throw std::invalid_argument("GateProgram: nodes holds (op, a, b) triples");
     check(mi355_msm_expr_create(&handle, dom.handle, nodes.data(), nodes.size() / 3, consts.empty() ? nullptr : consts.data(), consts.size(), n_chal, n_cols, 0));
   }
   GateProgram(const GateProgram&) = delete;
@@ -540,8 +575,13 @@ struct GateProgram {
 inline std::vector<BigInteger256> logup_sum(const Radix2EvaluationDomain& dom, const std::vector<BigInteger256>& table, const std::vector<BigInteger256>& mult,
                                             const std::vector<std::vector<BigInteger256>>& columns, const BigInteger256& beta, BigInteger256* total = nullptr) {
   const size_t n = table.size();
+  if (mult.size() != n) throw std::invalid_argument("logup_sum: mult holds one element per table row");
+  if (columns.empty()) throw std::invalid_argument("logup_sum: columns is empty");
   std::vector<BigInteger256> flat, phi(n);
-  for (const auto& c : columns) flat.insert(flat.end(), c.begin(), c.end());
+  for (const auto& c : columns) {
+    if (c.size() != n) throw std::invalid_argument("logup_sum: every one of columns holds one element per table row");
+    flat.insert(flat.end(), c.begin(), c.end());
+  }
   check(mi355_msm_domain_logup_sum(dom.handle, phi.data(), total, nullptr, table.data(), mult.data(), flat.data(), columns.size(), n, n, &beta, 0, nullptr));
   return phi;
 }
@@ -551,7 +591,10 @@ inline std::vector<BigInteger256> logup_sum(const Radix2EvaluationDomain& dom, c
 // h = coset_ifft((coset_fft(ifft(a)) * coset_fft(ifft(b)) - coset_fft(ifft(c))) / Z(g)).  (The Python layer keeps every step in device memory.)
 inline std::vector<BigInteger256> groth16_witness_map(const Radix2EvaluationDomain& dom, const SparseMatrix& A, const SparseMatrix& B,
                                                       const std::vector<BigInteger256>& z, size_t num_inputs) {
+  if (num_inputs > z.size()) throw std::invalid_argument("groth16_witness_map: z holds fewer than num_inputs elements");
   std::vector<BigInteger256> a = A.apply(z), b = B.apply(z);
+  if (a.size() + num_inputs > dom.size() || b.size() > dom.size())
+    throw std::invalid_argument("groth16_witness_map: the constraints and the inputs of z do not fit the domain");
   a.insert(a.end(), z.begin(), z.begin() + num_inputs);
   a.resize(dom.size());
   b.resize(dom.size());
