@@ -1631,8 +1631,11 @@ class Radix2EvaluationDomain:
         R1CS matrices ``A`` and ``B`` as ``SparseMatrix`` on this domain: ``a = A z`` with ``z[0 .. num_inputs)`` appended at rows
         ``n .. n + num_inputs`` (``n = A.rows`` constraints), ``b = B z``, ``c = a * b`` element by element, all zero-padded to ``size``;
         ``h = coset_ifft((coset_fft(ifft(a)) * coset_fft(ifft(b)) - coset_fft(ifft(c))) / Z(g))``.  With a GPU tensor in, every step
-        runs on the tensor's current stream and the result is a GPU tensor that ``MultiScalarMultContext.run`` takes as it is; nothing
-        but ``z`` comes from the host and nothing goes back."""
+        runs on the tensor's current stream and the result is a GPU tensor; nothing but ``z`` comes from the host and nothing goes back.
+        ``h[:size - 1]`` (the last coefficient is 0) is what ``MultiScalarMultContext.run`` takes as it is over ``h_query`` when the
+        context reads the form this call wrote: arkworks images (``montgomery=True``, the default here) need the context's option
+        ``scalars_montgomery`` set to 1 -- a new context has it at 0 and would read the images as plain integers, a wrong point and no
+        error --, plain integers (``montgomery=False``) need it at 0.  tests/test_gpu_groth16.py proves whole proofs in both forms."""
         if not self.handle:
             raise MsmError(-1, "the domain is closed")
         n, ni = int(A.rows), int(num_inputs)
