@@ -38,7 +38,7 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found: the MSM engine is HIP-only (no CPU fallback)")
 
 
-ENGINE_UNITS = ["msm_engine.hip", "partition.hip", "kernels_377g1.hip", "kernels_381g1.hip", "kernels_377g2.hip", "kernels_381g2.hip", "kernels_377te.hip", "kernels_377g2p.hip", "kernels_381g2p.hip", "kernels_check.hip", "kernels_fixed.hip", "kernels_codec.hip", "kernels_pmul.hip", "kernels_ntt.hip", "kernels_poly.hip", "kernels_gfft.hip", "kernels_scan.hip", "kernels_quot.hip", "kernels_sparse.hip", "kernels_mle.hip", "kernels_poseidon.hip", "kernels_pairing.hip", "kernels_h2c.hip", "kernels_lookup.hip", "kernels_expr.hip"]
+ENGINE_UNITS = ["msm_engine.hip", "partition.hip", "kernels_377g1.hip", "kernels_381g1.hip", "kernels_377g2.hip", "kernels_381g2.hip", "kernels_377te.hip", "kernels_377g2p.hip", "kernels_381g2p.hip", "kernels_check.hip", "kernels_fixed.hip", "kernels_codec.hip", "kernels_pmul.hip", "kernels_ntt.hip", "kernels_poly.hip", "kernels_gfft.hip", "kernels_scan.hip", "kernels_quot.hip", "kernels_sparse.hip", "kernels_mle.hip", "kernels_poseidon.hip", "kernels_pairing.hip", "kernels_h2c.hip", "kernels_lookup.hip", "kernels_expr.hip", "kernels_seg.hip"]
 
 
 def _depfile_deps(dfile: str):

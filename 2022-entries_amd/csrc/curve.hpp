@@ -460,6 +460,7 @@ MSM_HD void xyzz_madd(XyzzT<typename E::T>& acc, const AffineT<typename E::T>& p
 
 // acc += b   (add-2008-s; 12M + 2S).
 // (h2c.hpp holds a second statement of this law and of add_tail, h2c_slot_add: a change here must be made there as well.)
+// (seg_msm.hpp holds a third, sm_add_common -- the same operations, the addend fetched coordinate by coordinate: likewise.)
 template <class E>
 MSM_HD void xyzz_add(XyzzT<typename E::T>& acc, const XyzzT<typename E::T>& b, const typename E::Md& md) {
   if (xyzz_is_inf<E>(b)) return;

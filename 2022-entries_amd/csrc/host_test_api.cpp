@@ -2730,3 +2730,93 @@ int ht_expr(int field, unsigned flags, const uint32_t* nodes, uint64_t n_nodes, 
 }
 unsigned ht_expr_max_slots(void) { return EXPR_MAX_SLOTS; }
 }
+
+// ---- segmented MSM (seg_msm.hpp): the digits, one call walked serially through the kernels' per-element steps, the launch plan ----
+#include "seg_msm.hpp"
+
+template <class C>
+static int t_sm_segments(const uint8_t* points, size_t stride, const uint8_t* scalars, const uint64_t* offsets, size_t nseg, uint64_t shared_len, uint32_t c,
+                         uint32_t tile, unsigned flags, uint8_t* out, size_t out_stride) {
+  using E = typename C::E;
+  using El = typename E::T;
+  typename E::Md md;
+  std::vector<XyzzDevT<El>> res(nseg);
+  std::vector<uint32_t> sc;
+  for (size_t s = 0; s < nseg; s++) {
+    uint64_t p0, s0, len;
+    sm_segment_span(p0, s0, len, offsets, s, shared_len, 0);   // (the kernel's own statement of where a segment lies)
+    if (len == 0) {
+      xyzz_set_inf<E>(res[s].p);
+      continue;
+    }
+    sc.resize(8 * len);
+    memcpy(sc.data(), scalars + 32 * s0, 32 * len);
+    sm_serial_segment<E>(res[s].p, points + p0 * stride, stride, sc.data(), len, c ? c : sm_window_for(len), tile, (flags & 1) != 0, md);
+  }
+  pm_host_output<E>(res, (flags & 8) ? 2u : 0u, out, out_stride, md);
+  return 0;
+}
+
+extern "C" {
+// the signed digits of one 32-byte scalar for window size c, from the register form and from the memory form: sm_digits(c) values each
+int ht_sm_digits(const uint8_t* scalar, int c, int32_t* out, int32_t* out_mem) {
+  if (!scalar || !out || !out_mem || c < 1 || c > (int)SM_MAX_WINDOW) return -1;
+  uint32_t s[8];
+  memcpy(s, scalar, 32);
+  const uint32_t nd = sm_digits((uint32_t)c);
+  for (uint32_t j = 0; j < nd; j++) {
+    out[j] = sm_digit(s, j, (uint32_t)c);
+    out_mem[j] = sm_digit_mem(s, j, (uint32_t)c);
+  }
+  return (int)nd;
+}
+// mi355_msm_segments on the host, lane by lane: flags bit 0 Fr Montgomery scalars, bit 2 the shared form (offsets NULL, shared_len
+// points), bit 3 Projective images; c 0 = by length
+int ht_sm_segments(int curve, const uint8_t* points, size_t stride, const uint8_t* scalars, const uint64_t* offsets, size_t nseg, uint64_t shared_len, int c,
+                   int tile, unsigned flags, uint8_t* out, size_t out_stride) {
+  if ((flags & ~13u) || c < 0 || c > (int)SM_MAX_WINDOW || tile < (int)SM_MIN_TILE || (tile & (tile - 1)) || out_stride % 4 || (nseg && !out)) return -1;
+  if (((flags & 4) != 0) != (offsets == nullptr)) return -1;
+  DISPATCH_C(curve, t_sm_segments, points, stride, scalars, offsets, nseg, shared_len, (uint32_t)c, (uint32_t)tile, flags, out, out_stride)
+}
+// the launch plan, flattened: per class 11 values {chunk, s0, s1, c, nwin, tile, nseg, position of its ids in `ids`, wsum_at, the chunk's
+// work_bytes, the chunk's wsum_records}; returns the number of classes, -1 for bad arguments or too small arrays, -2 when a segment
+// alone exceeds the limit.  summary: {chunks, max_segs, max_wsum_records}
+long ht_sm_plan(const uint64_t* offsets, size_t nseg, uint64_t shared_len, int force_c, int tile_opt, size_t max_segs, size_t work_limit, size_t xyzz_bytes,
+                size_t el_bytes, uint64_t* classes, size_t max_classes, uint32_t* ids, size_t max_ids, uint64_t* chunk_bounds, size_t max_chunks,
+                uint64_t* summary) {
+  if (force_c < 0 || force_c > (int)SM_MAX_WINDOW || !classes || !ids || !summary || !chunk_bounds) return -1;
+  SmPlan plan;
+  sm_plan(plan, offsets, nseg, shared_len, (uint32_t)force_c, (uint32_t)tile_opt, max_segs, work_limit, xyzz_bytes, el_bytes);
+  if (!plan.fits) return -2;
+  size_t nc = 0, ni = 0;
+  if (plan.chunks.size() > max_chunks) return -1;
+  for (size_t k = 0; k < plan.chunks.size(); k++) {
+    const SmChunk& ch = plan.chunks[k];
+    chunk_bounds[3 * k] = ch.s0;
+    chunk_bounds[3 * k + 1] = ch.s1;
+    chunk_bounds[3 * k + 2] = ch.work_bytes;
+    if (ni + ch.ids.size() > max_ids) return -1;
+    for (const SmClass& cl : ch.classes) {
+      if (nc >= max_classes) return -1;
+      const uint64_t row[11] = {k, ch.s0, ch.s1, cl.c, cl.nwin, cl.tile, cl.nseg, ni + cl.ids_at, cl.wsum_at, ch.work_bytes, ch.wsum_records};
+      memcpy(classes + 11 * nc++, row, sizeof row);
+    }
+    if (!ch.ids.empty()) memcpy(ids + ni, ch.ids.data(), 4 * ch.ids.size());
+    ni += ch.ids.size();
+  }
+  summary[0] = plan.chunks.size();
+  summary[1] = plan.max_segs;
+  summary[2] = plan.max_wsum_records;
+  return (long)nc;
+}
+// the geometry of one class's launch: {slices per block, lanes per block, LDS words, the tile sm_tile_for picks for maxlen}
+int ht_sm_geometry(int c, int tile_opt, uint64_t maxlen, int xyzz_words, uint32_t* out) {
+  if (c < 1 || c > (int)SM_MAX_WINDOW || !out) return -1;
+  out[0] = sm_slices((uint32_t)c);
+  out[1] = sm_block_threads((uint32_t)c);
+  out[3] = sm_tile_for((uint32_t)c, (uint32_t)tile_opt, maxlen);
+  out[2] = sm_lds_words((uint32_t)c, out[3], (uint32_t)xyzz_words);
+  return 0;
+}
+int ht_sm_window_for(uint64_t len) { return (int)sm_window_for(len); }
+}

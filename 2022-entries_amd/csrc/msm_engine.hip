@@ -34,6 +34,7 @@
 #include "host_fold64.hpp"
 #include "host_pipeline.hpp"
 #include "launch.hpp"
+#include "seg_msm.hpp"   // SM_MAX_WINDOW .. for the options; the glue is msm_seg.hpp at the end
 
 namespace {
 
@@ -428,7 +429,12 @@ struct mi355_msm_ctx {
   DevBuf pm_points, pm_scalars, pm_out;         // host-pointer calls: one chunk of staged points / scalars / packed output images
   hipEvent_t pm_ev[2] = {nullptr, nullptr};     // around the device work of a call, on the stream it runs on
   uint64_t last_mul_us = 0, last_mul_device_us = 0;
-  long opt_fft_points_chunk = 0;                // butterflies (table points) per chunk of fft_points (msm_gfft.hpp); 0 = the default
+  long opt_seg_window = 0, opt_seg_tile = 0, opt_seg_chunk = 0;   // msm_segments (msm_seg.hpp): window bits, points per tile, segments per chunk; 0 = the defaults
+  DevBuf sg_wsum, sg_stage, sg_prefix, sg_ids, sg_offs;   // one chunk of msm_segments: window sums, results in XYZZ, scratch, class lists; the call's offsets
+  DevBuf sg_points, sg_scalars, sg_out;                   // host-pointer calls: the staged points / scalars / packed output images
+  hipEvent_t sg_ev[2] = {nullptr, nullptr};
+  uint64_t last_segments_us = 0, last_segments_device_us = 0;
+  long opt_fft_points_chunk = 0;               // butterflies (table points) per chunk of fft_points (msm_gfft.hpp); 0 = the default
   DevBuf gf_stage, gf_rec, gf_prefix, gf_inf;   // one chunk of fft_points: table entries in XYZZ (then the chunk's results), their records, scratch, flags
   DevBuf gf_vec[2];                             // the vector between two stages: packed Affine images
   DevBuf gf_points, gf_out;                     // host-pointer calls: the staged input / the packed output images
@@ -2260,8 +2266,11 @@ RustError mi355_msm_destroy(mi355_msm_ctx* ctx) {
     DevBuf* bufs[] = {&ctx->bases, &ctx->inf, &ctx->scalars, &ctx->te_bases, &ctx->flags, &ctx->stateless_raw[0], &ctx->stateless_raw[1], &ctx->stateless_raw[2],
                       &ctx->codec_in, &ctx->codec_out, &ctx->codec_stat[0], &ctx->codec_stat[1],
                       &ctx->pm_stage, &ctx->pm_rec, &ctx->pm_prefix, &ctx->pm_inf, &ctx->pm_points, &ctx->pm_scalars, &ctx->pm_out,
-                      &ctx->gf_stage, &ctx->gf_rec, &ctx->gf_prefix, &ctx->gf_inf, &ctx->gf_vec[0], &ctx->gf_vec[1], &ctx->gf_points, &ctx->gf_out};
+                      &ctx->gf_stage, &ctx->gf_rec, &ctx->gf_prefix, &ctx->gf_inf, &ctx->gf_vec[0], &ctx->gf_vec[1], &ctx->gf_points, &ctx->gf_out,
+                      &ctx->sg_wsum, &ctx->sg_stage, &ctx->sg_prefix, &ctx->sg_ids, &ctx->sg_offs, &ctx->sg_points, &ctx->sg_scalars, &ctx->sg_out};
     for (DevBuf* b : bufs) b->release();
+    for (auto& ev : ctx->sg_ev)
+      if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : ctx->pm_ev)
       if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : ctx->gf_ev)
@@ -2542,6 +2551,19 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value) 
       // window bits of pairwise mul_points (0 = the default, 4); results do not depend on it: a test hook
       if (value < 0 || value > 6) bad_arg("mul_window %ld out of range [1, 6] (0 = the default)", value);
       ctx->opt_mul_window = value;
+    } else if (k == "seg_window") {
+      // window bits of msm_segments (0 = by the segment's length: seg_msm.hpp); results do not depend on it: a test hook
+      if (value < 0 || value > (long)SM_MAX_WINDOW) bad_arg("seg_window %ld out of range [1, %u] (0 = by length)", value, SM_MAX_WINDOW);
+      ctx->opt_seg_window = value;
+    } else if (k == "seg_tile") {
+      // points per sorting tile of msm_segments (0 = the default, 1024); results do not depend on it: a test puts tile edges at small lengths
+      if (value != 0 && (value < (long)SM_MIN_TILE || value > (long)SM_MAX_TILE || (value & (value - 1))))
+        bad_arg("seg_tile %ld is not a power of two in [%u, %u] (0 = the default)", value, SM_MIN_TILE, SM_MAX_TILE);
+      ctx->opt_seg_tile = value;
+    } else if (k == "seg_chunk") {
+      // segments per chunk of msm_segments (0 = as many as the work memory allows); results do not depend on it: a test puts seams at small calls
+      if (value < 0 || value >= (1l << 31)) bad_arg("seg_chunk %ld out of range [0, 2^31)", value);
+      ctx->opt_seg_chunk = value;
     } else if (k == "fft_points_chunk") {
       // butterflies per chunk of fft_points (0 = the default: msm_gfft.hpp); results do not depend on it: a test puts seams at small n
       if (value < 0 || value >= (1l << 31)) bad_arg("fft_points_chunk %ld out of range [0, 2^31)", value);
@@ -2708,6 +2730,19 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
       *value = pmul_chunk(ctx);
     else if (k == "mul_work_bytes")
       *value = ctx->pm_stage.bytes + ctx->pm_rec.bytes + ctx->pm_prefix.bytes + ctx->pm_inf.bytes + ctx->pm_points.bytes + ctx->pm_scalars.bytes + ctx->pm_out.bytes;
+    else if (k == "seg_window")
+      *value = (uint64_t)ctx->opt_seg_window;
+    else if (k == "seg_tile")
+      *value = ctx->opt_seg_tile > 0 ? (uint64_t)ctx->opt_seg_tile : SM_DEFAULT_TILE;
+    else if (k == "seg_chunk")
+      *value = (uint64_t)ctx->opt_seg_chunk;
+    else if (k == "seg_work_bytes")
+      *value = ctx->sg_wsum.bytes + ctx->sg_stage.bytes + ctx->sg_prefix.bytes + ctx->sg_ids.bytes + ctx->sg_offs.bytes + ctx->sg_points.bytes +
+               ctx->sg_scalars.bytes + ctx->sg_out.bytes;
+    else if (k == "last_segments_us")
+      *value = ctx->last_segments_us;
+    else if (k == "last_segments_device_us")
+      *value = ctx->last_segments_device_us;
     else if (k == "fft_points_chunk")
       *value = gfft_chunk(ctx);
     else if (k == "fft_points_work_bytes")
@@ -2989,3 +3024,4 @@ const char* mi355_msm_version(void) { return "mi355-msm 0.4 (gfx950)"; }
 #include "msm_gfft.hpp"
 #include "msm_lookup.hpp"
 #include "msm_expr.hpp"
+#include "msm_seg.hpp"

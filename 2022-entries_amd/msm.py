@@ -115,6 +115,7 @@ def load_library() -> ctypes.CDLL:
         "mi355_msm_point_to_compressed": [ci, vp, vp],
         "mi355_msm_mul_points": [vp, vp, sz, sz, vp, sz, ctypes.c_uint, vp, sz],
         "mi355_msm_mul_points_device": [vp, vp, sz, sz, vp, sz, ctypes.c_uint, vp, sz, vp],
+        "mi355_msm_segments": [vp, vp, sz, sz, vp, sz, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.c_uint, vp, sz, vp],
         "mi355_msm_fft_points": [vp, vp, vp, sz, vp, sz, sz, ctypes.c_uint, ctypes.c_uint, vp],
         "mi355_msm_fft_points_device": [vp, vp, vp, sz, vp, sz, sz, ctypes.c_uint, ctypes.c_uint, vp, vp],
         "mi355_msm_last_stateless": [ctypes.POINTER(ctypes.c_double), sz],
@@ -539,6 +540,43 @@ class MultiScalarMultContext:
         scalars) are read in place on the current torch stream and give a GPU tensor, ready for ``set_bases``."""
         return self._mul_points(points, _Buf(scalars), SCALAR_BYTES, (1 if montgomery else 0) | (2 if projective else 0), stride, out_stride)
 
+    def msm_segments(self, points, scalars, offsets=None, shared: bool = False, montgomery: bool = False, projective: bool = False,
+                     stride: Optional[int] = None, out_stride: Optional[int] = None, out=None, lengths=None):
+        """Many small MSMs in one call (mi355_msm_segments): ``out[s] = sum of scalars[i] * points[i]`` over
+        ``offsets[s] <= i < offsets[s + 1]``; an empty segment gives the point at infinity.  ``offsets``: any integer sequence or array
+        of S + 1 values, 0 first, non-decreasing, the number of points last (``lengths``: the S segment lengths instead); always taken
+        to the host.  ``shared=True``: ``scalars`` is ``(S, L, 32)`` and every segment runs over all L ``points``.  ``points``: Affine
+        images ``stride`` bytes apart, read as ``mul_points`` reads them (the flag byte is authoritative, no curve or subgroup test).
+        ``scalars``: 32-byte little-endian integers, all 256 bits significant; ``montgomery``: arkworks ``Fr`` images.  Affine images out
+        (``projective``: normalised Projective images), ``out_stride`` bytes apart.  bytes / NumPy / torch CPU in give the same kind
+        out; GPU tensors (points and scalars) are read in place on the current torch stream and give a GPU tensor (``out``: a GPU
+        uint8 tensor of S * out_stride bytes to write into), ready for ``set_bases``, ``fft_points`` and ``compress_points``."""
+        import numpy as np
+
+        a = _segments_args(self.curve, points, scalars, offsets, lengths, shared, projective, stride, out_stride, out)
+        b, sc, offs, nseg, npoints, nscalars, stride, out_stride = a
+        self._check_device(b, "points")
+        self._check_device(sc, "scalars")
+        flags = (1 if montgomery else 0) | (2 if b.is_device else 0) | (4 if shared else 0) | (8 if projective else 0)
+        optr = None if offs is None else offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+        if b.is_device:
+            import torch
+
+            if out is None:
+                out = torch.zeros((nseg, out_stride), dtype=torch.uint8, device=b.keep.device)
+            else:
+                ob = _Buf(out)
+                self._check_device(ob, "out")
+            if nseg:
+                _check(self._lib.mi355_msm_segments(self.context, b.ptr if npoints else None, npoints, stride, sc.ptr if nscalars else None, nscalars, optr, nseg,
+                                                    flags, out.data_ptr(), out_stride, b.stream))
+            return out
+        o = np.zeros(nseg * out_stride, dtype=np.uint8)
+        if nseg:
+            _check(self._lib.mi355_msm_segments(self.context, b.ptr if npoints else None, npoints, stride, sc.ptr if nscalars else None, nscalars, optr, nseg,
+                                                flags, o.ctypes.data, out_stride, None))
+        return _like_input(points, o, (nseg, out_stride))
+
     def mul_points_by(self, points, k, projective: bool = False, stride: Optional[int] = None, out_stride: Optional[int] = None):
         """``out[i] = k * points[i]`` for ONE integer k of up to 512 bits (an int, or little-endian bytes whose length is a multiple of 4
         from 4 to 64): no table, one doubling per bit and one addition per non-zero digit of k's non-adjacent form."""
@@ -779,6 +817,88 @@ def mul_points(points, scalars, curve="bls12_377_g1", montgomery: bool = False, 
     """MultiScalarMultContext.mul_points on a throwaway context (on the tensor's device for a GPU tensor)."""
     return _throwaway(points, curve, device, lambda c: c.mul_points(points, scalars, montgomery=montgomery, projective=projective, stride=stride,
                                                                    out_stride=out_stride))
+
+
+def _segments_args(cid, points, scalars, offsets, lengths, shared, projective, stride, out_stride, out):
+    """The argument checks of msm_segments, all on the host and before any GPU work: (points _Buf, scalars _Buf, offsets as a uint64
+    array or None, segments, points, scalars, stride, out_stride)."""
+    import numpy as np
+
+    size = projective_bytes(cid) if projective else affine_stride(cid)
+    stride = affine_stride(cid) if stride is None else int(stride)
+    out_stride = size if out_stride is None else int(out_stride)
+    if stride % 4 or stride < 2 * (projective_bytes(cid) // 3) + 1:
+        raise ValueError(f"stride {stride} must be a multiple of 4 and hold two coordinates and the flag byte")
+    if out_stride % 4 or out_stride < size:
+        raise ValueError(f"out_stride {out_stride} must be a multiple of 4 and at least the {size}-byte image")
+    b, sc = _Buf(points), _Buf(scalars)
+    if b.nbytes % stride:
+        raise ValueError(f"points image of {b.nbytes} bytes is not a multiple of the {stride}-byte stride")
+    if sc.nbytes % SCALAR_BYTES:
+        raise ValueError(f"scalars of {sc.nbytes} bytes are not a multiple of {SCALAR_BYTES}")
+    if sc.is_device != b.is_device:
+        raise TypeError("points and scalars must both be host data or both be GPU tensors")
+    npoints, nscalars = b.nbytes // stride, sc.nbytes // SCALAR_BYTES
+    if npoints >= 1 << 32:
+        raise ValueError(f"{npoints} points exceed 2^32-1")
+    if shared:
+        if offsets is not None or lengths is not None:
+            raise ValueError("shared=True takes neither offsets nor lengths: every segment runs over all points")
+        shape = tuple(getattr(scalars, "shape", ()))
+        if len(shape) == 3 and shape[1] != npoints:
+            raise ValueError(f"shared=True takes scalars of shape (S, {npoints}, 32), not {shape}")
+        if npoints == 0:
+            if len(shape) != 3:
+                raise ValueError("shared=True with no points takes scalars of shape (S, 0, 32): the number of segments is its first dimension")
+            nseg = int(shape[0])
+        else:
+            if nscalars % npoints:
+                raise ValueError(f"shared=True: {nscalars} scalars are not a multiple of the {npoints} points")
+            nseg = nscalars // npoints
+        offs = None
+    else:
+        if (offsets is None) == (lengths is None):
+            raise ValueError("pass offsets (S + 1 values) or lengths (S values), one of them")
+        src = offsets if offsets is not None else lengths
+        if hasattr(src, "detach"):
+            src = src.detach().cpu().numpy()
+        arr = np.asarray(src)
+        if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+            raise ValueError("offsets / lengths must be a one-dimensional integer sequence")
+        if arr.size and int(arr.min()) < 0:
+            raise ValueError("offsets / lengths must not be negative")
+        arr = arr.astype(np.uint64)
+        if offsets is None:
+            arr = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(arr, dtype=np.uint64)])
+        if arr.size == 0:
+            raise ValueError("offsets hold S + 1 values: at least the leading 0")
+        if int(arr[0]) != 0:
+            raise ValueError(f"offsets[0] = {int(arr[0])}: the first offset must be 0")
+        down = np.nonzero(arr[1:] < arr[:-1])[0]
+        if down.size:
+            i = int(down[0]) + 1
+            raise ValueError(f"offsets[{i}] = {int(arr[i])} is smaller than offsets[{i - 1}] = {int(arr[i - 1])}: offsets must not decrease")
+        if int(arr[-1]) != npoints:
+            raise ValueError(f"offsets[{arr.size - 1}] = {int(arr[-1])}: the last offset must equal the {npoints} points")
+        if nscalars != npoints:
+            raise ValueError(f"{npoints} points need {npoints} scalars, not {nscalars}")
+        offs = np.ascontiguousarray(arr)
+        nseg = arr.size - 1
+    if out is not None:
+        if not b.is_device:
+            raise TypeError("out= goes with GPU tensors; host inputs return a new container")
+        if not (hasattr(out, "is_cuda") and out.is_cuda and out.is_contiguous() and out.numel() == nseg * out_stride):
+            raise ValueError(f"out must be a contiguous GPU uint8 tensor of {nseg} * {out_stride} bytes")
+    return b, sc, offs, nseg, npoints, nscalars, stride, out_stride
+
+
+def msm_segments(points, scalars, offsets=None, curve="bls12_377_g1", shared: bool = False, montgomery: bool = False, projective: bool = False,
+                 stride: Optional[int] = None, out_stride: Optional[int] = None, out=None, lengths=None, device: Optional[int] = None):
+    """MultiScalarMultContext.msm_segments on a throwaway context (on the tensor's device for a GPU tensor); the arguments are judged
+    before the context is made."""
+    _segments_args(_curve_id(curve), points, scalars, offsets, lengths, shared, projective, stride, out_stride, out)
+    return _throwaway(points, curve, device, lambda c: c.msm_segments(points, scalars, offsets, shared=shared, montgomery=montgomery, projective=projective,
+                                                                     stride=stride, out_stride=out_stride, out=out, lengths=lengths))
 
 
 def mul_points_by(points, k, curve="bls12_377_g1", projective: bool = False, stride: Optional[int] = None, out_stride: Optional[int] = None,

@@ -1043,6 +1043,45 @@ RustError mi355_msm_expr_run(mi355_msm_expr* e, void* out, const void* const* co
 RustError mi355_msm_expr_query(mi355_msm_expr* e, const char* key, uint64_t* value);
 RustError mi355_msm_expr_destroy(mi355_msm_expr* e);
 
+/* ---- segmented MSM: many small MSMs in one call ------------------------------------------------------------------------------------
+ * S independent sums in one launch chain -- the h-vector of FK20 / PeerDAS cell proofs (128 MSMs of 64 points per blob), the short
+ * columns of a circuit over one SRS, IPA and Verkle rounds, committee key aggregation.  mi355_msm_run is built for one sum of 2^20 to
+ * 2^26 pairs; this call for sums of 1 to a few thousand terms (longer segments are legal and slow: they are mi355_msm_run's job).
+ *   general  (flag bit 2 clear) `offsets` is a HOST array of nsegments + 1 values, offsets[0] = 0, non-decreasing,
+ *            offsets[nsegments] = npoints = nscalars;  out[s] = sum over i in [offsets[s], offsets[s+1]) of scalars[i] * points[i].
+ *            An empty segment gives the point at infinity.  `offsets` is host memory also with device pointers: it is the shape of
+ *            the call, and the launch plan is built from it.
+ *   shared   (flag bit 2, value 4) `offsets` must be NULL and nscalars = nsegments * npoints;
+ *            out[s] = sum over i < npoints of scalars[s * npoints + i] * points[i]: one set of bases serves every member.
+ *   points   Affine images `stride` bytes apart, read exactly as mi355_msm_mul_points reads them: the flag byte is authoritative,
+ *            infinities are allowed anywhere, no curve test and no subgroup test.  A record on no curve gives an unspecified result;
+ *            the call still finishes without a fault.
+ *   scalars  32-byte little-endian integers; all 256 bits count, nothing is reduced modulo r.  Flag bit 0 (value 1): arkworks Fr
+ *            images, converted first.
+ *   out      one image per segment, out_stride bytes apart (a multiple of 4, at least the image size).  Default: Affine images with
+ *            every flag and pad byte written, as mi355_msm_mul_points writes them -- ready for set_bases, fft_points,
+ *            compress_points and the pairing calls.  Flag bit 3 (value 8): normalised Projective images, the bytes mi355_msm_run
+ *            returns.  `out` must not overlap an input.
+ *   pointers flag bit 1 (value 2): points, scalars and out are DEVICE pointers (4-byte aligned) and `stream` is the hipStream_t on
+ *            which they become ready (NULL = the default stream); the work is enqueued there and the call returns when the output is
+ *            written.  Without bit 1 they are host pointers and a non-null stream is an error; the points, the scalars and the
+ *            packed output are staged WHOLE in device buffers the context keeps (npoints * stride + 32 * nscalars bytes: unlike
+ *            mul_points the call is not chunked over its inputs, only over its segments' work memory), so a call near the 2^32
+ *            limit belongs to the device-pointer form.
+ * The bytes of out[s] depend on the pairs of segment s alone: never on the window size, the tile length, the chunking, the pointer
+ * kind, the form, or what the neighbouring segments hold.  nsegments = 0 succeeds and writes nothing.
+ * Options (mi355_msm_set_option; test hooks, readable through mi355_msm_query): "seg_window" 1..9 (0 = by the segment's length:
+ * 4 up to 256 pairs, 5 up to 768, 6 up to 2560, 7 up to 8192, 8 up to 16384, 9 beyond), "seg_tile" (an UPPER BOUND on the points per sorting tile, a
+ * power of two from 64 to 4096; 0 = 1024: a class of segments runs with the largest power of two that is within it, within 20 KiB
+ * of LDS a block and not longer than its longest segment needs -- at most 256 at window size 4, 512 at 5), "seg_chunk" (segments per chunk; 0 = as many as 2 GiB of work memory hold).  Queries also:
+ * "seg_work_bytes", "last_segments_us", "last_segments_device_us".
+ * Errors: -1 with a message that names the argument -- null pointers where a length is non-zero, a stride too small or not a multiple
+ * of 4, offsets that do not start at 0, that decrease or that do not end at npoints (the message names the first offending index),
+ * the shared form with offsets or a wrong nscalars, npoints >= 2^32, unknown flag bits, out overlapping an input, a sharded context,
+ * a stream with host pointers -- decided before any device call; hipErrorNoDevice without a GPU. */
+RustError mi355_msm_segments(mi355_msm_ctx* ctx, const void* points, size_t npoints, size_t stride, const void* scalars, size_t nscalars,
+                             const uint64_t* offsets, size_t nsegments, unsigned flags, void* out, size_t out_stride, void* stream);
+
 /* Sum `count` projective images (any Z) into one normalised image: the multi-GPU combine step
  * ("final 8-point curve add").  Pure host arithmetic on <= a few dozen points; no device needed. */
 RustError mi355_msm_fold(int curve, void* out_projective, const void* projective, size_t count);

@@ -163,6 +163,11 @@ pub mod sys {
                                     scalar_bytes: usize, flags: c_uint, out: *mut c_void, out_stride: usize) -> Error;
         pub fn mi355_msm_mul_points_device(ctx: *mut c_void, d_points: *const c_void, npoints: usize, stride: usize, scalars: *const c_void,
                                            scalar_bytes: usize, flags: c_uint, d_out: *mut c_void, out_stride: usize, stream: *mut c_void) -> Error;
+        /// S independent sums in one call: out[s] = sum of scalars[i] * points[i] over segment s.  General form: `offsets` is a HOST array
+        /// of nsegments + 1 values (0 first, non-decreasing, npoints last).  Flags: bit 0 Fr images, bit 1 DEVICE pointers and a stream,
+        /// bit 2 the shared form (`offsets` null, nscalars = nsegments * npoints, every segment over all points), bit 3 Projective images.
+        pub fn mi355_msm_segments(ctx: *mut c_void, points: *const c_void, npoints: usize, stride: usize, scalars: *const c_void, nscalars: usize,
+                                  offsets: *const u64, nsegments: usize, flags: c_uint, out: *mut c_void, out_stride: usize, stream: *mut c_void) -> Error;
         pub fn mi355_msm_shard_timings(ctx: *mut c_void, shard: c_int, ms: *mut f32, info: *mut u64) -> Error;
         pub fn mi355_msm_last_stateless(out: *mut f64, count: usize) -> Error;
         pub fn mi355_msm_trim() -> Error;
@@ -1251,5 +1256,50 @@ pub mod mle {
                                                    if r_prev.is_some() { fptrs.as_ptr() } else { std::ptr::null() }, 0, std::ptr::null_mut()));
         evals.truncate(d + 1);
         (evals, folded)
+    }
+}
+
+/// Many small MSMs in one call (`mi355_msm_segments`): the h-vector of FK20, the short columns of a circuit over one SRS, IPA rounds.
+pub mod segments {
+    use super::sys;
+    use super::{Fr, G1Affine};
+    use ark_std::Zero;
+    use std::os::raw::c_void;
+
+    fn check(err: super::Error) {
+        if err.code != 0 {
+            panic!("{}", String::from(err));
+        }
+    }
+
+    /// `out[s] = sum over offsets[s] <= i < offsets[s + 1] of scalars[i] * points[i]`; an empty segment gives the point at infinity.
+    ///
+    /// # Safety
+    /// `ctx` is a live single-device context of `sys::mi355_msm_create` over the curve of `G1Affine`.
+    pub unsafe fn msm_segments(ctx: *mut c_void, points: &[G1Affine], scalars: &[Fr], offsets: &[u64]) -> Vec<G1Affine> {
+        assert!(!offsets.is_empty(), "offsets hold one value more than there are segments");
+        assert_eq!(points.len(), scalars.len(), "one scalar per point");
+        assert_eq!(offsets[0], 0, "offsets start at 0");
+        assert!(offsets.windows(2).all(|w| w[0] <= w[1]), "offsets must not decrease");
+        assert_eq!(*offsets.last().unwrap() as usize, points.len(), "offsets end at the number of points");
+        let nseg = offsets.len() - 1;
+        let mut out = vec![G1Affine::zero(); nseg];
+        check(sys::mi355_msm_segments(ctx, points.as_ptr() as *const c_void, points.len(), std::mem::size_of::<G1Affine>(),
+                                      scalars.as_ptr() as *const c_void, scalars.len(), offsets.as_ptr(), nseg, 1,
+                                      out.as_mut_ptr() as *mut c_void, std::mem::size_of::<G1Affine>(), std::ptr::null_mut()));
+        out
+    }
+
+    /// The shared form: `scalars` holds `nsegments` rows of `points.len()` values, `out[s] = sum_i scalars[s][i] * points[i]`.
+    ///
+    /// # Safety
+    /// as `msm_segments`
+    pub unsafe fn msm_segments_shared(ctx: *mut c_void, points: &[G1Affine], scalars: &[Fr], nsegments: usize) -> Vec<G1Affine> {
+        assert_eq!(scalars.len(), nsegments * points.len(), "nsegments rows of one scalar per point");
+        let mut out = vec![G1Affine::zero(); nsegments];
+        check(sys::mi355_msm_segments(ctx, points.as_ptr() as *const c_void, points.len(), std::mem::size_of::<G1Affine>(),
+                                      scalars.as_ptr() as *const c_void, scalars.len(), std::ptr::null(), nsegments, 1 | 4,
+                                      out.as_mut_ptr() as *mut c_void, std::mem::size_of::<G1Affine>(), std::ptr::null_mut()));
+        out
     }
 }
