@@ -2820,3 +2820,62 @@ int ht_sm_geometry(int c, int tile_opt, uint64_t maxlen, int xyzz_words, uint32_
 }
 int ht_sm_window_for(uint64_t len) { return (int)sm_window_for(len); }
 }
+
+// ---- Entries32 (msm_types.hpp): the sorted entry stream written and read back with the format's own helpers ----------------------
+// The writer restates what the last grouping pass does (partition.hpp): a block sees one segment -- the keys [seg_keys[s],
+// seg_keys[s + 1]) -- and gives the first entry of every non-empty bin its distance to the previous non-empty bin of the SAME segment,
+// an escape for the segment's first bin and for gaps above 30 (every run start when seg_subjobs[s] != 0: a segment cut into
+// sub-jobs), and the key of every lane start in run_keys.  The reader is the accumulation's walk, lane by lane.
+#include "msm_types.hpp"
+
+extern "C" {
+// keys[n] non-decreasing, values[n] = base index | sign << 31; run_keys[n] is written only where the format needs it (the caller
+// pre-fills it to see where).  Returns the number of escapes, -1 for bad arguments (unsorted keys, a key below the first segment, K = 0).
+long ht_e32_encode(const uint32_t* keys, const uint32_t* values, size_t n, uint32_t K, const uint32_t* seg_keys, const uint8_t* seg_subjobs, size_t nseg,
+                   uint32_t* words, uint32_t* run_keys) {
+  if (K == 0 || nseg == 0 || !seg_keys || (n && (!keys || !values || !words || !run_keys))) return -1;
+  long escapes = 0;
+  size_t seg = 0, prev_seg = (size_t)-1;
+  for (size_t i = 0; i < n; i++) {
+    if (i && keys[i] < keys[i - 1]) return -1;
+    if (keys[i] < seg_keys[0]) return -1;
+    while (seg + 1 < nseg && seg_keys[seg + 1] <= keys[i]) seg++;
+    uint32_t step = 0;
+    if (i == 0 || keys[i] != keys[i - 1]) {
+      const bool first_of_segment = seg != prev_seg;
+      step = e32_step_of_gap(first_of_segment ? 0u : keys[i] - keys[i - 1], first_of_segment || (seg_subjobs && seg_subjobs[seg]));
+      prev_seg = seg;
+    }
+    words[i] = e32_pack(values[i], step);
+    if (step == E32_ESCAPE) {
+      run_keys[i] = keys[i];
+      escapes++;
+    }
+  }
+  // the lane starts, run by run: the multiples of K inside [start of the run, its end)
+  for (size_t i = 0; i < n;) {
+    size_t j = i;
+    while (j < n && keys[j] == keys[i]) j++;
+    for (uint64_t q = e32_first_lane_start((uint32_t)i, K); q < j; q += K) run_keys[q] = keys[i];
+    i = j;
+  }
+  return escapes;
+}
+// the walk of lane t over [t K, (t + 1) K): keys_out[n]; continued[t] = 1 when the lane's first entry continues the bucket of the lane before
+int ht_e32_decode(const uint32_t* words, const uint32_t* run_keys, size_t n, uint32_t K, uint32_t* keys_out, uint32_t* values_out, uint8_t* continued) {
+  if (K == 0) return -1;
+  for (size_t beg = 0, t = 0; beg < n; beg += K, t++) {
+    const size_t end = beg + K < n ? beg + K : n;
+    uint32_t cur = run_keys[beg];
+    if (continued) continued[t] = e32_step(words[beg]) == 0;
+    for (size_t i = beg; i < end; i++) {
+      if (i > beg) cur = e32_next_key(cur, words[i], run_keys, (uint32_t)i);
+      keys_out[i] = cur;
+      values_out[i] = (words[i] & 0x80000000u) | e32_index(words[i]);
+    }
+  }
+  return 0;
+}
+uint32_t ht_e32_run_keys_offset(uint64_t capacity) { return e32_run_keys_offset(capacity); }
+int ht_e32_applies(uint64_t idx0, uint64_t n, uint32_t table_levels) { return e32_applies(idx0, n, table_levels) ? 1 : 0; }
+}

@@ -62,8 +62,9 @@ template <class G>
 struct WalkLaunch {
   using El = typename LawMem<G>::MemT;
   using BaseDev = typename LawMem<G>::BaseDev;
+  // `e32_rk_off` != 0: the entries are Entries32 words (msm_types.hpp) and run_keys starts that many words into the buffer
   static hipError_t accumulate(const uint2* entries, const uint32_t* n_real, uint32_t K, const BaseDev* bases, SegOutT<El> out, uint32_t nlanes,
-                               uint32_t* flags, hipStream_t st);
+                               uint32_t* flags, uint32_t e32_rk_off, hipStream_t st);
   // anchored window: one fragment per lane of the plain sum of bases [first, first + n) (k_sum_bases)
   static hipError_t sum_bases(const BaseDev* bases, const uint8_t* inf, uint32_t first, uint32_t n, uint32_t per_lane, SegOutT<El> out, uint32_t nlanes,
                               uint32_t* flags, hipStream_t st);

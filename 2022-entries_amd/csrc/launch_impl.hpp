@@ -63,11 +63,20 @@ uint32_t walk_blocks(uint64_t walkers) {
 
 template <class G>
 hipError_t WalkLaunch<G>::accumulate(const uint2* entries, const uint32_t* n_real, uint32_t K, const BaseDev* bases, SegOutT<El> out, uint32_t nlanes,
-                                     uint32_t* flags, hipStream_t st) {
+                                     uint32_t* flags, uint32_t e32_rk_off, hipStream_t st) {
   // MSM_GATHER = 0 builds the one-lane-per-record walk of the XYZZ laws instead (A/B: profiles/r02_ab_gather.txt)
 #ifndef MSM_GATHER
 #define MSM_GATHER 2
 #endif
+  if (e32_rk_off) {
+    const uint32_t* const words = reinterpret_cast<const uint32_t*>(entries);
+    const Entries32Ptr e32{words, words + e32_rk_off};
+    if constexpr (MSM_GATHER == 2 || !kIsSwLaw<G>)
+      hipLaunchKernelGGL((k_accumulate_glds<G, Entries32>), dim3(walk_blocks<G>(nlanes)), dim3(256), 0, st, e32, n_real, K, bases, out, nlanes, flags);
+    else
+      hipLaunchKernelGGL((k_accumulate<G, Entries32>), dim3(walk_blocks<G>(nlanes)), dim3(256), 0, st, e32, n_real, K, bases, out, nlanes, flags);
+    return hipGetLastError();
+  }
   if constexpr (MSM_GATHER == 2 || !kIsSwLaw<G>)
     hipLaunchKernelGGL((k_accumulate_glds<G>), dim3(walk_blocks<G>(nlanes)), dim3(256), 0, st, entries, n_real, K, bases, out, nlanes, flags);
   else
@@ -146,7 +155,7 @@ hipError_t WalkLaunch<G>::bucket_merge(XyzzDevT<El>* total, const XyzzDevT<El>* 
   using S_ = SegOutT<E::T>;                                                                                                                      \
   using W_ = WalkLaunch<SwLaw<E>>;                                                                                                               \
   template hipError_t Launch<E>::convert_bases(const uint8_t*, size_t, uint32_t, bool, A_*, uint8_t*, hipStream_t);                              \
-  template hipError_t W_::accumulate(const uint2*, const uint32_t*, uint32_t, const A_*, S_, uint32_t, uint32_t*, hipStream_t);                  \
+  template hipError_t W_::accumulate(const uint2*, const uint32_t*, uint32_t, const A_*, S_, uint32_t, uint32_t*, uint32_t, hipStream_t);        \
   template hipError_t W_::segreduce(const X_*, const uint32_t*, uint32_t, uint32_t, S_, uint32_t, uint32_t, uint32_t*, hipStream_t);             \
   template hipError_t Launch<E>::pre_double(const A_*, const uint8_t*, uint32_t, uint32_t, X_*, hipStream_t);                                    \
   template hipError_t Launch<E>::pre_normalize(const X_*, uint32_t, uint32_t, E::T*, A_*, uint8_t*, hipStream_t);                                \

@@ -377,6 +377,8 @@ struct Plan {
   uint32_t levels;          // table levels in use (1 = none)
   uint32_t anchor;          // the anchored window (kNoAnchor: plain signed digits)
   bool wide;                // ... which also carries the scalar's top bit (anchor_wide_fits): bucket set anchor + 1 holds its large magnitudes
+  bool e32;                 // the sorted entries may be Entries32 words (msm_types.hpp): the option is on, no tables, at most 2^26 pairs (run_chunk_impl
+                            // adds the condition on the chunk's base indices)
   uint64_t entries;     // windows * n
   uint32_t K, nlanes;   // accumulate geometry
   uint32_t segK;        // fragment-merge fan-in
@@ -389,6 +391,11 @@ struct Plan {
 };
 
 }  // namespace
+
+// option "entries32": the default (profiles/ab_entries32.txt)
+#ifndef MSM_ENTRIES32_DEFAULT
+#define MSM_ENTRIES32_DEFAULT 1
+#endif
 
 #ifndef MSM_G2_PAIRED_DEFAULT
 #define MSM_G2_PAIRED_DEFAULT 31
@@ -459,6 +466,8 @@ struct mi355_msm_ctx {
   uint32_t wide_streak = 0;
   uint64_t wide_fallbacks = 0, wide_demotions = 0;
   bool last_wide = false;         // the most recent chunk ran with it
+  long opt_entries32 = MSM_ENTRIES32_DEFAULT;   // option "entries32": 1 = the last grouping pass writes 32-bit entries with run steps (msm_types.hpp) where they apply
+  bool last_e32 = false;          // the most recent chunk ran on them ("entries32_active")
   DevBuf wide_flag, wide_r;       // the device flag word of k_l1_hist; direct scan: the plain sum of bucket set anchor + 1
   uint32_t* h_wide_flag = nullptr;   // pinned copy (k_collect_sums)
   long opt_reduce_log_chunk = 0, opt_reduce_log_chunk0 = 0;
@@ -533,6 +542,7 @@ struct mi355_msm_ctx {
     p.anchor = anchor_armed ? anchor_window((int)p.c, scalar_bits(), opt_anchor == 2) : kNoAnchor;
     p.wide = wide_wanted() && !tables && anchor_wide_fits(p.anchor, (int)p.c, scalar_bits());
     p.windows = (257 + p.c - 1) / p.c;
+    p.e32 = opt_entries32 != 0 && !tables && n <= ((size_t)1 << E32_IDX_BITS);
     p.levels = tables ? std::min<uint32_t>(pre_windows, p.windows) : 1;
     p.bucket_windows = ceil_div(p.windows, p.levels);
     p.levels = ceil_div(p.windows, p.bucket_windows);
@@ -576,7 +586,7 @@ struct mi355_msm_ctx {
         double best_fill = fill(best);
         for (long step = 8; step <= 96 && best_fill < 0.985; step += 8)
           for (long k : {(long)K - step, (long)K + step})
-            if (k >= 64 && fill(k) > best_fill + 0.004) {
+            if (k >= 64 && (!p.e32 || k % 16 == 0) && fill(k) > best_fill + 0.004) {
               best = k;
               best_fill = fill(k);
             }
@@ -584,6 +594,7 @@ struct mi355_msm_ctx {
       }
     }
     p.K = K >= 8 ? (K + 7) & ~7u : (K + 3) & ~3u;   // a lane's entries start on a 64-byte boundary (k_accumulate_glds refills its entry queue by whole sectors)
+    if (p.e32 && !opt_lane_entries && p.K >= 16) p.K = (p.K + 15) & ~15u;   // ... which hold 16 Entries32 words (a forced K stays: 16-byte loads work from any multiple of 4)
     p.nlanes = ceil_div(p.entries, p.K);
     p.segK = opt_seg_entries >= 4 ? (uint32_t)opt_seg_entries : (p.entries < (2u << 20) ? 4 : 8);   // small inputs: shallower levels (-1..-3 %)
     uint64_t nb = (uint64_t)p.bucket_windows * p.half;
@@ -679,7 +690,7 @@ hipStream_t create_copy_stream() {
 uint64_t work_bytes(const Plan& p, uint64_t el, bool carry = false) {
   const PartPlan pp = part_plan((uint32_t)(p.entries / p.windows), p.c, p.windows, p.levels, 0, 0);
   const PartScratchSizes ps = part_scratch_sizes(pp);
-  return p.entries * 16 + ps.matrix + ps.partial + ps.segs_a + ps.segs_b + ps.subjob_first + ps.counts + ps.totals +
+  return p.entries * 16 + 256 + ps.matrix + ps.partial + ps.segs_a + ps.segs_b + ps.subjob_first + ps.counts + ps.totals +
          (uint64_t)p.bucket_windows * p.half * 224 * el * (carry ? 2 : 1) + 2 * (2ull * p.nlanes) * (224 * el + 4) + (p.scan_direct ? (uint64_t)p.bucket_windows * p.half : 4ull * (p.bucket_windows + (p.wide ? 1 : 0)) * p.scan_nb) * 224 * el;
 }
 
@@ -710,7 +721,7 @@ WorkBytes chunk_work_bytes(const Plan& p, size_t n, bool use_tables, size_t xyzz
   const size_t nbuckets = (size_t)p.bucket_windows * p.half, nslots0 = 2 * (size_t)p.nlanes;
   // direct scan: a second bucket-sized array to ping-pong with; a wide anchored window: one more row, the plain sums of its upper bucket set
   const size_t red0 = p.scan_direct ? nbuckets : (size_t)(p.bucket_windows + (p.wide ? 1 : 0)) * p.scan_nb;
-  w.b[0] = w.b[1] = p.entries * 8 + 64;
+  w.b[0] = w.b[1] = p.entries * 8 + 128;   // 64 bytes of slack behind the entries; Entries32: words, slack, then run_keys from e32_run_keys_offset on
   w.b[2] = gs.matrix;
   w.b[3] = gs.partial;
   w.b[4] = gs.segs_a;
@@ -930,6 +941,7 @@ int precompute_auto_levels(mi355_msm_ctx* ctx, size_t n) {
     tmp.opt_assume_subgroup = ctx->opt_assume_subgroup;
     tmp.opt_anchor = ctx->opt_anchor;
     tmp.opt_anchor_wide = ctx->opt_anchor_wide;
+    tmp.opt_entries32 = ctx->opt_entries32;
     tmp.opt_carry = ctx->opt_carry;
     tmp.opt_lane_entries = ctx->opt_lane_entries;
     tmp.opt_seg_entries = ctx->opt_seg_entries;
@@ -1250,6 +1262,8 @@ void merge_fragments(mi355_msm_ctx* ctx, uint32_t nlanes, uint32_t K, long paire
 template <class G>
 XyzzDevT<typename LawMem<G>::MemT>* accumulate_chunk(mi355_msm_ctx* ctx, const Plan& p, const PartPlan& gp, const PartBuffers& gb, const uint2* entries,
                                                      const BucketCarry* carry, hipStream_t st, hipEvent_t* ev) {
+  // (Entries32: where run_keys starts in the buffer the grouping returned -- the offset its last pass wrote them at)
+  const uint32_t e32_rk_off = gb.e32_lane_k ? e32_run_keys_offset(p.entries) : 0u;
   using El = typename LawMem<G>::MemT;
   using XyzzDev = XyzzDevT<El>;
   const size_t nbuckets = (size_t)p.bucket_windows * p.half;
@@ -1262,7 +1276,7 @@ XyzzDevT<typename LawMem<G>::MemT>* accumulate_chunk(mi355_msm_ctx* ctx, const P
   SegOutT<El> so{ctx->buckets.as<XyzzDev>(), ctx->slots[0].as<XyzzDev>(), ctx->slot_keys[0].as<uint32_t>()};
   so.carry_in = carry_in ? 1u : 0u;
   HIP_OK(walk_form<G>(ctx, 1, false, [&]<class L>() {
-    return WalkLaunch<L>::accumulate(entries, gb.totals, p.K, law_bases<G>(ctx), so, p.nlanes, law_flags<G>(ctx), st);
+    return WalkLaunch<L>::accumulate(entries, gb.totals, p.K, law_bases<G>(ctx), so, p.nlanes, law_flags<G>(ctx), e32_rk_off, st);
   }));
   HIP_OK(hipEventRecord(ev[3], st));
 #ifdef MSM_DEBUG
@@ -1480,6 +1494,9 @@ bool run_chunk_impl(mi355_msm_ctx* ctx, const uint32_t* d_scalars, size_t base0,
   HIP_OK(hipEventRecord(ev[0], st));
   PartBuffers gb{};
   gb.wide_flag = p.wide ? ctx->wide_flag.as<uint32_t>() : nullptr;
+  // Entries32: K is fixed here, before the grouping, and the last pass marks the lane starts for it
+  gb.e32_lane_k = (p.e32 && e32_applies(base0, n, use_tables ? p.levels : 1) && p.K % 4 == 0) ? p.K : 0u;
+  ctx->last_e32 = gb.e32_lane_k != 0;
   const uint2* entries = group_chunk(ctx, d_scalars, gp, gb, st, ev[1]);
   XyzzDev* const bucket_src = accumulate_chunk<G>(ctx, p, gp, gb, entries, carry, st, ev);
   HIP_OK(hipEventRecord(ev[4], st));
@@ -2587,6 +2604,12 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value) 
       ctx->wide_off = false;
       ctx->wide_streak = 0;
       ctx->fitted_chunk = 0;
+    } else if (k == "entries32") {
+      // 1: the last grouping pass writes the sorted entries as 32-bit words whose spare bits carry the key's step from the entry before
+      // (msm_types.hpp, Entries32) wherever a chunk has at most 2^26 pairs, base indices below 2^26 and no precomputed tables; 0: (value, key) pairs
+      if (value < 0 || value > 1) bad_arg("entries32 %ld out of range [0, 1]", value);
+      ctx->opt_entries32 = value;
+      ctx->fitted_chunk = 0;
     } else if (k == "first_piece_div") {
       if (value != 0 && (value < 2 || value > 64)) bad_arg("first_piece_div %ld out of range [2, 64]", value);
       ctx->opt_first_piece_div = value;
@@ -2681,9 +2704,9 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
       //  the per-shard value (the largest, should the slices differ), not the sum over the shards)
       static const char* const kAll[] = {"twisted_edwards", "assume_subgroup", "carry"};
       static const char* const kMean[] = {"table_levels", "table_window_bits"};
-      static const char* const kFirst[] = {"precompute", "g2_paired", "guard_tail", "te_limb_bits", "anchor", "anchor_wide"};
+      static const char* const kFirst[] = {"precompute", "g2_paired", "guard_tail", "te_limb_bits", "anchor", "anchor_wide", "entries32"};
       static const char* const kMax[] = {"bucket_windows", "l1_bits", "l1_bins", "group_passes", "anchored_window", "anchor_sum_us", "anchor_wide_active",
-                                          "reduce_path", "reduce_chunks", "reduce_row"};
+                                          "reduce_path", "reduce_chunks", "reduce_row", "entries32_active"};
       auto in = [&](const char* const* set, size_t n) {
         for (size_t i = 0; i < n; i++)
           if (k == set[i]) return true;
@@ -2693,7 +2716,7 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
         *value = all;
       } else if (in(kMean, 2)) {
         *value = sum / ctx->shards.size();
-      } else if (in(kFirst, 6) || in(kMax, 10)) {
+      } else if (in(kFirst, 7) || in(kMax, 11)) {
         uint64_t first = 0, mx = 0;
         for (size_t g = 0; g < ctx->shards.size(); g++) {
           uint64_t v = 0;
@@ -2706,7 +2729,7 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
           if (g == 0) first = v;
           mx = std::max(mx, v);
         }
-        *value = in(kFirst, 6) ? first : mx;
+        *value = in(kFirst, 7) ? first : mx;
       } else {
         *value = sum;
       }
@@ -2766,6 +2789,10 @@ RustError mi355_msm_query(mi355_msm_ctx* ctx, const char* key, uint64_t* value) 
       *value = (ctx->opt_anchor_wide && !ctx->wide_off) ? 1 : 0;
     else if (k == "anchor_wide_active")  // the most recent chunk ran with a wide anchored window
       *value = ctx->last_wide ? 1 : 0;
+    else if (k == "entries32")
+      *value = ctx->opt_entries32 ? 1 : 0;
+    else if (k == "entries32_active")    // the most recent chunk's sorted entries were Entries32 words
+      *value = ctx->last_e32 ? 1 : 0;
     else if (k == "anchor_wide_fallbacks")   // chunks or batches repeated without it because a scalar had bits above bits(r)
       *value = ctx->wide_fallbacks;
     else if (k == "anchor_wide_demotions")

@@ -103,15 +103,86 @@ __device__ __forceinline__ void carry_begin_run(const SegOutT<typename G::MemT>&
   if (fresh) G::begin_run(acc);
 }
 
+// The format of the sorted entries a walking kernel reads, its second template parameter.
+//   Entries64 (the default): (value = base index | sign << 31, key) pairs.
+//   Entries32: one word per entry, the key as its step from the entry before (msm_types.hpp); `run_keys` holds the keys of the
+//              escapes and of every lane start.  Half the bytes per entry: a 16-byte queue register holds four entries.
+struct Entries64 {
+  static constexpr bool WORD32 = false;
+  static constexpr int PER16 = 2;   // entries in 16 bytes
+  using Word = uint2;
+  using Ptr = const uint2*;
+  static __device__ __forceinline__ const uint2* words(Ptr p) { return p; }
+  static __device__ __forceinline__ uint32_t index(uint32_t value) { return value & IDX_MASK; }
+};
+struct Entries32Ptr {
+  const uint32_t* words;
+  const uint32_t* run_keys;
+};
+struct Entries32 {
+  static constexpr bool WORD32 = true;
+  static constexpr int PER16 = 4;
+  using Word = uint32_t;
+  using Ptr = Entries32Ptr;
+  static __device__ __forceinline__ const uint32_t* words(Ptr p) { return p.words; }
+  static __device__ __forceinline__ uint32_t index(uint32_t value) { return e32_index(value); }
+};
+
 // The hot kernel.  Lane t walks sorted entries [t*K, (t+1)*K): ~K mixed adds, one bucket store per run.
 // The next base is fetched before the current add so the gather latency hides under ~5k VALU ops.
 // G = the group-law policy (laws.hpp); `flags[1]` is raised when the law reports a result it could not compute.
-template <class G>
-__global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate(const uint2* __restrict__ entries, const uint32_t* __restrict__ n_real,
+template <class G, class EF = Entries64>
+__global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate(typename EF::Ptr entries_arg, const uint32_t* __restrict__ n_real,
                                                     uint32_t K, const typename G::BaseDev* __restrict__ bases,
                                                     SegOutT<typename G::T> out, uint32_t nlanes, uint32_t* __restrict__ flags) {
   using E = typename G::E;
   static_assert(G::LANES == 1, "the one-lane-per-record walk has no paired form");
+  if constexpr (EF::WORD32) {
+    // Entries32: the same walk; an entry's key is the key before it plus its step, read from run_keys at the lane's start and at escapes
+    const uint32_t* __restrict__ words = entries_arg.words;
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nlanes) return;
+    typename E::Md md;
+    out.slot_keys[2 * (size_t)t] = KEY_NONE;
+    out.slot_keys[2 * (size_t)t + 1] = KEY_NONE;
+    const uint32_t n_entries = *n_real;
+    const uint64_t beg64 = (uint64_t)t * K;
+    if (beg64 >= n_entries) return;
+    const uint32_t beg = (uint32_t)beg64;
+    const uint32_t end = (n_entries - beg > K) ? beg + K : n_entries;
+    uint32_t w_c = words[beg], w_n = 0;
+    if (end - beg > 1) w_n = words[beg + 1];
+    typename G::Base p_c;
+    if (G::PREFETCH_BASE) p_c = G::from_dev(bases[e32_index(w_c)]);
+    uint32_t cur = KEY_NONE;
+    bool first = true, fresh = true, bad = false;
+    XyzzT<typename G::T> acc;
+    G::set_identity(acc);
+    for (uint32_t e = beg; e < end; e++) {
+      const uint32_t val = w_c;
+      if (!G::PREFETCH_BASE) p_c = G::from_dev(bases[e32_index(val)]);
+      const typename G::Base p = p_c;
+      w_c = w_n;
+      if (G::PREFETCH_BASE && end - e > 1) p_c = G::from_dev(bases[e32_index(w_c)]);
+      if (end - e > 2) w_n = words[e + 2];
+      if (e == beg || e32_step(val) != 0) {
+        if (e != beg) {
+          seg_flush<G>(out, t, nlanes, cur, acc, first, false);
+          first = false;
+        }
+        cur = e == beg ? entries_arg.run_keys[e] : e32_next_key(cur, val, entries_arg.run_keys, e);
+        fresh = true;
+        G::begin_run(acc);
+      }
+      G::madd(acc, p, (val >> 31) != 0, fresh, md);
+      if (G::CHECKS) bad |= G::failed(acc);
+      fresh = false;
+    }
+    if (cur != KEY_NONE) seg_flush<G>(out, t, nlanes, cur, acc, first, true);
+    if (G::CHECKS && bad) flags[1] = 1;
+    return;
+  } else {
+  const uint2* __restrict__ entries = entries_arg;
   const uint32_t t = blockIdx.x * 256 + threadIdx.x;
   if (t >= nlanes) return;
   typename E::Md md;
@@ -160,6 +231,7 @@ __global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate(const uint2* _
   }
   if (cur != KEY_NONE) seg_flush<G>(out, t, nlanes, cur, acc, first, true);
   if (G::CHECKS && bad) flags[1] = 1;
+  }
 }
 
 // The same walk with QUAD-COOPERATIVE gathers done by LDS-DMA (`global_load_lds_dwordx4`: global -> LDS, no VGPR in between).
@@ -178,13 +250,15 @@ __global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate(const uint2* _
 // drained (lgkmcnt(0)) before the next DMA may overwrite the regions.
 typedef __attribute__((address_space(3))) void* msm_lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* msm_gbl_ptr_t;
+typedef uint32_t msm_u32x4_t __attribute__((ext_vector_type(4)));
 
-template <class G>
-__global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate_glds(const uint2* __restrict__ entries, const uint32_t* __restrict__ n_real,
+template <class G, class EF = Entries64>
+__global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate_glds(typename EF::Ptr entries_arg, const uint32_t* __restrict__ n_real,
                                                          uint32_t K, const typename G::BaseDev* __restrict__ bases,
                                                          SegOutT<typename G::MemT> out, uint32_t nlanes, uint32_t* __restrict__ flags) {
   using E = typename G::E;
   using Base = typename G::Base;
+  const typename EF::Word* __restrict__ entries = EF::words(entries_arg);
   // LANES = 2 (SwPairLaw, fp2pair.hpp): walking lane t is the PAIR of hardware lanes 2t, 2t + 1, each holding one half of every Fp2
   // value; both run the code below on the same entries.  A quad then gathers RPQ = 2 records per iteration instead of 4.
   constexpr int LANES = G::LANES, RPQ = 4 / LANES;
@@ -229,24 +303,45 @@ __global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate_glds(const uin
   // the 2^26 launch (profiles/r03_calib_fetch.txt + r03_pmc_k_accumulate.json) against 7 GB of entries.  With EQ > 0 a lane
   // fetches 2 EQ entries at once (EQ 16-byte loads issued back to back: one request for a whole sector when EQ = 4) into a
   // register queue, refilled every 2 EQ iterations; entries are popped by a static rotation (no dynamic register indexing).
+  // Entries32: the same registers hold twice the entries (QCAP = 4 EQ: a whole sector is 16 of them), popped a word at a time; the
+  // key variables stay unused (the key is cur + step, below).
   constexpr int EQ = G::ENTRY_Q;
+  constexpr int QCAP = EF::PER16 * EQ;   // entries per refill
   uint4 q[EQ > 0 ? EQ : 1];
   uint32_t q_left = 0;   // wave-uniform
 #define MSM_Q_REFILL(first_entry)                                                   \
   do {                                                                              \
-    const uint4* src_ = reinterpret_cast<const uint4*>(entries + (first_entry));    \
-    _Pragma("unroll") for (int j_ = 0; j_ < EQ; j_++) q[j_] = src_[j_];             \
+    if constexpr (EF::WORD32) {                                                     \
+      /* (as whole vectors: element-wise copies of the words came back as one more 8-byte load of the last two) */ \
+      const msm_u32x4_t* src_ = reinterpret_cast<const msm_u32x4_t*>(entries + (first_entry)); \
+      _Pragma("unroll") for (int j_ = 0; j_ < EQ; j_++) {                           \
+        const msm_u32x4_t v_ = src_[j_];                                            \
+        q[j_] = make_uint4(v_.x, v_.y, v_.z, v_.w);                                 \
+      }                                                                             \
+    } else {                                                                        \
+      const uint4* src_ = reinterpret_cast<const uint4*>(entries + (first_entry));  \
+      _Pragma("unroll") for (int j_ = 0; j_ < EQ; j_++) q[j_] = src_[j_];           \
+    }                                                                               \
   } while (0)
 #define MSM_Q_POP(key_out, val_out)                                                 \
   do {                                                                              \
-    key_out = q[0].y;                                                               \
     val_out = q[0].x;                                                               \
-    _Pragma("unroll") for (int j_ = 0; j_ < EQ; j_++) {                             \
-      q[j_].x = q[j_].z;                                                            \
-      q[j_].y = q[j_].w;                                                            \
-      if (j_ + 1 < EQ) {                                                            \
-        q[j_].z = q[j_ + 1].x;                                                      \
-        q[j_].w = q[j_ + 1].y;                                                      \
+    if constexpr (EF::WORD32) {                                                     \
+      _Pragma("unroll") for (int j_ = 0; j_ < EQ; j_++) {                           \
+        q[j_].x = q[j_].y;                                                          \
+        q[j_].y = q[j_].z;                                                          \
+        q[j_].z = q[j_].w;                                                          \
+        if (j_ + 1 < EQ) q[j_].w = q[j_ + 1].x;                                     \
+      }                                                                             \
+    } else {                                                                        \
+      key_out = q[0].y;                                                             \
+      _Pragma("unroll") for (int j_ = 0; j_ < EQ; j_++) {                           \
+        q[j_].x = q[j_].z;                                                          \
+        q[j_].y = q[j_].w;                                                          \
+        if (j_ + 1 < EQ) {                                                          \
+          q[j_].z = q[j_ + 1].x;                                                    \
+          q[j_].w = q[j_ + 1].y;                                                    \
+        }                                                                           \
       }                                                                             \
     }                                                                               \
   } while (0)
@@ -254,22 +349,42 @@ __global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate_glds(const uin
   if constexpr (EQ > 0) {
     // (entries past a lane's `end` belong to the next lane, or to the 64 bytes of slack behind the buffer; they are never used)
     if (end > beg) MSM_Q_REFILL(beg);
-    MSM_Q_POP(key_c, val_c);
-    MSM_Q_POP(key_n, val_n);
-    q_left = 2 * EQ - 2;
+    if constexpr (EF::WORD32) {
+      // (the first two words at once: the queue moves by two words as it does for one 64-bit entry)
+      val_c = q[0].x;
+      val_n = q[0].y;
+#pragma unroll
+      for (int j = 0; j < EQ; j++) {
+        q[j].x = q[j].z;
+        q[j].y = q[j].w;
+        if (j + 1 < EQ) {
+          q[j].z = q[j + 1].x;
+          q[j].w = q[j + 1].y;
+        }
+      }
+    } else {
+      MSM_Q_POP(key_c, val_c);
+      MSM_Q_POP(key_n, val_n);
+    }
+    q_left = QCAP - 2;
     if (q_left == 0) {
       if (end - beg > 2 && end > beg) MSM_Q_REFILL(beg + 2);
-      q_left = 2 * EQ;
+      q_left = QCAP;
     }
     if (end <= beg) key_c = key_n = KEY_NONE;
   } else if (end > beg) {
-    const uint2 e0 = entries[beg];
-    key_c = e0.y;
-    val_c = e0.x;
-    if (end - beg > 1) {
-      const uint2 e1 = entries[beg + 1];
-      key_n = e1.y;
-      val_n = e1.x;
+    if constexpr (EF::WORD32) {
+      val_c = entries[beg];
+      if (end - beg > 1) val_n = entries[beg + 1];
+    } else {
+      const uint2 e0 = entries[beg];
+      key_c = e0.y;
+      val_c = e0.x;
+      if (end - beg > 1) {
+        const uint2 e1 = entries[beg + 1];
+        key_n = e1.y;
+        val_n = e1.x;
+      }
     }
   }
   bool alive = end > beg;
@@ -282,7 +397,7 @@ __global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate_glds(const uin
   } while (0)
 #define MSM_GLDS_ISSUE(val, valid)                                \
   do {                                                            \
-    const int mine_ = (valid) ? (int)((((val) & IDX_MASK & MSM_ACC_IDX_AND)) << MSM_ACC_IDX_SHL) : 0; \
+    const int mine_ = (valid) ? (int)(((EF::index(val) & MSM_ACC_IDX_AND)) << MSM_ACC_IDX_SHL) : 0; \
     if constexpr (LANES == 1) {                                   \
       MSM_GLDS_ONE(0, 0x00);                                      \
       MSM_GLDS_ONE(1, 0x55);                                      \
@@ -336,18 +451,28 @@ __global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate_glds(const uin
       // covered by the s_waitcnt vmcnt(0) at the top of the next one (q_left is wave-uniform: every lane pops once per iteration)
       if (--q_left == 0) {
         if (add_now && end - e > 3) MSM_Q_REFILL(e + 3);
-        q_left = 2 * EQ;
+        q_left = QCAP;
       }
     } else if (add_now && end - e > 2) {
-      const uint2 e2 = entries[e + 2];
-      key_n = e2.y;
-      val_n = e2.x;
+      if constexpr (EF::WORD32) {
+        val_n = entries[e + 2];
+      } else {
+        const uint2 e2 = entries[e + 2];
+        key_n = e2.y;
+        val_n = e2.x;
+      }
     }
 #if MSM_ACC_PRIO == 2
     __builtin_amdgcn_s_setprio(0);
 #endif
     if (add_now) {
-      if (key != cur) {
+      // a run starts here: the key differs from the one before -- Entries32: the step is not 0 -- or the lane starts
+      bool new_run;
+      if constexpr (EF::WORD32)
+        new_run = k == 0 || e32_step(val) != 0;
+      else
+        new_run = key != cur;
+      if (new_run) {
         const bool lane_first = cur == KEY_NONE;
         if (cur != KEY_NONE) {
 #ifndef MSM_ACC_NO_FLUSH   // A/B only (profiles/r06_ab_flush.txt): defined = a finished run is not stored (wrong sums): what the bucket stores cost
@@ -355,12 +480,23 @@ __global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate_glds(const uin
 #endif
           first = false;
         }
-        cur = key;
+        if constexpr (EF::WORD32) {
+          // (the cold part of the flush: a load only at the lane's start and at an escape -- ~1 run in 1000 of a uniform input)
+          const uint32_t step = e32_step(val);
+          cur = (lane_first || step == E32_ESCAPE) ? entries_arg.run_keys[e] : cur + step;
+        } else {
+          cur = key;
+        }
         fresh = true;
         G::begin_run(acc);
         if constexpr (G::CARRY_IN) {
           // (rare: once per run, and only in the later chunks of a carried batch; the entry before the lane is read here, not kept in a register)
-          if (out.carry_in && !(lane_first && t > 0 && entries[beg - 1].y == key)) carry_begin_run<G>(out, key, acc, fresh, half);
+          // "my first run continues the previous lane's bucket": Entries32 says so in the lane's first step
+          if constexpr (EF::WORD32) {
+            if (out.carry_in && !(lane_first && e32_step(val) == 0)) carry_begin_run<G>(out, cur, acc, fresh, half);
+          } else {
+            if (out.carry_in && !(lane_first && t > 0 && entries[beg - 1].y == key)) carry_begin_run<G>(out, key, acc, fresh, half);
+          }
         }
       }
 #if MSM_ACC_PRIO == 1
@@ -368,7 +504,7 @@ __global__ void __launch_bounds__(256, G::ACC_WAVES) k_accumulate_glds(const uin
 #endif
       if (G::madd_loaded(acc, p, (val >> 31) != 0, fresh, md)) {
         // exceptional pair (short Weierstrass only): the record in LDS is already being overwritten, so fetch it again
-        const Base again = G::from_dev_lane(bases[val & IDX_MASK], half);
+        const Base again = G::from_dev_lane(bases[EF::index(val)], half);
         G::madd_same_x(acc, again, (val >> 31) != 0, md);
       }
 #if MSM_ACC_PRIO == 1

@@ -18,6 +18,15 @@
 //        a skewed input (all scalars equal: one segment holds everything) is spread over the chip like a uniform one; offsets
 //        again come from a (sub-job x bin) histogram matrix, not from atomics.  The last pass writes the full key into the
 //        high word: the output is the (key, value) array the accumulation walks, fully sorted by key.
+//        -- or, where Entries32 applies (msm_types.hpp: at most 2^26 pairs, base indices below 2^26, no tables; option "entries32"), HALF
+//        of it: one 32-bit word per entry, whose five spare bits carry the key's STEP from the entry before (0 = same bucket, 1..30
+//        buckets on, 31 = the key stands in run_keys).  The accumulation only ever asks "same bucket as the entry before?" and needs
+//        the number when it stores a run, so the keys need not travel per entry.  A fused block knows its segment's whole histogram
+//        before it scatters and derives every bin's distance to the previous non-empty bin from it; what it cannot know -- the last
+//        key of the segment before, or of another sub-job -- becomes an escape, and the key of every lane start (multiples of the
+//        accumulation's K, fixed before the grouping) is stored as well.  run_keys is sparse and lives in the upper half of the same
+//        output buffer, which the words leave empty.  Earlier levels keep their 8-byte entries (a 4-byte intermediate format measured
+//        nothing, profiles/r05_ab_group_compact.txt).
 //
 // Zero digits and bases flagged infinite produce NO entry (the count of real entries lives in device memory and the
 // accumulation reads it), so there are no sentinel keys any more.
@@ -34,6 +43,7 @@
 #include <algorithm>
 
 #include "digits.hpp"
+#include "msm_types.hpp"
 #include "partition_plan.hpp"
 
 namespace msm {
@@ -753,9 +763,21 @@ struct PassLds {
 // Scatter of the entries [beg, end) of one segment; the caller has set the cursors L.cur, zeroed L.cnt and passed a barrier:
 // LDS multisplit tile by tile, runs written contiguously; the next tile's entries are already in flight while the current one
 // is split.
+//
+// E32 (the last pass only): the output is Entries32 words (msm_types.hpp) instead of (value, key) pairs.  Thread b owns bin b in the
+// scan step of every tile, and `my_step` is what it still owes: the step of the bin's FIRST entry (1..30, or 31 with the key in
+// run_keys) while that entry has not been staged by this job, 0 afterwards or when the bin's run starts in another sub-job.  The
+// tile in which the bin's first entry leaves carries the step in the high half of L.tstart[b] (its low half, the staged slot of
+// the bin's first entry of the tile, is at most PART_PTILE), so the copy-out learns it with the one LDS read it compares its
+// slot with -- no more LDS than the 64-bit form, which the block has none to spare of.  The same thread writes the bin's key to
+// run_keys at every lane start (multiple of e32.lane_k) inside the bin's contiguous run of the tile: one division per bin and
+// tile, no modulo per entry.
+template <bool E32>
 __device__ __forceinline__ void pass_scatter_tiles(PassLds& L, const uint2* __restrict__ in, uint2* __restrict__ out, uint32_t beg, uint32_t end,
-                                                   const PassPlan& pp, uint32_t key_base) {
+                                                   const PassPlan& pp, uint32_t key_base, const PassE32& e32 = PassE32{}, uint32_t my_step = 0) {
   const uint32_t nb = 1u << pp.rb, shift = pp.rem - pp.rb, keepmask = (1u << shift) - 1;
+  uint32_t* const out32 = reinterpret_cast<uint32_t*>(out);
+  uint32_t* const run_keys = out32 + e32.rk_off;
   constexpr int PER = PART_PTILE / 1024;
   uint2 nxt[PER];
 #pragma unroll
@@ -794,7 +816,18 @@ __device__ __forceinline__ void pass_scatter_tiles(PassLds& L, const uint2* __re
       const uint32_t ex = block_excl_scan<false>(v, L.tmp, tot);
       if (threadIdx.x < nb) {
         const uint32_t c0 = L.cur[threadIdx.x];
-        L.tstart[threadIdx.x] = ex;
+        if constexpr (E32) {
+          uint32_t ts = ex;
+          if (v) {
+            ts |= my_step << 16;   // (0 once the bin's first entry has left)
+            my_step = 0;
+            // the bin's entries of this tile go to [c0, c0 + v): the lane starts among them
+            for (uint32_t q = e32_first_lane_start(c0, e32.lane_k); q - c0 < v; q += e32.lane_k) run_keys[q] = key_base + threadIdx.x;
+          }
+          L.tstart[threadIdx.x] = ts;
+        } else {
+          L.tstart[threadIdx.x] = ex;
+        }
 #ifdef PART_EXP_PS_ALIGNED   // diagnosis only (wrong output): every run starts on a 128-byte line
         L.dst[threadIdx.x] = (c0 & ~15u) - ex;
 #else
@@ -808,12 +841,20 @@ __device__ __forceinline__ void pass_scatter_tiles(PassLds& L, const uint2* __re
     lds_barrier();   // B
 #pragma unroll
     for (int k = 0; k < PER; k++)
-      if (where[k] != 0xffffffffu) L.stage[L.tstart[where[k] >> 16] + (where[k] & 0xffffu)] = ent[k];
+      if (where[k] != 0xffffffffu) L.stage[(E32 ? L.tstart[where[k] >> 16] & 0xffffu : L.tstart[where[k] >> 16]) + (where[k] & 0xffffu)] = ent[k];
     lds_barrier();   // C
     const uint32_t total = L.tstart[nb];
     for (uint32_t j = threadIdx.x; j < total; j += 1024) {
       uint2 e = L.stage[j];
       const uint32_t bin = e.y >> 16;
+      if constexpr (E32) {
+        // (the last pass: nothing is left below the bin, the key is key_base + bin)
+        const uint32_t ts = L.tstart[bin], pos = L.dst[bin] + j;
+        const uint32_t step = (ts & 0xffffu) == j ? ts >> 16 : 0u;
+        out32[pos] = e32_pack(e.x, step);
+        if (step == E32_ESCAPE) run_keys[pos] = key_base + bin;
+        continue;
+      }
       // leaving: after the last pass the key word is the full key, before it the bits the next pass will look at
       e.y = pp.last ? key_base + bin : (e.y & 0xffffu);
 #if defined(PART_EXP_PS_NOSTORE)
@@ -843,10 +884,16 @@ __device__ __forceinline__ void pass_scatter_tiles(PassLds& L, const uint2* __re
 //
 // What bounds the scatter is not LDS or issue but how many partially written 128-B lines the XCD's 4-MB L2 has to keep open
 // (bins x concurrent blocks): hence big tiles, one block per CU.
+//
+// E32: the last pass writes Entries32 words (pass_scatter_tiles).  A fused block knows the whole segment's histogram before it scatters:
+// the step of a bin's first entry is its distance to the previous non-empty bin of the segment (31 = the key stands in run_keys: a gap
+// above 30, and the segment's first non-empty bin).  A sub-job knows only its own rows: the sub-job whose row of `positions` still
+// equals the bin's start in the segment (the row of the segment's first sub-job) starts the bin's run, always with an escape.
+template <bool E32>
 __global__ void __launch_bounds__(1024, PART_PASS_OCC) k_pass_scatter(const uint2* __restrict__ in, const PartSeg* __restrict__ segs,
                                                           const uint32_t* __restrict__ subjob_first, PassPlan pp, uint32_t gen,
                                                           const uint32_t* __restrict__ positions, uint2* __restrict__ out,
-                                                          PartSeg* __restrict__ out_segs) {
+                                                          PartSeg* __restrict__ out_segs, PassE32 e32) {
   __shared__ PassLds L;
   const uint32_t nb = 1u << pp.rb, shift = pp.rem - pp.rb;
   if (blockIdx.x < gen) {
@@ -858,13 +905,15 @@ __global__ void __launch_bounds__(1024, PART_PASS_OCC) k_pass_scatter(const uint
       const PartSeg sg = segs[seg];
       if (part_fused_takes(sg.len)) continue;
       const uint32_t* row = positions + (size_t)j * nb;
+      uint32_t my_step = 0;
       lds_barrier();   // the previous sub-job's copy-out still reads L
       for (uint32_t b = threadIdx.x; b < nb; b += 1024) {
         L.cur[b] = row[b];
         L.cnt[b] = 0;
+        if constexpr (E32) my_step = row[b] == positions[(size_t)subjob_first[seg] * nb + b] ? E32_ESCAPE : 0u;   // (nb <= 1024: one bin per thread)
       }
       lds_barrier();
-      pass_scatter_tiles(L, in, out, beg, end, pp, sg.key_base);
+      pass_scatter_tiles<E32>(L, in, out, beg, end, pp, sg.key_base, e32, my_step);
     }
     return;
   }
@@ -878,6 +927,7 @@ __global__ void __launch_bounds__(1024, PART_PASS_OCC) k_pass_scatter(const uint
   }
   const uint32_t beg = sg.start, end = sg.start + sg.len;
   for (uint32_t b = threadIdx.x; b < nb; b += 1024) L.cnt[b] = 0;
+  uint32_t my_step = 0;
   lds_barrier();
   {
     // four loads in flight per thread
@@ -901,9 +951,29 @@ __global__ void __launch_bounds__(1024, PART_PASS_OCC) k_pass_scatter(const uint
       L.cnt[threadIdx.x] = 0;
       if (out_segs) out_segs[(size_t)s * nb + threadIdx.x] = PartSeg{beg + ex, v, sg.key_base + (threadIdx.x << shift), 0};
     }
+    if constexpr (E32) {
+      // distance of every non-empty bin to the non-empty bin before it: the waves' occupancy masks through L.tmp (free again: the scan
+      // ended with a barrier), the bin's own wave first, then the waves below it
+      const uint64_t m = __builtin_amdgcn_ballot_w64(v != 0);
+      const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+      if (ln == 0) {
+        L.tmp[2 * wv] = (uint32_t)m;
+        L.tmp[2 * wv + 1] = (uint32_t)(m >> 32);
+      }
+      lds_barrier();
+      if (v) {
+        const uint64_t below = m & ((1ull << ln) - 1);
+        int prev = below ? (int)(wv * 64 + 63 - __clzll((long long)below)) : -1;
+        for (int u = (int)wv - 1; u >= 0 && prev < 0; u--) {
+          const uint64_t mu = (uint64_t)L.tmp[2 * u] | ((uint64_t)L.tmp[2 * u + 1] << 32);
+          if (mu) prev = u * 64 + 63 - __clzll((long long)mu);
+        }
+        my_step = e32_step_of_gap(threadIdx.x - (uint32_t)prev, prev < 0);
+      }
+    }
   }
   lds_barrier();
-  pass_scatter_tiles(L, in, out, beg, end, pp, sg.key_base);
+  pass_scatter_tiles<E32>(L, in, out, beg, end, pp, sg.key_base, e32, my_step);
 }
 
 }  // namespace msm
@@ -975,6 +1045,61 @@ __global__ void __launch_bounds__(256) k_dbg_check_sorted(const uint2* __restric
     if (e.y >= key_limit) atomicAdd(&dbg[DBG_KEY_RANGE], 1u);
     const uint32_t idx = e.x & 0x7fffffffu;
     if (idx < idx_lo || idx >= idx_hi) atomicAdd(&dbg[DBG_VALUE_RANGE], 1u);
+  }
+}
+
+// The same checks on Entries32 words (msm_types.hpp), decoded the way the accumulation reads them: thread t walks lane t from
+// run_keys[t K].  On top of them the format's own invariants, counted with the unsorted keys: a lane start whose step is 0 continues
+// the previous lane's last key, and the key the walk arrives at is the one stored at the next lane start.
+__global__ void __launch_bounds__(256) k_dbg_check_sorted_e32(const uint32_t* __restrict__ words, const uint32_t* __restrict__ run_keys, uint32_t K,
+                                                              const uint32_t* __restrict__ totals, uint32_t key_limit, uint32_t idx_lo, uint32_t idx_hi,
+                                                              uint32_t* __restrict__ dbg) {
+  const uint32_t n = totals[0];
+  for (uint64_t beg = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * K; beg < n; beg += (uint64_t)gridDim.x * 256 * K) {
+    const uint32_t end = (uint32_t)(beg + K < n ? beg + K : n);
+    uint32_t key = run_keys[beg];
+    if (key >= key_limit) atomicAdd(&dbg[DBG_KEY_RANGE], 1u);
+    for (uint32_t i = (uint32_t)beg; i < end; i++) {
+      const uint32_t w = words[i];
+      if (i > beg) {
+        const uint32_t next = e32_next_key(key, w, run_keys, i);
+        if (next < key || (next == key) != (e32_step(w) == 0)) atomicAdd(&dbg[DBG_UNSORTED], 1u);
+        if (next >= key_limit) atomicAdd(&dbg[DBG_KEY_RANGE], 1u);
+        key = next;
+      }
+      const uint32_t idx = e32_index(w);
+      if (idx < idx_lo || idx >= idx_hi) atomicAdd(&dbg[DBG_VALUE_RANGE], 1u);
+    }
+    if (end < n) {
+      const uint32_t w = words[end], stored = run_keys[end];
+      const uint32_t step = e32_step(w);
+      const bool ok = step == 0 ? stored == key : (stored > key && (step == E32_ESCAPE || stored == key + step));
+      if (!ok) atomicAdd(&dbg[DBG_UNSORTED], 1u);
+    }
+  }
+}
+
+// ... and the planted violation: the keys of the first two neighbouring entries of different keys change places (both become escapes,
+// and so does the entry behind them, which keeps its key)
+__global__ void k_dbg_corrupt_e32(uint32_t* __restrict__ words, uint32_t* __restrict__ run_keys, const uint32_t* __restrict__ totals) {
+  const uint32_t n = totals[0];
+  if (n < 2) return;
+  uint32_t key = run_keys[0];
+  for (uint32_t i = 0; i + 1 < n; i++) {
+    const uint32_t next = e32_next_key(key, words[i + 1], run_keys, i + 1);
+    if (next != key) {
+      if (i + 2 < n) {
+        const uint32_t after = e32_next_key(next, words[i + 2], run_keys, i + 2);
+        words[i + 2] = e32_pack(words[i + 2], E32_ESCAPE);
+        run_keys[i + 2] = after;
+      }
+      words[i] = e32_pack(words[i], E32_ESCAPE);
+      run_keys[i] = next;
+      words[i + 1] = e32_pack(words[i + 1], E32_ESCAPE);
+      run_keys[i + 1] = key;
+      return;
+    }
+    key = next;
   }
 }
 
@@ -1087,8 +1212,12 @@ inline int part_run(const uint32_t* d_scalars, const uint8_t* d_inf, const PartP
       hipLaunchKernelGGL(k_pass_scan, dim3(pp.nsegs), dim3(1024), 0, st, b.segs[seg_cur], b.subjob_first, pp, b.counts, out_segs);
       PART_MARK("pass_scan");
     }
-    hipLaunchKernelGGL(k_pass_scatter, dim3(gen + pp.nsegs), dim3(1024), 0, st, b.entries[cur], b.segs[seg_cur], b.subjob_first, pp, gen, b.counts,
-                       b.entries[cur ^ 1], out_segs);
+    if (pp.last && b.e32_lane_k)
+      hipLaunchKernelGGL(k_pass_scatter<true>, dim3(gen + pp.nsegs), dim3(1024), 0, st, b.entries[cur], b.segs[seg_cur], b.subjob_first, pp, gen, b.counts,
+                         b.entries[cur ^ 1], out_segs, PassE32{b.e32_lane_k, e32_run_keys_offset(entries)});
+    else
+      hipLaunchKernelGGL(k_pass_scatter<false>, dim3(gen + pp.nsegs), dim3(1024), 0, st, b.entries[cur], b.segs[seg_cur], b.subjob_first, pp, gen, b.counts,
+                         b.entries[cur ^ 1], out_segs, PassE32{});
     PART_MARK("pass_scatter");
     cur ^= 1;
     rem -= rb[i];
@@ -1103,8 +1232,15 @@ inline int part_run(const uint32_t* d_scalars, const uint8_t* d_inf, const PartP
   {
     const uint32_t key_limit = p.bsets * p.half;
     const uint32_t idx_hi = p.idx0 + p.n + (p.levels - 1) * p.table_stride;
-    if (getenv("MI355_MSM_DEBUG_CORRUPT")) hipLaunchKernelGGL(k_dbg_corrupt, dim3(1), dim3(1), 0, st, b.entries[cur], b.totals);
-    hipLaunchKernelGGL(k_dbg_check_sorted, dim3(2048), dim3(256), 0, st, b.entries[cur], b.totals, key_limit, p.idx0, idx_hi, dbg);
+    if (b.e32_lane_k) {
+      uint32_t* const words = reinterpret_cast<uint32_t*>(b.entries[cur]);
+      uint32_t* const run_keys = words + e32_run_keys_offset(entries);
+      if (getenv("MI355_MSM_DEBUG_CORRUPT")) hipLaunchKernelGGL(k_dbg_corrupt_e32, dim3(1), dim3(1), 0, st, words, run_keys, b.totals);
+      hipLaunchKernelGGL(k_dbg_check_sorted_e32, dim3(2048), dim3(256), 0, st, words, run_keys, b.e32_lane_k, b.totals, key_limit, p.idx0, idx_hi, dbg);
+    } else {
+      if (getenv("MI355_MSM_DEBUG_CORRUPT")) hipLaunchKernelGGL(k_dbg_corrupt, dim3(1), dim3(1), 0, st, b.entries[cur], b.totals);
+      hipLaunchKernelGGL(k_dbg_check_sorted, dim3(2048), dim3(256), 0, st, b.entries[cur], b.totals, key_limit, p.idx0, idx_hi, dbg);
+    }
     if (p.fold)
       hipLaunchKernelGGL((k_dbg_count_digits<FR, MODE, true>), dim3(part_ceil_div(p.n, 256)), dim3(256), 0, st, d_scalars, d_inf, p, dbg);
     else

@@ -206,6 +206,14 @@ struct PartBuffers {
   uint32_t* counts;
   uint32_t* totals;          // [0] = real entries (read by the accumulation), [1] = sub-jobs of the pass in flight
   uint32_t* wide_flag;       // PartPlan::wide: set to 1 when a scalar has a bit at or above wide_top (never cleared here)
+  uint32_t e32_lane_k;       // != 0: the last pass writes Entries32 words (msm_types.hpp) for walking lanes of this many entries; the caller
+                             // has checked e32_applies, and each entry buffer holds 128 bytes more than windows * n entries
+};
+
+// What the last pass needs to write Entries32 (an argument of k_pass_scatter, filled by part_run): the lane length K of the accumulation
+// and where run_keys starts in the output buffer, in words (e32_run_keys_offset).  Zero for the 64-bit form.
+struct PassE32 {
+  uint32_t lane_k, rk_off;
 };
 
 

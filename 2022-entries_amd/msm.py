@@ -714,7 +714,8 @@ class MultiScalarMultContext:
         """Context state: "twisted_edwards", "twisted_edwards_fallbacks", "twisted_edwards_demotions", "oom_backoffs", "chunk_cap",
         "device", "shards", "rccl_exchanges", "peer_stagings", "bases", "table_levels", "table_window_bits", "base_bytes", "assume_subgroup",
         "carry", "precompute", "g2_paired", "anchor", "anchored_window", "anchor_sums", "anchor_sum_us", "anchor_wide", "anchor_wide_active", "anchor_wide_fallbacks",
-        "anchor_wide_demotions", and the geometry of the most recent chunk: "bucket_windows", "l1_bits", "l1_bins", "group_passes",
+        "anchor_wide_demotions", "entries32", "entries32_active" (the most recent chunk's sorted entries were 32-bit words with run steps),
+        and the geometry of the most recent chunk: "bucket_windows", "l1_bits", "l1_bins", "group_passes",
         and how its buckets were reduced: "reduce_path" (0 recursive chunked levels only, 1 direct scan on the buckets, 2 one chunked level
         then a scan on full rows, 3 the same on rows padded to a power of two), "reduce_chunks" (chunks per bucket set on the first
         level, T0) and "reduce_row" (elements of a scan row).  A sharded context reports the largest over its shards."""

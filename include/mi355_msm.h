@@ -266,6 +266,12 @@ RustError mi355_msm_job_wait(mi355_msm_job* job);
  * pairs of BLS12-377 G1, -1.8 % of G2 (profiles/ab_anchor_wide.txt).  A scalar with a bit at or above bits(r) = 253 set is not read
  * that far: the device reports it and the chunk -- of a carried batch: the batch -- runs again without the option, so any 256-bit scalar
  * stays legal; after two such repeats in a row the context stops using it until the option is set again.
+ * "entries32" (default 1; 0 = (value, key) pairs of 8 bytes): the last grouping pass writes the sorted entries as one 32-bit word each --
+ * base index, sign, and in five spare bits the step of the bucket key from the entry before -- with the key itself stored only where a
+ * reader cannot derive it (gaps of more than 30 buckets, the first run of a grouping segment, the start of every accumulation lane).
+ * Half the bytes written by the last pass and read by the accumulation: -1.5 % at 2^26 pairs of BLS12-377 G1, -0.9 % of BLS12-381 G1
+ * (profiles/ab_entries32.txt).  Applies to chunks of at most 2^26 pairs whose base indices lie below 2^26, without precomputed tables;
+ * every other chunk keeps the 64-bit format through the same kernels.  Results never depend on it.
  * "carry" (default 1): a batch that runs as several chunks (max_chunk, the memory budget, the pieces of a host-scalar batch) carries
  * ONE bucket array through them -- every chunk uses the window size of the whole batch and only the last one reduces; 0 = every
  * chunk reduces its own buckets and the partial sums are added on the host.  "first_piece_div" (default 13; 4 with carry = 0): the
@@ -298,6 +304,7 @@ RustError mi355_msm_set_option(mi355_msm_ctx* ctx, const char* key, long value);
  * recent chunk, 0 = plain digits), "anchor_sums" (sums of bases computed so far), "anchor_sum_us" (host time the most recent run spent on one),
  * "anchor_wide" (the option; 0 once the context has stopped using it), "anchor_wide_active" (the most recent chunk ran with it),
  * "anchor_wide_fallbacks" (chunks / batches repeated without it), "anchor_wide_demotions",
+ * "entries32" (the option), "entries32_active" (the most recent chunk's sorted entries were 32-bit words),
  * "reduce_path" (how the most recent chunk's buckets were reduced: 0 recursive chunked levels only, 1 direct scan on the buckets, 2 one
  * chunked level then a scan on full rows, 3 the same on rows padded to a power of two), "reduce_chunks" (chunks per bucket set on the
  * first level) and "reduce_row" (elements of a scan row),

@@ -10,6 +10,7 @@ them are listed as `cold`).
 
     python tools/isa_histogram.py                 # the three product kernels + the 14 x 28 Edwards law for comparison
     python tools/isa_histogram.py te29 --json     # one law, machine-readable
+    python tools/isa_histogram.py te29 --entries32   # the instantiation that reads 32-bit entries with run steps (csrc/msm_types.hpp)
 """
 import json
 import os
@@ -56,9 +57,12 @@ def classify(op):
     return "other"
 
 
-def compile_kernel(law, extra_flags=()):
+def compile_kernel(law, extra_flags=(), entries32=False):
     tmpl, args, _ = LAWS[law]
-    inst = "template __global__ void k_accumulate_glds<%s>(const uint2*, const uint32_t*, uint32_t, %s, uint32_t, uint32_t*);" % (tmpl, args)
+    if entries32:
+        inst = "template __global__ void k_accumulate_glds<%s, Entries32>(Entries32Ptr, const uint32_t*, uint32_t, %s, uint32_t, uint32_t*);" % (tmpl, args)
+    else:
+        inst = "template __global__ void k_accumulate_glds<%s>(const uint2*, const uint32_t*, uint32_t, %s, uint32_t, uint32_t*);" % (tmpl, args)
     src = '#include "%s/2022-entries_amd/csrc/msm_kernels.hpp"\nnamespace msm {\n%s\n}\n' % (ROOT, inst)
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "acc.hip"), "w").write(src)
@@ -136,16 +140,16 @@ def loop_histogram(body):
     return hot, cold_h, total, (lo, hi, len(instrs))
 
 
-def report(law, as_json=False, extra_flags=()):
-    body, res = compile_kernel(law, extra_flags)
+def report(law, as_json=False, extra_flags=(), entries32=False):
+    body, res = compile_kernel(law, extra_flags, entries32)
     hot, cold, total, (lo, hi, n) = loop_histogram(body)
     valu = sum(v for k, v in hot.items() if k in ("mad", "shift", "add64", "logic", "addsub", "mul_lo", "select", "cmp", "mov", "valu_other"))
-    out = {"law": law, "what": LAWS[law][2], "resources": res, "loop_instructions": hi - lo, "static_instructions": n, "hot": hot, "cold": cold,
+    out = {"law": law, "what": LAWS[law][2] + (", Entries32" if entries32 else ""), "resources": res, "loop_instructions": hi - lo, "static_instructions": n, "hot": hot, "cold": cold,
            "valu_per_addition": valu, "mad_per_addition": hot.get("mad", 0), "non_mad_valu": valu - hot.get("mad", 0),
            "mad_share": round(hot.get("mad", 0) / valu, 4) if valu else None}
     if as_json:
         return out
-    print("%s -- %s" % (law, LAWS[law][2]))
+    print("%s -- %s" % (law, out["what"]))
     print("  VGPRs %s, scratch %s B/lane, %s waves/SIMD; loop = %d of %d static instructions" % (res["vgprs"], res["scratch"], res["occupancy"], hi - lo, n))
     print("  per trip (one mixed addition), hot path:   VALU %d = MAD %d + other %d   (MAD share %.3f)" % (valu, out["mad_per_addition"], out["non_mad_valu"], out["mad_share"]))
     print("    " + "  ".join("%s %d" % (k, hot[k]) for k, _ in CLASSES if k in hot))
@@ -159,6 +163,6 @@ if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     as_json = "--json" in sys.argv
     laws = args or ["te29", "te28", "sw381", "sw377", "g2p377", "g2p381"]
-    outs = [report(l, as_json) for l in laws]
+    outs = [report(l, as_json, entries32="--entries32" in sys.argv) for l in laws]
     if as_json:
         print(json.dumps(outs, indent=1))

@@ -3,6 +3,8 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++20 tools/partition_test.hip -o tools/partition_test
 //   tools/partition_test [npow=20] [c=0 (auto)] [levels=0 (no tables) | 1 (a table level per window) | k (k levels: windows g, g + G, ...
 //                        share bucket set g)] [pattern=0 uniform|1 all-equal|2 small|3 zeros+ones] [reps=3]
+//                        [e32_K=0 (64-bit entries) | K: the last pass writes Entries32 words for lanes of K entries (msm_types.hpp), which
+//                        are decoded the way the accumulation walks them before they are compared]
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -26,6 +28,7 @@ int main(int argc, char** argv) {
   const bool shared = levels_arg != 0;
   const int pattern = argc > 4 ? atoi(argv[4]) : 0;
   const int reps = argc > 5 ? atoi(argv[5]) : 3;
+  const uint32_t e32_K = argc > 6 ? (uint32_t)atoi(argv[6]) : 0;
   const uint32_t n = npow >= 0 ? (1u << npow) : (uint32_t)(-npow);   // negative: a literal (ragged) count
   if (!c) c = npow >= 24 ? 20 : (npow >= 16 ? 14 : 9);
   const uint32_t windows = (257 + c - 1) / c;
@@ -89,7 +92,11 @@ int main(int argc, char** argv) {
   CHECK(hipMemcpy(d_sc, sc.data(), (size_t)n * 32, hipMemcpyHostToDevice));
   CHECK(hipMemcpy(d_inf, inf.data(), nbases, hipMemcpyHostToDevice));
   PartBuffers b{};
-  CHECK(hipMalloc(&b.entries[0], E * 8 + 64)); CHECK(hipMalloc(&b.entries[1], E * 8 + 64));
+  CHECK(hipMalloc(&b.entries[0], E * 8 + 128)); CHECK(hipMalloc(&b.entries[1], E * 8 + 128));
+  if (e32_K) {
+    if (e32_K % 4 || !e32_applies(idx0, n, shared ? levels : 1)) { fprintf(stderr, "Entries32 does not apply (K %% 4, tables, or indices >= 2^26)\n"); return 2; }
+    b.e32_lane_k = e32_K;
+  }
   CHECK(hipMalloc(&b.matrix, sz.matrix)); CHECK(hipMalloc(&b.partial, sz.partial));
   CHECK(hipMalloc(&b.segs[0], sz.segs_a)); CHECK(hipMalloc(&b.segs[1], sz.segs_b));
   CHECK(hipMalloc(&b.subjob_first, sz.subjob_first)); CHECK(hipMalloc(&b.counts, sz.counts)); CHECK(hipMalloc(&b.totals, sz.totals));
@@ -129,6 +136,20 @@ int main(int argc, char** argv) {
   int bad = 0;
   if (model) {
     std::vector<uint2> out(totals[0]);
+    if (e32_K) {
+      // the accumulation's walk: lane t starts from run_keys[t K], a step moves the key on, an escape reads it
+      const uint32_t rk_off = e32_run_keys_offset(E);
+      std::vector<uint32_t> raw((size_t)rk_off + totals[0]);
+      CHECK(hipMemcpy(raw.data(), b.entries[res], raw.size() * 4, hipMemcpyDeviceToHost));
+      const uint32_t* run_keys = raw.data() + rk_off;
+      uint64_t escapes = 0;
+      for (uint32_t i = 0, key = 0; i < totals[0]; i++) {
+        key = (i % e32_K == 0) ? run_keys[i] : e32_next_key(key, raw[i], run_keys, i);
+        escapes += e32_step(raw[i]) == E32_ESCAPE;
+        out[i] = make_uint2((raw[i] & 0x80000000u) | e32_index(raw[i]), key);
+      }
+      printf("Entries32: K = %u, %llu escapes in %u entries\n", e32_K, (unsigned long long)escapes, totals[0]);
+    } else
     CHECK(hipMemcpy(out.data(), b.entries[res], (size_t)totals[0] * 8, hipMemcpyDeviceToHost));
     if (totals[0] != want_total) { printf("FAIL: %u entries, model has %llu\n", totals[0], (unsigned long long)want_total); bad++; }
     std::map<uint32_t, Agg> got;
